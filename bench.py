@@ -5,7 +5,12 @@ One "step" = one iteration of the reference's DDIM loop (ddim.py:139-160) for a 
 classifier-free guidance: both U-Net evaluations (cond + uncond, ddim.py:177-178) + the fused CFG-rescale /
 DDIM update. Synthetic inputs resident in HBM, PRNG-recipe weights of the NS32 architecture.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f16|bf16|parity] [--batch 64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f16|bf16|parity] [--batch 64] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` = milliseconds of one timed step).
+--dump-outputs DIR writes what the last timed step returns to its caller (x_prev, pred_x0) as DIR/<name>.npy, float32, from seeded
+inputs: two builds compare output for output. --full adds every side measurement below (roofline, the other numerics modes, REF128,
+64x64 latents, end-to-end sampling run, training step, CPU baseline and oracle deviations); the --no-* / --ref128-batch options trim it.
 
 `value` / `dtype` are the fastest numerics mode that meets north_star's tolerance (1e-3 relative to the fp32 reference, as rel-L2) on the
 MEASURED deviation, single forward and over the whole DDIM-50 loop: fp16 single-product operands with fp32 accumulation (the reference is
@@ -226,7 +231,8 @@ def ref128_leg(dev, precision, B, steps=6, warmup=2, spatial_transformer=False):
 
 
 def run_steps(ld, xT, cond, unc, warmup, steps, world):
-    """W untimed + K timed denoising steps (hipGraph replay). Returns (seconds for K steps, final latents)."""
+    """W untimed + K timed denoising steps (hipGraph replay). Returns (seconds for K steps, final latents). Past the 50th step the loop
+    starts a new DDIM-50 run from the same x_T (index and latents reset), so any W + K samples what W + K - 50 would, never its own output."""
     from stedm_amd.ddim import DDIMSampler, StepGraph
     smp = DDIMSampler(ld, use_graph=True)
     smp.make_schedule(50, ddim_eta=0.0, verbose=False)      # BASELINE config 3: DDIM-50, eta 0, cfg 1.5
@@ -240,7 +246,7 @@ def run_steps(ld, xT, cond, unc, warmup, steps, world):
         left = n - 2
         for _ in range(max(0, warmup - 1)):
             if left < 0:
-                sg.reset(n - 1); left = n - 1
+                sg.reset(n - 1); img.copy_(xT); left = n - 1
             sg.replay(); left -= 1
         torch.cuda.current_stream().synchronize()
         if world > 1:
@@ -249,15 +255,17 @@ def run_steps(ld, xT, cond, unc, warmup, steps, world):
         t0 = time.perf_counter()
         for _ in range(steps):
             if left < 0:
-                sg.reset(n - 1); left = n - 1
+                sg.reset(n - 1); img.copy_(xT); left = n - 1
             sg.replay(); left -= 1
         torch.cuda.synchronize()
         run_steps.own_seconds = time.perf_counter() - t0          # this rank's K steps alone (before the closing barrier)
+        run_steps.pred_x0 = sg.pred_x0                            # the last step's x0 estimate (x_prev is the returned latents)
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
     sg.join()
+    ld.model.diffusion_model.check_f16_range("bench.py's denoising steps")     # fp16 modes: raise rather than time steps run through an inf
     return dt, img
 
 
@@ -461,6 +469,21 @@ def csrc_fingerprint():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(path, arrays, limit=64 << 20):
+    """arrays: name -> tensor with samples along dim 0, all with the same number of samples. Writes <path>/<name>.npy in float32; above
+    `limit` bytes in all, the same seeded sample of rows of every array (sorted sample indices), so two runs stay comparable row for row."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(4 * v.numel() for v in arrays.values())
+    rows = None
+    if total > limit:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:n * limit // total].sort().values
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), (v if rows is None else v[rows]).numpy())
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` outside a launcher: start N rank processes of this script (what torch.distributed.run does for
     train_diff.py:75 / predict_diff.py:86 in the reference) and return their exit code. Runs before anything initialises HIP."""
@@ -539,7 +562,12 @@ def main():
     ap.add_argument("--no-parity-leg", action="store_true")
     ap.add_argument("--no-train-leg", action="store_true")
     ap.add_argument("--no-e2e-leg", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (x_prev, pred_x0) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement (roofline, other modes and shapes, training step, "
+                                                        "sampling run, CPU baseline); a plain run times the headline step alone")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -581,6 +609,12 @@ def main():
         from stedm_amd import parallel as par
         gathered = par.all_gather_samples(final, B * world)                # prediction-side RCCL all-gather of the samples
         assert gathered.shape[0] == B * world and bool(torch.isfinite(gathered).all())
+    if args.dump_outputs:
+        outputs = {"x_prev": final, "pred_x0": run_steps.pred_x0}
+        if world > 1:
+            outputs = {"x_prev": gathered, "pred_x0": par.all_gather_samples(run_steps.pred_x0, B * world)}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
     ranks_seen = torch.distributed.get_world_size() if world > 1 else 1
     dt = float(t.item())
     steps_per_s = world * args.steps / dt
@@ -588,6 +622,25 @@ def main():
 
     out = None
     if rank == 0:
+        # whole-step figure against the MFMA peak: reference-equivalent = the FLOPs of the reference's two full forwards per step
+        # (what a user gets per second, in the reference's currency)
+        step_tflops = 2 * B * GFLOP_PER_SAMPLE_FORWARD / 1e3 / (ms_per_step * 1e-3) * 1.0
+        out = {
+            "metric": "U-Net denoising steps/sec (32x32x4 latent, bs=64)", "value": round(steps_per_s, 3), "unit": "steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": ld.model.diffusion_model.precision.label,
+            "data": "synthetic",
+            "config": {"workload": "HER2-style DDIM-50 + CFG 1.5 (rescale 0.7) denoising step, NS32 U-Net (234.6M params, "
+                                   "random-init PRNG weights), 32x32x4 latents + 3-ch layout concat, style vector 512",
+                       "batch_per_gpu": B, "global_batch": B * world, "latent": "32x32x4", "cfg": "cond+uncond per step",
+                       "parallelism": f"dp{world} (independent latents, no in-loop collective)"},
+            "sample_steps_per_s": round(steps_per_s * B, 1),
+            "rccl_ranks": ranks_seen,
+            "ms_per_step_by_rank": rank_ms,
+            "step_reference_equivalent_tflops": round(step_tflops, 1),
+            "step_reference_equivalent_frac_of_mfma_peak": round(step_tflops / PEAK_MFMA_TFLOPS, 4),
+        }
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (conv_igemm): live HIP-event timing of every launch of one eager step
         from stedm_amd.ddim import DDIMSampler, StepGraph
         smp = DDIMSampler(ld)
@@ -629,28 +682,11 @@ def main():
                     "convolution_only": {"achieved": round(cs2["tflops"], 2), "frac": round(cs2["tflops"] / PEAK_MFMA_TFLOPS, 4),
                                          "conv_ms_per_step": round(cs2["total_ms"] / 2, 3),
                                          "what": "the same launches with every riding GroupNorm run as its own launch outside the bracket"}}
-        # whole-step figures against the same peak: (a) reference-equivalent = the FLOPs of the reference's two full forwards per step
-        # (what a user gets per second, in the reference's currency); (b) executed = the conv FLOPs the hardware really runs per step
-        # (shared encoder evaluated once, sub-pixel upsample at 4/9 of the MACs): the honest MFMA utilisation of the whole step
-        step_tflops = 2 * B * GFLOP_PER_SAMPLE_FORWARD / 1e3 / (ms_per_step * 1e-3) * 1.0
+        # executed = the conv FLOPs the hardware really runs per step (shared encoder evaluated once, sub-pixel upsample at 4/9 of the MACs):
+        # the honest MFMA utilisation of the whole step
         exec_tflops = cs["flops_per_launch"] * (cs["launches"] // 2) / 1e12 / (ms_per_step * 1e-3)
-        out = {
-            "metric": "U-Net denoising steps/sec (32x32x4 latent, bs=64)", "value": round(steps_per_s, 3), "unit": "steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": ld.model.diffusion_model.precision.label,
-            "data": "synthetic",
-            "config": {"workload": "HER2-style DDIM-50 + CFG 1.5 (rescale 0.7) denoising step, NS32 U-Net (234.6M params, "
-                                   "random-init PRNG weights), 32x32x4 latents + 3-ch layout concat, style vector 512",
-                       "batch_per_gpu": B, "global_batch": B * world, "latent": "32x32x4", "cfg": "cond+uncond per step",
-                       "parallelism": f"dp{world} (independent latents, no in-loop collective)"},
-            "sample_steps_per_s": round(steps_per_s * B, 1),
-            "rccl_ranks": ranks_seen,
-            "ms_per_step_by_rank": rank_ms,
-            "step_reference_equivalent_tflops": round(step_tflops, 1),
-            "step_reference_equivalent_frac_of_mfma_peak": round(step_tflops / PEAK_MFMA_TFLOPS, 4),
-            "step_executed_conv_tflops": round(exec_tflops, 1), "step_executed_frac_of_mfma_peak": round(exec_tflops / PEAK_MFMA_TFLOPS, 4),
-            "roofline": roofline,
-        }
+        out.update({"step_executed_conv_tflops": round(exec_tflops, 1), "step_executed_frac_of_mfma_peak": round(exec_tflops / PEAK_MFMA_TFLOPS, 4),
+                    "roofline": roofline})
         if not args.no_parity_leg and world == 1:
             del sg, smp
             # the other numerics modes on the same workload, batch, graph, steps and warm-up as the headline
@@ -952,7 +988,7 @@ def main():
             out["cpu_baseline"] = None
         else:
             out["cpu_baseline"] = "n/a (world > 1): the CPU oracle is timed on rank 0 of the N = 1 run only"
-    if world > 1 and not args.no_train_leg:
+    if world > 1 and args.full and not args.no_train_leg:
         # the training half of north_star on N ranks (train_diff.py:75-76: DDP over the ranks, one process per GPU): BASELINE config 2's step
         # at the per-GPU batch — forward + L1 + backward with the gradient buckets all-reduced over RCCL while the backward still runs, then
         # fused AdamW + EMA on the rank-averaged gradients. Timed like the headline: barrier + synchronize on both sides, max over ranks.

@@ -226,7 +226,7 @@ def test_bench_gpus2_self_launch_on_one_device(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(STEDM_BENCH_ONE_DEVICE="1", STEDM_BENCH_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--no-parity-leg", "--no-e2e-leg", "--batch", "16"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -245,6 +245,38 @@ def test_bench_gpus2_self_launch_on_one_device(dev):
     assert tl["n_gpus"] == 2 and tl["global_batch"] == 32 and len(tl["ms_by_rank"]) == 2 and tl["ms"] >= max(tl["ms_by_rank"]) - 1e-2
     assert tl["overlapped_all_reduces"] >= tl["buckets"] and tl["weights_equal_across_ranks"] is True
     assert abs(tl["samples_per_s"] - 32 / (tl["ms"] * 1e-3)) < 1e-2 * tl["samples_per_s"]
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_one(dev, tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line alone, times exactly --steps steps, and --dump-outputs writes what the
+    last timed step returned (x_prev, pred_x0): bitwise what the same steps give in this process from the same seeded inputs, and what
+    50 steps more give (past the DDIM-50 schedule the loop samples again from x_T: finite at any --steps, not its own output re-noised)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "8",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["dtype"] == "f16" and line["higher_is_better"] is True
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+    assert "roofline" not in line and "cpu_baseline" not in line and "train_step" not in line
+    ld = bench.build_model(dev, "f16")
+    xT, cond, unc = bench.synth_inputs(dev, 8, 0)
+    for steps in (3, 53):
+        _, final = bench.run_steps(ld, xT, cond, unc, 2, steps, 1)
+        for name, want in (("x_prev", final), ("pred_x0", bench.run_steps.pred_x0)):
+            got = np.load(tmp_path / (name + ".npy"))
+            assert got.dtype == np.float32 and got.shape == (8, 4, 32, 32) and np.isfinite(got).all()
+            assert np.array_equal(got, want.float().cpu().numpy()), (name, steps)
+    del ld
+    torch.cuda.empty_cache()
 
 
 _RCCL_ONE_RANK = r"""

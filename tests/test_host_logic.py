@@ -210,3 +210,21 @@ def test_batch_prefetcher_interface_without_gpu():
         pytest.skip("GPU present: covered by tests/test_gpu_sampler.py::test_batch_prefetcher_overlaps_and_preserves_data")
     with pytest.raises(Exception):
         BatchPrefetcher("cuda:0")
+
+
+def test_bench_dump_outputs_caps_size_with_a_seeded_row_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per output, whole arrays while they fit in 64 MB, above that the same seeded rows of every
+    array (sorted), identical from call to call so that two builds compare output for output."""
+    import bench
+    a = torch.arange(3000 * 4 * 32 * 32, dtype=torch.float64).reshape(3000, 4, 32, 32)
+    b = -a
+    bench.dump_outputs(str(tmp_path / "small"), {"x_prev": a[:64], "pred_x0": b[:64]})
+    x = np.load(tmp_path / "small" / "x_prev.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, a[:64].float().numpy())
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), {"x_prev": a, "pred_x0": b})
+    x1, p1 = np.load(tmp_path / "big1" / "x_prev.npy"), np.load(tmp_path / "big1" / "pred_x0.npy")
+    assert x1.nbytes + p1.nbytes <= 64 << 20 and x1.shape[0] == 2048 and x1.dtype == np.float32
+    rows = x1[:, 0, 0, 0].astype(np.int64) // (4 * 32 * 32)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(p1, -x1)
+    assert np.array_equal(x1, np.load(tmp_path / "big2" / "x_prev.npy"))

@@ -3,7 +3,7 @@
 # and profiles/traffic.json (run here, in the repo root).
 TAG=${1:-r04}
 S="rocprofv3 --kernel-trace --stats --output-format csv --"
-B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity-leg --no-train-leg --no-e2e-leg"
+B="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-parity-leg --no-train-leg --no-e2e-leg"
 R=${TAG#r}; R="Round $((10#$R))"
 python tools/stats_md.py gpurun_out/prof_${TAG}_step ${TAG}_step "$R, denoising step (f16 headline mode, B = 64 CFG step)" "$S $B" 4 "denoising step" ddim_step 5 | tail -1
 python tools/stats_md.py gpurun_out/prof_${TAG}_parity ${TAG}_parity "$R, denoising step in parity mode (f16 x 3)" "$S $B --precision parity" 4 "denoising step" ddim_step 5 | tail -1

@@ -6,7 +6,7 @@ TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity-leg --no-train-leg --no-e2e-leg --ref128-batch 0"
+B="python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-parity-leg --no-train-leg --no-e2e-leg --ref128-batch 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_stepA -o run -- $B > $O/prof_${TAG}_stepA.log 2>&1 && echo A ok
 for kv in "$@"; do export "$kv"; done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_stepB -o run -- $B > $O/prof_${TAG}_stepB.log 2>&1 && echo B ok
