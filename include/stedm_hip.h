@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 12
+#define STEDM_ABI_VERSION 13
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -565,6 +565,16 @@ int stedm_q_sample(const float* x0, const float* noise, const int64_t* t, const 
  * first_id + row. Philox4x32-10, counter {element / 4, stream, 0x4E524D4C, 0}, key {seed (low 32 bits), sample id}; Box-Muller on word
  * pairs (the parity tests hold a numpy restatement of this definition). */
 int stedm_philox_normal(float* out, int rows, int n, const long* sample_ids, int first_id, unsigned long long seed, unsigned stream, void* stream_);
+/* Masked DDIM (ddim.py:143-146), before the U-Net call of a step: img = q_sample(x0, t) * mask + (1 - mask) * img, in place on img
+ * [B][C][HW] fp32; q_sample = ddpm.py:277-280 with sqrt_ac[t[b]] / sqrt_1mac[t[b]] gathered from the fp32 schedule buffers (t: DEVICE int64
+ * [B], e.g. the buffer stedm_step_set_t fills). x0 [B][C][HW]. mask: element (b, c, p) at mask[b * mask_bstride + c * mask_cstride + p];
+ * mask_cstride is 0 (one plane for every channel) or HW, mask_bstride 0 (one mask for the batch) or the mask's per-sample size.
+ * noise [B][C][HW] N(0, 1), or NULL: drawn in the kernel as row first_id + b of stedm_philox_normal with stream 0x8000 + *step_idx
+ * (step_idx: DEVICE int32, so that every replay of a captured step draws new noise; the same bits as stedm_philox_normal). mask == 0
+ * leaves img unchanged bit for bit. */
+int stedm_ddim_mask_blend(float* img, const float* x0, const float* mask, long mask_bstride, long mask_cstride, const float* noise,
+                          const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const int32_t* step_idx, int B, int C, int HW,
+                          long first_id, unsigned long long seed, void* stream);
 
 /* loss = mean|target - pred| (ddpm.py:282-295 'l1' + :1030-1040), d_pred = grad_scale * sign(pred - target) / n (NULL: skip).
  * ws: 1024 doubles. */

@@ -52,4 +52,16 @@ __device__ __forceinline__ uint32_t attn_keep_bits(U4& s, uint32_t thr16) {
   return ~lt;
 }
 
+// per-sample normal noise (stedm_philox_normal, include/stedm_hip.h): the four N(0, 1) values of element group g of the row of sample `sid`.
+// Philox4x32-10(counter {g, stream, 0x4E524D4C, 0}, key {seed, sid}); Box-Muller on the word pairs with u = (w + 0.5) 2^-32, fp32 arithmetic
+// with the hardware log / sin / cos. Shared by every kernel that draws these rows, so that all of them give the same bits.
+__device__ __forceinline__ void philox_normal4(uint32_t g, uint32_t stream, uint32_t seed, uint32_t sid, float z[4]) {
+  const U4 r = philox4x32_10(U4{g, stream, 0x4E524D4Cu, 0u}, seed, sid);
+  const float k = 2.3283064365386963e-10f;     // 2^-32
+  const float u0 = ((float)r.x + 0.5f) * k, u1 = ((float)r.y + 0.5f) * k, u2 = ((float)r.z + 0.5f) * k, u3 = ((float)r.w + 0.5f) * k;
+  const float ra = sqrtf(-2.0f * __logf(fminf(fmaxf(u0, 1.1641532e-10f), 0.99999994f))), rb = sqrtf(-2.0f * __logf(fminf(fmaxf(u2, 1.1641532e-10f), 0.99999994f)));
+  z[0] = ra * __cosf(6.283185307179586f * u1); z[1] = ra * __sinf(6.283185307179586f * u1);
+  z[2] = rb * __cosf(6.283185307179586f * u3); z[3] = rb * __sinf(6.283185307179586f * u3);
+}
+
 }  // namespace stedm

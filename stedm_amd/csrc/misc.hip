@@ -964,13 +964,8 @@ __global__ void __launch_bounds__(256) philox_normal_kernel(float* __restrict__ 
   const unsigned sid = ids ? (unsigned)ids[row] : (unsigned)(id0 + row);
   const int ngroups = (n + 3) >> 2;
   for (int g = blockIdx.x * 256 + threadIdx.x; g < ngroups; g += gridDim.x * 256) {
-    const U4 r = philox4x32_10(U4{(unsigned)g, stream, 0x4E524D4Cu, 0u}, seed, sid);
     float z[4];
-    const float k = 2.3283064365386963e-10f;     // 2^-32
-    const float u0 = ((float)r.x + 0.5f) * k, u1 = ((float)r.y + 0.5f) * k, u2 = ((float)r.z + 0.5f) * k, u3 = ((float)r.w + 0.5f) * k;
-    const float ra = sqrtf(-2.0f * __logf(fminf(fmaxf(u0, 1.1641532e-10f), 0.99999994f))), rb = sqrtf(-2.0f * __logf(fminf(fmaxf(u2, 1.1641532e-10f), 0.99999994f)));
-    z[0] = ra * __cosf(6.283185307179586f * u1); z[1] = ra * __sinf(6.283185307179586f * u1);
-    z[2] = rb * __cosf(6.283185307179586f * u3); z[3] = rb * __sinf(6.283185307179586f * u3);
+    philox_normal4((unsigned)g, stream, seed, sid, z);
     float* o = out + (long)row * n + 4 * g;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -983,6 +978,95 @@ extern "C" int stedm_philox_normal(float* out, int rows, int n, const long* samp
   const int ngroups = (n + 3) / 4;
   dim3 grid((ngroups + 255) / 256 < 64 ? (ngroups + 255) / 256 : 64, rows);
   philox_normal_kernel<<<grid, 256, 0, as_stream(stream_)>>>(out, sample_ids, first_id, n, (unsigned)(seed & 0xFFFFFFFFull), stream);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ------------------------------------------------------------------------------------------------ masked DDIM: known region from x0
+// ddim.py:143-146 before the U-Net call of every step: img = q_sample(x0, ts) * mask + (1 - mask) * img, q_sample = ddpm.py:277-280 with the
+// fp32 schedule buffers gathered by t[b] (extract_into_tensor, util.py:96-99) and fresh noise each step. In place on img [B][C][HW]. One thread
+// = one group of four consecutive elements of a sample's row (the group of philox_normal4). mask is read through (batch, channel) strides, 0
+// broadcasting. noise: given ([B][C][HW]), or drawn here as stedm_philox_normal's row of sample first_id + b with stream 0x8000 + *step_idx -
+// bit-identical to that kernel - so that a replayed graph draws new noise at every step. Two products then a sum at each stage, like torch
+// (no FMA contraction): a mask of 0 returns img exactly.
+template <bool VEC>
+__global__ void __launch_bounds__(256) ddim_mask_blend_kernel(float* __restrict__ img, const float* __restrict__ x0, const float* __restrict__ mask,
+                                                              long mbs, long mcs, const float* __restrict__ noise, const int64_t* __restrict__ t,
+                                                              const float* __restrict__ sa, const float* __restrict__ s1, const int32_t* __restrict__ step_idx,
+                                                              int C, int HW, unsigned id0, unsigned seed) {
+  const int b = blockIdx.y;
+  const int n = C * HW;
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (4 * g >= n) return;
+  const int64_t tb = t[b];
+  const float ca = sa[tb], cn = s1[tb];
+  float z[4];
+  if (noise) {
+    if (VEC) {
+      const float4 v = *reinterpret_cast<const float4*>(noise + (long)b * n + 4 * g);
+      z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) z[j] = 4 * g + j < n ? noise[(long)b * n + 4 * g + j] : 0.0f;
+    }
+  } else {
+    philox_normal4((unsigned)g, 0x8000u + (unsigned)*step_idx, seed, id0 + (unsigned)b, z);
+  }
+  float xi[4], x0v[4], m[4];
+  const long row = (long)b * n;
+  if (VEC) {                                            // HW % 4 == 0: the group lies in one channel plane
+    const int c = (4 * g) / HW, p = 4 * g - c * HW;
+    const float4 a = *reinterpret_cast<const float4*>(img + row + 4 * g), q = *reinterpret_cast<const float4*>(x0 + row + 4 * g);
+    const float4 w = *reinterpret_cast<const float4*>(mask + b * mbs + c * mcs + p);
+    xi[0] = a.x; xi[1] = a.y; xi[2] = a.z; xi[3] = a.w;
+    x0v[0] = q.x; x0v[1] = q.y; x0v[2] = q.z; x0v[3] = q.w;
+    m[0] = w.x; m[1] = w.y; m[2] = w.z; m[3] = w.w;
+  } else {                                              // scalar tail form: any HW, groups may straddle planes or the row end
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int e = 4 * g + j;
+      const bool in = e < n;
+      const int c = in ? e / HW : 0, p = in ? e - c * HW : 0;
+      xi[j] = in ? img[row + e] : 0.0f;
+      x0v[j] = in ? x0[row + e] : 0.0f;
+      m[j] = in ? mask[b * mbs + c * mcs + p] : 0.0f;
+    }
+  }
+  float o[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float q = __fadd_rn(__fmul_rn(ca, x0v[j]), __fmul_rn(cn, z[j]));
+    o[j] = __fadd_rn(__fmul_rn(q, m[j]), __fmul_rn(__fsub_rn(1.0f, m[j]), xi[j]));
+  }
+  if (VEC) {
+    *reinterpret_cast<float4*>(img + row + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * g + j < n) img[row + 4 * g + j] = o[j];
+  }
+}
+
+extern "C" int stedm_ddim_mask_blend(float* img, const float* x0, const float* mask, long mask_bstride, long mask_cstride, const float* noise,
+                                     const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const int32_t* step_idx, int B, int C, int HW,
+                                     long first_id, unsigned long long seed, void* stream) {
+  STEDM_CHECK_ARG(img && x0 && mask && t && sqrt_ac && sqrt_1mac, "ddim_mask_blend: null pointer");
+  STEDM_CHECK_ARG(noise || step_idx, "ddim_mask_blend: the in-kernel noise draw needs the device step index");
+  STEDM_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && HW > 0 && (long)C * HW <= 0x7FFFFFFFL, "ddim_mask_blend: bad shape B=%d C=%d HW=%d", B, C, HW);
+  STEDM_CHECK_ARG(mask_cstride == 0 || mask_cstride == HW, "ddim_mask_blend: mask channel stride %ld (0 or HW=%d)", mask_cstride, HW);
+  STEDM_CHECK_ARG(mask_bstride == 0 || mask_bstride == (mask_cstride ? (long)C * HW : (long)HW),
+                  "ddim_mask_blend: mask batch stride %ld (0 or the mask's per-sample size)", mask_bstride);
+  STEDM_CHECK_ARG(first_id >= 0 && first_id + B <= (1L << 32), "ddim_mask_blend: sample ids %ld + %d outside [0, 2^32]", first_id, B);
+  const int n = C * HW;
+  const bool aligned = ((uintptr_t)img | (uintptr_t)x0 | (uintptr_t)mask | (uintptr_t)noise) % 16 == 0;
+  dim3 grid(((n + 3) / 4 + 255) / 256, B);
+  if (HW % 4 == 0 && aligned)
+    ddim_mask_blend_kernel<true><<<grid, 256, 0, as_stream(stream)>>>(img, x0, mask, mask_bstride, mask_cstride, noise, t, sqrt_ac, sqrt_1mac,
+                                                                        step_idx, C, HW, (unsigned)first_id, (unsigned)(seed & 0xFFFFFFFFull));
+  else
+    ddim_mask_blend_kernel<false><<<grid, 256, 0, as_stream(stream)>>>(img, x0, mask, mask_bstride, mask_cstride, noise, t, sqrt_ac, sqrt_1mac,
+                                                                         step_idx, C, HW, (unsigned)first_id, (unsigned)(seed & 0xFFFFFFFFull));
   STEDM_LAUNCH_CHECK();
   return 0;
 }

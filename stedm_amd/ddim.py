@@ -8,6 +8,8 @@ operation of the loop body runs in HIP kernels:
     when the model offers it, else two calls in the reference's order (cond, then uncond);
   * ddim.py:179-184 (CFG combine + (C,H)-std rescale, phi = 0.7) and :195-210 (x0 / direction / noise)
     -> one fused kernel (stedm_ddim_step);
+  * masked sampling, ddim.py:143-146 (q_sample of x0 blended into img before the U-Net call) -> one kernel
+    (stedm_ddim_mask_blend) whose noise is drawn in it from the device step index, so it is captured with the step;
   * with `use_graph=True` the whole step (timestep fill, U-Net, update, counter decrement) is captured
     once in a hipGraph and replayed per step, per-step scalars coming from a device table.
 """
@@ -59,23 +61,62 @@ class DDIMSampler(object):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, **kwargs):
-        """ddim.py:56-110."""
-        if quantize_x0 or mask is not None or x0 is not None or score_corrector is not None or noise_dropout > 0. \
-                or temperature != 1.:
-            raise NotImplementedError("quantize_x0 / mask / x0 / score_corrector / noise_dropout / temperature: "
+        """ddim.py:56-110.
+
+        Masked sampling (ddim.py:143-146): with `mask` (and `x0`, required with it) every step starts with
+        img = q_sample(x0, t) * mask + (1 - mask) * img — mask == 1 keeps x0, mask == 0 generates, soft values blend. x0 is
+        [B, C, H, W] (a batch-1 x0 is refused: the reference's one batch-shaped noise draw shared by every sample cannot be reproduced by
+        per-sample streams); mask is [B|1, 1|C, H, W]. Repo-specific keywords: `mask_noises` (one N(0,1) tensor per iteration in place
+        of q_sample's draw; eager loop), else the draw is made in the kernel from `mask_seed` (default: one draw from torch's CPU
+        generator per call) and the global sample id `sample_id0 + b` (ops.ddim_mask_blend)."""
+        if quantize_x0 or score_corrector is not None or noise_dropout > 0. or temperature != 1.:
+            raise NotImplementedError("quantize_x0 / score_corrector / noise_dropout / temperature: "
                                       "unused by the reference drivers (ldm_diffusion.py:82,90), not implemented")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
+        masking = {}
+        if mask is not None:
+            masking = self._mask_args(size, mask, x0, kwargs.get("mask_noises"), kwargs.get("mask_seed"), kwargs.get("sample_id0", 0))
         return self.ddim_sampling(conditioning, size, callback=callback, img_callback=img_callback, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, noises=kwargs.get("noises"))
+                                  unconditional_conditioning=unconditional_conditioning, noises=kwargs.get("noises"), **masking)
+
+    def _mask_args(self, size, mask, x0, mask_noises, mask_seed, sample_id0):
+        """Checks and device placement of the masked-sampling inputs (see `sample`)."""
+        if x0 is None:
+            raise ValueError("mask given without x0 (ddim.py:144 asserts x0 is not None)")
+        B, C, H, W = size
+        dev = self.model.device
+        x0 = x0.to(dev).float().contiguous()
+        mask = mask.to(dev).float().contiguous()
+        if x0.dim() != 4 or tuple(x0.shape[1:]) != (C, H, W) or x0.shape[0] != B:
+            raise ValueError(f"x0 {tuple(x0.shape)} must be [{B}, {C}, {H}, {W}] (a batch-1 x0 is not broadcast: per-sample noise streams "
+                             "cannot reproduce the reference's one draw shared by the batch)")
+        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) or tuple(mask.shape[2:]) != (H, W):
+            raise ValueError(f"mask {tuple(mask.shape)} must be [{B}|1, 1|{C}, {H}, {W}]")
+        if mask_noises is not None:
+            mask_noises = list(mask_noises)
+            if len(mask_noises) != self.ddim_timesteps.shape[0]:
+                raise ValueError(f"mask_noises holds {len(mask_noises)} tensors for {self.ddim_timesteps.shape[0]} iterations")
+        elif mask_seed is None:
+            mask_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        return {"mask": mask, "x0": x0, "mask_noises": mask_noises, "mask_seed": None if mask_seed is None else int(mask_seed),
+                "sample_id0": int(sample_id0)}
+
+    def _blend(self, img, mask, x0, t, step, noise=None, seed=0, first_id=0):
+        """ddim.py:143-146 in place on img (one kernel; q_sample's noise given or drawn in it)."""
+        m = self.model
+        ops.ddim_mask_blend(img, x0, mask, t, m.sqrt_alphas_cumprod, m.sqrt_one_minus_alphas_cumprod, noise=noise, step_idx=step,
+                            seed=0 if seed is None else seed, first_id=first_id)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, noises=None, **kwargs):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, noises=None, mask=None, x0=None,
+                      mask_noises=None, mask_seed=None, sample_id0=0, **kwargs):
         """ddim.py:113-162. `noises` (optional list, one N(0,1) tensor per iteration) replaces the global-RNG
-        draw of ddim.py:206 so that runs are reproducible across devices and shard counts."""
+        draw of ddim.py:206 so that runs are reproducible across devices and shard counts. mask / x0 / mask_noises / mask_seed /
+        sample_id0: masked sampling, checked and placed by `sample` (the blend runs before the U-Net call; x_inter logs unblended img)."""
         device = self.model.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().clone()
@@ -85,10 +126,12 @@ class DDIMSampler(object):
         cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         need_inter = lambda index: index % log_every_t == 0 or index == total_steps - 1
 
+        blend = None if mask is None else (mask, x0, mask_seed, int(sample_id0))
+
         if self.use_graph and callback is None and img_callback is None and self._eta == 0.0 \
-                and hasattr(self.model, "apply_model_cfg"):
+                and hasattr(self.model, "apply_model_cfg") and mask_noises is None:
             out = self._sample_graph(img, cond, unconditional_conditioning, unconditional_guidance_scale, cfg,
-                                     total_steps, log_every_t, intermediates)
+                                     total_steps, log_every_t, intermediates, blend)
             ops.f16_guard_check("the DDIM sampling loop")       # fp16 modes: raise rather than return samples computed through an inf
             return out
 
@@ -96,6 +139,9 @@ class DDIMSampler(object):
         for i, step in enumerate(np.flip(timesteps)):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
+            if mask is not None:            # ddim.py:143-146
+                mnz = None if mask_noises is None else mask_noises[i].to(device).float().contiguous()
+                self._blend(img, mask, x0, ts, self._idx_all[index:index + 1], noise=mnz, seed=mask_seed, first_id=sample_id0)
             nz = None
             if noises is not None:
                 nz = noises[i].to(device).float().contiguous()
@@ -140,9 +186,9 @@ class DDIMSampler(object):
         return x_prev, pred_x0
 
     # ------------------------------------------------------------------------------------------------ graph replay
-    def _sample_graph(self, img, cond, uncond, scale, cfg, total_steps, log_every_t, intermediates):
+    def _sample_graph(self, img, cond, uncond, scale, cfg, total_steps, log_every_t, intermediates, blend=None):
         """Only taken for eta == 0 (sigma == 0: the noise term of ddim.py:206 is identically zero)."""
-        sg = StepGraph(self, img, cond, uncond if cfg else None, scale)
+        sg = StepGraph(self, img, cond, uncond if cfg else None, scale, blend=blend)
 
         def log(index):
             if index % log_every_t == 0 or index == total_steps - 1:
@@ -163,12 +209,14 @@ class DDIMSampler(object):
 
 
 class StepGraph:
-    """One denoising step = {t fill from the device table, U-Net (shared-encoder CFG pass), fused DDIM/CFG update in
-    place on `img`, device index decrement}, capturable once in a hipGraph and replayed for every step."""
+    """One denoising step = {t fill from the device table, [masked sampling: blend of q_sample(x0, t) into `img`, noise drawn in the
+    kernel from the device index], U-Net (shared-encoder CFG pass), fused DDIM/CFG update in place on `img`, device index decrement},
+    capturable once in a hipGraph and replayed for every step. blend: None or (mask, x0, seed, first sample id)."""
 
-    def __init__(self, sampler: DDIMSampler, img: torch.Tensor, cond, uncond, scale: float, rescale_phi: float = 0.7):
+    def __init__(self, sampler: DDIMSampler, img: torch.Tensor, cond, uncond, scale: float, rescale_phi: float = 0.7, blend=None):
         self.s = sampler
         self.img = img
+        self.blend = blend
         self.cond, self.uncond, self.scale, self.phi = cond, uncond, float(scale), float(rescale_phi)
         dev = img.device
         b = img.shape[0]
@@ -186,6 +234,9 @@ class StepGraph:
     def step_eager(self):
         s, m = self.s, self.s.model
         ops.step_set_t(s._ts_table, self.step, self.t_buf)
+        if self.blend is not None:
+            mask, x0, seed, first_id = self.blend
+            s._blend(self.img, mask, x0, self.t_buf, self.step, seed=seed, first_id=first_id)
         if self.cfg:
             e_c, e_u = m.apply_model_cfg(self.img, self.t_buf, self.cond, self.uncond, out=self.eps, uniform_t=True)
         else:

@@ -667,18 +667,29 @@ def prepare_batch(batch, device=None) -> dict:
 
 @torch.no_grad()
 def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: float = 0.0, cfg_scale: float = 1.0,
-                    style_sampling: str = "nearby", x_T: Optional[torch.Tensor] = None, dedup_uncond: bool = True, noises=None):
+                    style_sampling: str = "nearby", x_T: Optional[torch.Tensor] = None, dedup_uncond: bool = True, noises=None,
+                    mask: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None, sample_id0: int = 0):
     """Lightning-free restatement of LDM_Diffusion.predict_step (modules/ldm_diffusion.py:76-91) up to the sampled latents:
     conditional get_input, unconditional batch {image: 0, segmentation: same, style_imgs: -2}, DDIM + CFG.
 
     dedup_uncond: the unconditional style input is the same constant (-2) image stack for every sample (ldm_diffusion.py:86) and the
     style encoder works per sample, so its output is one vector: it is computed for ONE sample and broadcast instead of running the
     encoder over the whole constant batch; the layout conditioning of the unconditional batch is the conditional one (same
-    segmentation). False: the reference's literal second get_input."""
-    z, c_0 = model.get_input(ldm_batch, "image", predict_only=True)
+    segmentation). False: the reference's literal second get_input.
+
+    Masked sampling (DDIMSampler.sample's mask / x0, ddim.py:143-146): mask == 1 keeps the real tile, mask == 0 lets the model generate,
+    soft values blend. x0 defaults to the latent of the batch's own image (get_input with the first-stage encode: the `z` the reference
+    computes and discards). mask is at latent resolution ([B|1, 1|C, h, w]) or at image resolution ([B, 1, H, W] or [B, H, W], H = f h):
+    an image mask is min-pooled by the first stage's factor f, so a latent pixel is kept only where its whole f x f footprint is kept.
+    mask_seed / sample_id0: the per-sample stream of the blend's noise (DDIMSampler.sample). The returned latent is the model's output:
+    its kept region is close to x0, not pasted from it."""
+    masked = mask is not None
+    z, c_0 = model.get_input(ldm_batch, "image", predict_only=not (masked and x0 is None))
     kw = {} if x_T is None else {"x_T": x_T}
     if noises is not None:          # one N(0,1) tensor per DDIM iteration in place of the global-RNG draw of ddim.py:206 (eta > 0)
         kw["noises"] = noises
+    if masked:
+        kw.update(mask=latent_mask(model, mask, len(z)), x0=z if x0 is None else x0, mask_seed=mask_seed, sample_id0=int(sample_id0))
     if cfg_scale == 1 or style_sampling == "none":
         out, _ = model.sample_log(c_0, batch_size=len(z), ddim=True, ddim_steps=ddim_steps, eta=eta, log_every_t=1000, **kw)
     else:
@@ -696,15 +707,41 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
     return out
 
 
+def latent_mask(model: LatentDiffusion, mask: torch.Tensor, batch: int) -> torch.Tensor:
+    """A sampling mask at latent resolution: latent masks ([B|1, 1|C, h, w]) pass; image masks ([B, 1, H, W] or [B, H, W] with H = f h,
+    W = f w, f the first stage's downsampling factor) are min-pooled over f x f blocks (a latent pixel is kept only if its whole footprint
+    is kept; soft values take the block's minimum)."""
+    h = w = int(model.image_size)
+    m = mask.to(model.device).float()
+    if m.dim() == 3:
+        m = m[:, None]
+    if m.dim() != 4:
+        raise ValueError(f"mask {tuple(mask.shape)}: expected [B|1, 1|C, {h}, {w}] or an image mask [B, 1, H, W] / [B, H, W]")
+    if tuple(m.shape[2:]) == (h, w):
+        return m.contiguous()
+    H, W = int(m.shape[2]), int(m.shape[3])
+    f = H // h
+    enc = getattr(model.first_stage_model, "encoder", None)
+    want = 2 ** (enc.num_resolutions - 1) if enc is not None and hasattr(enc, "num_resolutions") else None
+    if f < 2 or H != f * h or W != f * w or m.shape[1] != 1 or (want is not None and f != want) or m.shape[0] not in (1, batch):
+        raise ValueError(f"mask {tuple(mask.shape)} is neither a latent mask [B|1, 1|C, {h}, {w}] nor an image mask [B, 1, f*{h}, f*{w}]"
+                         + ("" if want is None else f" with the first stage's factor f = {want}"))
+    return m.reshape(m.shape[0], 1, h, f, w, f).amin(dim=(3, 5)).contiguous()
+
+
 @torch.no_grad()
 def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: int, ddim_steps: int, eta: float = 0.0, cfg_scale: float = 1.0,
-                            seed: int = 0, rank: Optional[int] = None, world: Optional[int] = None, group=None, gather: bool = True, **kw):
+                            seed: int = 0, rank: Optional[int] = None, world: Optional[int] = None, group=None, gather: bool = True,
+                            mask: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None, **kw):
     """predict_step on one rank of a data-parallel prediction run (predict_diff.py:86: Trainer.predict under DDP hands every rank its shard of
     the dataset; modules/ldm_diffusion.py:76-107). `shard_batch` holds this rank's samples — the contiguous slice
     parallel.shard_range(global_batch, rank, world) of the global batch. Latents are independent, so nothing is exchanged inside the loop;
     the initial noise x_T (ddim.py:122) and, for eta > 0, every step's noise (ddim.py:206) come from per-SAMPLE streams keyed by the global
     sample id (parallel.per_sample_normal), so sample i is the same for every world size, which the reference's batch-shaped global-RNG
-    draw cannot give. gather: all-gather the shards (RCCL over xGMI with backend "nccl") -> [global_batch, C, H, W] on every rank."""
+    draw cannot give. gather: all-gather the shards (RCCL over xGMI with backend "nccl") -> [global_batch, C, H, W] on every rank.
+
+    mask / x0 (masked sampling, see predict_latents): given for the global batch (their rows lo:hi are taken), for the shard, or (mask
+    only) as one row for every sample. The blend's noise is keyed by (seed, global sample id), like x_T."""
     import torch.distributed as dist
     from . import parallel as par
     if rank is None or world is None:
@@ -727,6 +764,9 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
         from .schedule import make_ddim_timesteps
         n_iter = int(make_ddim_timesteps(int(ddim_steps), model.num_timesteps).shape[0])      # (S = 6 -> 7 iterations: ddim.py's uniform stride)
         noises = [draw(1 + i) for i in range(n_iter)]
+    if mask is not None:
+        rows = lambda a: a[lo:hi] if (a.shape[0] == int(global_batch) and a.shape[0] != n) else a
+        kw.update(mask=rows(mask), x0=None if x0 is None else rows(x0), mask_seed=int(seed), sample_id0=lo)
     from ._lib import StedmHipError
     err: Optional[StedmHipError] = None
     lat = None

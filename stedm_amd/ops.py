@@ -959,6 +959,39 @@ def ddim_step(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], c
     return x_prev
 
 
+def ddim_mask_blend(img: torch.Tensor, x0: torch.Tensor, mask: torch.Tensor, t: torch.Tensor, sqrt_ac: torch.Tensor, sqrt_1mac: torch.Tensor,
+                    noise: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None, seed: int = 0, first_id: int = 0) -> torch.Tensor:
+    """ddim.py:143-146 in place: img = q_sample(x0, t) * mask + (1 - mask) * img (stedm_ddim_mask_blend). img, x0 [B, C, h, w]; mask
+    [B|1, 1|C, h, w] (broadcast over batch / channel); t int64 [B]. noise [B, C, h, w], or None: row first_id + b of ops.philox_normal with
+    stream 0x8000 + step_idx[0], drawn in the kernel (step_idx: device int32 [1])."""
+    _chk(img, name="img"); _chk(x0, name="x0"); _chk(mask, name="mask"); _chk(t, torch.int64, "t")
+    _chk(sqrt_ac, name="sqrt_ac"); _chk(sqrt_1mac, name="sqrt_1mac")
+    if img.dim() != 4:
+        raise ValueError(f"img must be [B, C, h, w], got {tuple(img.shape)}")
+    B, Cc, H, W = img.shape
+    if tuple(x0.shape) != tuple(img.shape):
+        raise ValueError(f"x0 {tuple(x0.shape)} must have img's shape {tuple(img.shape)}")
+    if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cc) or tuple(mask.shape[2:]) != (H, W):
+        raise ValueError(f"mask {tuple(mask.shape)} must be [B|1, 1|C, h, w] for img {tuple(img.shape)}")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"t must be [B] = [{B}], got {tuple(t.shape)}")
+    if noise is not None:
+        _chk(noise, name="noise")
+        if tuple(noise.shape) != tuple(img.shape):
+            raise ValueError(f"noise {tuple(noise.shape)} must have img's shape {tuple(img.shape)}")
+    elif step_idx is None:
+        raise ValueError("the in-kernel noise draw needs step_idx (device int32)")
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+    HW = H * W
+    cstride = HW if mask.shape[1] == Cc else 0
+    bstride = 0 if mask.shape[0] == 1 else mask.shape[1] * HW
+    check(lib().stedm_ddim_mask_blend(img.data_ptr(), x0.data_ptr(), mask.data_ptr(), bstride, cstride, _ptr(noise), t.data_ptr(),
+                                      sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(), _ptr(step_idx), B, Cc, HW, int(first_id),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "stedm_ddim_mask_blend")
+    return img
+
+
 def step_advance(step_idx: torch.Tensor, delta: int = 1) -> None:
     check(lib().stedm_step_advance(step_idx.data_ptr(), delta, _stream()), "stedm_step_advance")
 
