@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 13
+#define STEDM_ABI_VERSION 14
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -323,6 +323,11 @@ int stedm_conv_out(const float* src, int c, const float* chan_stats, int nslab, 
 int stedm_time_embed(const int64_t* t, const float* freqs, const float* w0t, const float* b0,
                      const float* w2t, const float* b2, float* emb, float* ws, int B, int mc, int ted,
                      void* stream);
+/* The same with fp32 timesteps t [B] (ABI 14): DPM-Solver's fractional model times (dpm_solver.py:246-253), which util.py:151-171 allows.
+ * The same sinusoid (t * freq formed in fp32, precise cos / sin) and Linears: an integer-valued t gives the bits of stedm_time_embed. */
+int stedm_time_embed_f32(const float* t, const float* freqs, const float* w0t, const float* b0,
+                         const float* w2t, const float* b2, float* emb, float* ws, int B, int mc, int ted,
+                         void* stream);
 /* emb_layers = SiLU -> Linear of every ResBlock at once (openaimodel.py:231-237,277):
  * out[b][n] = bias[n] + sum_k silu(emb[b][k]) * wt[k][n]; wt is [k][ntot] (layers concatenated). */
 int stedm_emb_proj(const float* emb, const float* wt, const float* bias, float* out, int B, int k, int ntot,
@@ -359,6 +364,20 @@ int stedm_step_advance(int32_t* step_idx, int delta, void* stream);
 /* t_buf[0..B) = ts_table[*step_idx] : ts = torch.full((b,), step) of ddim.py:141, device-side so that one
  * captured graph serves every step. ts_table: DEVICE int64 [nsteps] (ddim_timesteps, ascending). */
 int stedm_step_set_t(const int64_t* ts_table, const int32_t* step_idx, int64_t* t_buf, int B, void* stream);
+/* The same over an fp32 table and an fp32 t_buf (ABI 14): the model times of a DPM-Solver run. */
+int stedm_step_set_t_f32(const float* ts_table, const int32_t* step_idx, float* t_buf, int B, void* stream);
+
+/* ---- DPM-Solver++(2M) update (ABI 14) ------------------------------------------------------ */
+/* One step of the reference's multistep DPM-Solver++ of order 2 (dpm_solver.py, predict_x0=True, solver_type 'dpm_solver',
+ * thresholding off), elementwise over n fp32 elements, in place:
+ *   eps = e_u + s (e_c - e_u)  (e_u NULL: eps = e_c)       x0 = (x - sigma_i eps) / alpha_i
+ *   x = (r x - A x0) - (0.5 A) (inv_r0 (x0 - x0_prev))     x0_prev = x0; pred_x0 (may be NULL) = x0
+ * coefs: DEVICE table [S][STEDM_DPM_NCOEF] = {alpha_i, sigma_i, r = sigma_{i+1} / sigma_i, A = alpha_{i+1} (e^{-h} - 1), inv_r0 = 1 / r0,
+ * 0.5 A}; a row whose last entry is 0 is a first-order step (x0_prev is then not read). Row *step_idx (DEVICE int32; NULL: row 0).
+ * x, x0_prev and pred_x0 may alias element for element. */
+#define STEDM_DPM_NCOEF 6
+int stedm_dpm_step(float* x, const float* e_c, const float* e_u, float* x0_prev, float* pred_x0, const float* coefs,
+                   const int32_t* step_idx, float cfg_scale, long n, void* stream);
 
 /* ---- style path: set-ViT encoder (networks/vit_set.py), aggregation blocks, layout rescaler -------------------- */
 /* SPT vit_set.py:84-107 + token assembly :175-186. img [B][ns][H][W][3] fp32 -> x [B][ntok+2][dim]:

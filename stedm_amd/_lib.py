@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 
@@ -86,6 +86,7 @@ SIGNATURES = {
     "stedm_conv_in": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "stedm_conv_out": (_I, [_P, _I, _P, _I, _P, _P, _F, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "stedm_time_embed": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "stedm_time_embed_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "stedm_emb_proj": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "stedm_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "stedm_attn_legacy": (_I, [_P, _P, _I, _I, _I, _I, _P]),
@@ -93,6 +94,8 @@ SIGNATURES = {
     "stedm_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I, _P]),
     "stedm_step_advance": (_I, [_P, _I, _P]),
     "stedm_step_set_t": (_I, [_P, _P, _P, _I, _P]),
+    "stedm_step_set_t_f32": (_I, [_P, _P, _P, _I, _P]),
+    "stedm_dpm_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, C.c_long, _P]),
     "stedm_svit_patch_embed": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _P]),
     "stedm_svit_patch_ln16": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _I, _P]),
     "stedm_svit_tok_place": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

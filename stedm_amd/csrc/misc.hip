@@ -672,8 +672,11 @@ static int launch_linear(const float* x, const float* wt, const float* bias, flo
   return 0;
 }
 
-// sinusoid [B][mc]: cos half first (util.py:166)
-__global__ void sinusoid_kernel(const int64_t* __restrict__ t, const float* __restrict__ freqs, float* __restrict__ te, int mc) {
+// sinusoid [B][mc]: cos half first (util.py:166). T: int64 (training, DDIM) or float (DPM-Solver's fractional model times,
+// dpm_solver.py:246-253); the argument t * freq is formed in fp32 either way (util.py:165 `timesteps[:, None].float() * freqs`), so an
+// integer-valued float t gives the bits of the int64 path. Precise cosf / sinf: the arguments reach ~1000 rad.
+template <typename T>
+__global__ void sinusoid_kernel(const T* __restrict__ t, const float* __restrict__ freqs, float* __restrict__ te, int mc) {
   const int b = blockIdx.x, half = mc / 2;
   const float tv = (float)t[b];
   for (int i = threadIdx.x; i < half; i += blockDim.x) {
@@ -685,18 +688,29 @@ __global__ void sinusoid_kernel(const int64_t* __restrict__ t, const float* __re
 }
 
 // emb [B][ted]; ws: caller-provided scratch of B*(mc+ted) floats (sinusoid + hidden layer).
-extern "C" int stedm_time_embed(const int64_t* t, const float* freqs, const float* w0t, const float* b0, const float* w2t,
-                                const float* b2, float* emb, float* ws, int B, int mc, int ted, void* stream) {
+template <typename T>
+static int time_embed_impl(const T* t, const float* freqs, const float* w0t, const float* b0, const float* w2t, const float* b2, float* emb,
+                           float* ws, int B, int mc, int ted, void* stream) {
   STEDM_CHECK_ARG(t && freqs && w0t && b0 && w2t && b2 && emb && ws, "time_embed: null pointer");
   STEDM_CHECK_ARG(B > 0 && mc > 0 && ted > 0, "time_embed: bad sizes B=%d mc=%d ted=%d", B, mc, ted);
   float* te = ws;
   float* h1 = ws + (size_t)B * mc;
   hipStream_t st = as_stream(stream);
-  sinusoid_kernel<<<B, 64, 0, st>>>(t, freqs, te, mc);
+  sinusoid_kernel<T><<<B, 64, 0, st>>>(t, freqs, te, mc);
   STEDM_LAUNCH_CHECK();
   int rc = launch_linear(te, w0t, b0, h1, B, mc, ted, 0, 1, st);
   if (rc) return rc;
   return launch_linear(h1, w2t, b2, emb, B, ted, ted, 0, 0, st);
+}
+
+extern "C" int stedm_time_embed(const int64_t* t, const float* freqs, const float* w0t, const float* b0, const float* w2t,
+                                const float* b2, float* emb, float* ws, int B, int mc, int ted, void* stream) {
+  return time_embed_impl(t, freqs, w0t, b0, w2t, b2, emb, ws, B, mc, ted, stream);
+}
+
+extern "C" int stedm_time_embed_f32(const float* t, const float* freqs, const float* w0t, const float* b0, const float* w2t,
+                                    const float* b2, float* emb, float* ws, int B, int mc, int ted, void* stream) {
+  return time_embed_impl(t, freqs, w0t, b0, w2t, b2, emb, ws, B, mc, ted, stream);
 }
 
 // generic small Linear with optional input / output activation (0 none, 1 SiLU, 2 ReLU): Agg_Linear agg_blocks.py:14-18
@@ -910,13 +924,95 @@ extern "C" int stedm_step_advance(int32_t* step_idx, int delta, void* stream) {
   return 0;
 }
 
-__global__ void step_set_t_kernel(const int64_t* __restrict__ ts, const int32_t* __restrict__ idx, int64_t* __restrict__ t, int B) {
+template <typename T>
+__global__ void step_set_t_kernel(const T* __restrict__ ts, const int32_t* __restrict__ idx, T* __restrict__ t, int B) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B) t[i] = ts[*idx];
 }
 extern "C" int stedm_step_set_t(const int64_t* ts_table, const int32_t* step_idx, int64_t* t_buf, int B, void* stream) {
   STEDM_CHECK_ARG(ts_table && step_idx && t_buf && B > 0, "step_set_t: bad args");
-  step_set_t_kernel<<<(B + 255) / 256, 256, 0, as_stream(stream)>>>(ts_table, step_idx, t_buf, B);
+  step_set_t_kernel<int64_t><<<(B + 255) / 256, 256, 0, as_stream(stream)>>>(ts_table, step_idx, t_buf, B);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int stedm_step_set_t_f32(const float* ts_table, const int32_t* step_idx, float* t_buf, int B, void* stream) {
+  STEDM_CHECK_ARG(ts_table && step_idx && t_buf && B > 0, "step_set_t_f32: bad args");
+  step_set_t_kernel<float><<<(B + 255) / 256, 256, 0, as_stream(stream)>>>(ts_table, step_idx, t_buf, B);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// DPM-Solver++(2M) update (dpm_solver.py, predict_x0=True, solver_type 'dpm_solver'), elementwise over the flat [B*C*H*W] tensors:
+//   eps = e_u + s (e_c - e_u)                              model_wrapper, classifier-free (dpm_solver.py:305-321); e_u NULL: eps = e_c
+//   x0  = (x - sigma_i eps) / alpha_i                      data_prediction_fn (:361-368), thresholding off
+//   x   = (r x - A x0) - (0.5 A) (inv_r0 (x0 - x0_prev))   multistep update: first order (:478-505) when the row's 0.5 A is 0,
+//                                                          second order (:732-767) otherwise; x0_prev not read at first order
+//   x0_prev = x0 (pred_x0 = x0 if given)
+// The reference's operations in its order, each rounded once (contraction into FMAs is off): with equal inputs, torch's CPU arithmetic
+// gives the same bits, in the float4 and the elementwise form alike. Row *step_idx of coefs [S][STEDM_DPM_NCOEF] = {alpha_i, sigma_i, r, A, inv_r0, 0.5 A (0: first order)}. One thread = four
+// consecutive elements: float4 accesses when every pointer is 16-byte aligned, elementwise for the tail and otherwise. x, x0_prev and
+// pred_x0 may alias one another element for element (each element is read before it is written).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float dpm_update1(float xv, float ec, float eu, float xp, bool cfg, float s, float alpha, float sigma, float r,
+                                             float A, float inv_r0, float hA, float& x0) {
+#pragma clang fp contract(off)       // every product and sum rounded on its own (HIP's default contracts them into FMAs across statements)
+  const float eps = cfg ? eu + s * (ec - eu) : ec;
+  x0 = (xv - sigma * eps) / alpha;     // IEEE division (HIP's default: correctly rounded fp32 divide)
+  float o = r * xv - A * x0;
+  if (hA != 0.0f) o = o - hA * (inv_r0 * (x0 - xp));
+  return o;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) dpm_step_kernel(float* x, const float* __restrict__ e_c, const float* __restrict__ e_u, float* x0_prev,
+                                                       float* pred_x0, const float* __restrict__ coefs, const int32_t* __restrict__ step_idx,
+                                                       float s, long n) {
+  const long e0 = 4 * ((long)blockIdx.x * 256 + threadIdx.x);
+  if (e0 >= n) return;
+  const float* row = coefs + (long)(step_idx ? *step_idx : 0) * STEDM_DPM_NCOEF;
+  const float alpha = row[0], sigma = row[1], r = row[2], A = row[3], inv_r0 = row[4], hA = row[5];
+  const bool cfg = e_u != nullptr;
+  if (VEC && e0 + 4 <= n) {
+    const float4 xv = *reinterpret_cast<const float4*>(x + e0), ec = *reinterpret_cast<const float4*>(e_c + e0);
+    const float4 eu = cfg ? *reinterpret_cast<const float4*>(e_u + e0) : ec;
+    const float4 xp = hA != 0.0f ? *reinterpret_cast<const float4*>(x0_prev + e0) : ec;
+    float4 o, q;
+    o.x = dpm_update1(xv.x, ec.x, eu.x, xp.x, cfg, s, alpha, sigma, r, A, inv_r0, hA, q.x);
+    o.y = dpm_update1(xv.y, ec.y, eu.y, xp.y, cfg, s, alpha, sigma, r, A, inv_r0, hA, q.y);
+    o.z = dpm_update1(xv.z, ec.z, eu.z, xp.z, cfg, s, alpha, sigma, r, A, inv_r0, hA, q.z);
+    o.w = dpm_update1(xv.w, ec.w, eu.w, xp.w, cfg, s, alpha, sigma, r, A, inv_r0, hA, q.w);
+    *reinterpret_cast<float4*>(x + e0) = o;
+    *reinterpret_cast<float4*>(x0_prev + e0) = q;
+    if (pred_x0) *reinterpret_cast<float4*>(pred_x0 + e0) = q;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long e = e0 + j;
+      if (e < n) {
+        const float ec = e_c[e];
+        float q;
+        const float o = dpm_update1(x[e], ec, cfg ? e_u[e] : ec, hA != 0.0f ? x0_prev[e] : ec, cfg, s, alpha, sigma, r, A, inv_r0, hA, q);
+        x[e] = o;
+        x0_prev[e] = q;
+        if (pred_x0) pred_x0[e] = q;
+      }
+    }
+  }
+}
+
+extern "C" int stedm_dpm_step(float* x, const float* e_c, const float* e_u, float* x0_prev, float* pred_x0, const float* coefs,
+                              const int32_t* step_idx, float cfg_scale, long n, void* stream) {
+  STEDM_CHECK_ARG(x && e_c && x0_prev && coefs, "dpm_step: null pointer");
+  STEDM_CHECK_ARG(n > 0 && n <= (1L << 40), "dpm_step: bad element count %ld", n);
+  const bool aligned = ((uintptr_t)x | (uintptr_t)e_c | (uintptr_t)e_u | (uintptr_t)x0_prev | (uintptr_t)pred_x0) % 16 == 0;
+  const long groups = (n + 3) / 4;
+  const long blocks = (groups + 255) / 256;
+  STEDM_CHECK_ARG(blocks <= 0x7FFFFFFFL, "dpm_step: %ld elements exceed one launch", n);
+  if (aligned)
+    dpm_step_kernel<true><<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(x, e_c, e_u, x0_prev, pred_x0, coefs, step_idx, cfg_scale, n);
+  else
+    dpm_step_kernel<false><<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(x, e_c, e_u, x0_prev, pred_x0, coefs, step_idx, cfg_scale, n);
   STEDM_LAUNCH_CHECK();
   return 0;
 }

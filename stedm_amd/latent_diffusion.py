@@ -23,8 +23,11 @@ import torch.nn as nn
 from . import ops
 from ._lib import StedmHipError
 from .ddim import DDIMSampler
+from .dpm_solver import DPMSolverSampler
 from .schedule import NoiseSchedule
 from .unet import UNetModel
+
+SAMPLERS = ("ddim", "dpm_solver")          # sample_log / predict_latents(sampler=...)
 
 
 def instantiate_from_config(config):
@@ -246,6 +249,8 @@ class LatentDiffusion(nn.Module):
         the forward value only."""
         prefix = 'train' if self.training else 'val'
         if self.training and torch.is_grad_enabled():
+            if t.is_floating_point():
+                raise TypeError("the training step takes integer timesteps (floating ones are DPM-Solver's inference path); got " + str(t.dtype))
             if self.loss_type != 'l1':
                 raise NotImplementedError("the training step is built for loss_type 'l1' (conf/diffusion/ldm_based.yaml)")
             noise = torch.randn_like(x_start) if noise is None else noise
@@ -561,11 +566,17 @@ class LatentDiffusion(nn.Module):
 
     # ------------------------------------------------------------------------------------------ sampling
     @torch.no_grad()
-    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
-        """ddpm.py:1237-1250."""
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):
+        """ddpm.py:1237-1250. sampler: "ddim" (the reference's) or "dpm_solver" (DPMSolverSampler, the reference's
+        ldm/models/diffusion/dpm_solver: DPM-Solver++(2M), ddim_steps model evaluations)."""
         if not ddim:
             raise NotImplementedError("ancestral DDPM sampling is dead code for the shipped configs (SURVEY.md §2.1 #5)")
-        sampler = DDIMSampler(self, use_graph=self.use_graph)
+        if sampler not in SAMPLERS:
+            raise ValueError(f"unknown sampler {sampler!r}; choose from {SAMPLERS}")
+        if sampler == "dpm_solver":
+            sampler = DPMSolverSampler(self, device=self.device, use_graph=self.use_graph)
+        else:
+            sampler = DDIMSampler(self, use_graph=self.use_graph)
         shape = (self.channels, self.image_size, self.image_size)
         return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
 
@@ -668,7 +679,8 @@ def prepare_batch(batch, device=None) -> dict:
 @torch.no_grad()
 def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: float = 0.0, cfg_scale: float = 1.0,
                     style_sampling: str = "nearby", x_T: Optional[torch.Tensor] = None, dedup_uncond: bool = True, noises=None,
-                    mask: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None, sample_id0: int = 0):
+                    mask: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None, sample_id0: int = 0,
+                    sampler: str = "ddim"):
     """Lightning-free restatement of LDM_Diffusion.predict_step (modules/ldm_diffusion.py:76-91) up to the sampled latents:
     conditional get_input, unconditional batch {image: 0, segmentation: same, style_imgs: -2}, DDIM + CFG.
 
@@ -682,7 +694,14 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
     computes and discards). mask is at latent resolution ([B|1, 1|C, h, w]) or at image resolution ([B, 1, H, W] or [B, H, W], H = f h):
     an image mask is min-pooled by the first stage's factor f, so a latent pixel is kept only where its whole f x f footprint is kept.
     mask_seed / sample_id0: the per-sample stream of the blend's noise (DDIMSampler.sample). The returned latent is the model's output:
-    its kept region is close to x0, not pasted from it."""
+    its kept region is close to x0, not pasted from it.
+
+    sampler: "ddim" (default) or "dpm_solver" (DPM-Solver++(2M), stedm_amd/dpm_solver.py): ddim_steps is then the number of model
+    evaluations; it draws no noise after x_T, and eta != 0, noises and mask are refused."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}; choose from {SAMPLERS}")
+    if sampler == "dpm_solver" and (eta != 0.0 or noises is not None or mask is not None):
+        raise NotImplementedError("sampler='dpm_solver': eta != 0, per-step noises and masked sampling are DDIM options")
     masked = mask is not None
     z, c_0 = model.get_input(ldm_batch, "image", predict_only=not (masked and x0 is None))
     kw = {} if x_T is None else {"x_T": x_T}
@@ -690,6 +709,8 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
         kw["noises"] = noises
     if masked:
         kw.update(mask=latent_mask(model, mask, len(z)), x0=z if x0 is None else x0, mask_seed=mask_seed, sample_id0=int(sample_id0))
+    if sampler != "ddim":
+        kw["sampler"] = sampler
     if cfg_scale == 1 or style_sampling == "none":
         out, _ = model.sample_log(c_0, batch_size=len(z), ddim=True, ddim_steps=ddim_steps, eta=eta, log_every_t=1000, **kw)
     else:
@@ -741,7 +762,9 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
     draw cannot give. gather: all-gather the shards (RCCL over xGMI with backend "nccl") -> [global_batch, C, H, W] on every rank.
 
     mask / x0 (masked sampling, see predict_latents): given for the global batch (their rows lo:hi are taken), for the shard, or (mask
-    only) as one row for every sample. The blend's noise is keyed by (seed, global sample id), like x_T."""
+    only) as one row for every sample. The blend's noise is keyed by (seed, global sample id), like x_T.
+
+    sampler="dpm_solver" (through **kw): DPM-Solver draws nothing after x_T, so the per-sample x_T alone makes the shards invariant."""
     import torch.distributed as dist
     from . import parallel as par
     if rank is None or world is None:
@@ -760,7 +783,7 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
            (lambda st: par.per_sample_normal(seed, ids, shape, stream=st).to(dev))
     x_T = draw(0)
     noises = None
-    if eta != 0.0:
+    if eta != 0.0 and kw.get("sampler", "ddim") == "ddim":
         from .schedule import make_ddim_timesteps
         n_iter = int(make_ddim_timesteps(int(ddim_steps), model.num_timesteps).shape[0])      # (S = 6 -> 7 iterations: ddim.py's uniform stride)
         noises = [draw(1 + i) for i in range(n_iter)]

@@ -124,11 +124,15 @@ class LDM_Diffusion(_Base):
     @torch.no_grad()
     def predict_step(self, batch, batch_idx):
         """ldm_diffusion.py:76-107: conditional + unconditional conditioning, DDIM + CFG, VQ decode, uint8 images and class maps;
-        PNG files when `predict_dir` is set. Returns (images [B,H,W,3] uint8, segmentation [B,H,W] uint8) on the host."""
+        PNG files when `predict_dir` is set. Returns (images [B,H,W,3] uint8, segmentation [B,H,W] uint8) on the host.
+
+        The config key `sampler` (optional; "ddim" when absent, as in the reference's configs) selects "dpm_solver" (DPM-Solver++(2M),
+        stedm_amd/dpm_solver.py); `ddim_steps` is then the number of model evaluations (DDIM's uniform stride makes 128 into 143)."""
         cfg = self._cfg
         ldm_batch = self.prepare_batch(batch)
         sname = cfg.style_sampling["name"] if isinstance(cfg.style_sampling, dict) else cfg.style_sampling.name
-        lat = predict_latents(self._model, ldm_batch, ddim_steps=cfg.ddim_steps, eta=cfg.eta, cfg_scale=cfg.cfg_scale, style_sampling=sname)
+        lat = predict_latents(self._model, ldm_batch, ddim_steps=cfg.ddim_steps, eta=cfg.eta, cfg_scale=cfg.cfg_scale, style_sampling=sname,
+                              sampler=getattr(cfg, "sampler", None) or "ddim")
         dec = self._model.decode_first_stage(lat)
         img, seg = images_for_saving(dec, ldm_batch["segmentation"])
         img, seg = img.cpu().numpy(), seg.cpu().numpy()

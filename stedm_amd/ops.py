@@ -697,14 +697,21 @@ def conv_out(src: torch.Tensor, norm_weight: torch.Tensor, norm_bias: torch.Tens
 # ------------------------------------------------------------------------------------------- embeddings
 def time_embed(t: torch.Tensor, freqs: torch.Tensor, w0t: torch.Tensor, b0: torch.Tensor, w2t: torch.Tensor, b2: torch.Tensor,
                out: torch.Tensor, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
-    _chk(t, torch.int64, "timesteps")
+    """timestep_embedding + time_embed MLP. t: int64 [B] (stedm_time_embed) or float32 [B], fractional model times
+    (stedm_time_embed_f32); any other dtype is refused."""
+    if t.dtype == torch.float32:
+        fn, name = lib().stedm_time_embed_f32, "stedm_time_embed_f32"
+    else:
+        _chk(t, torch.int64, "timesteps")
+        fn, name = lib().stedm_time_embed, "stedm_time_embed"
+    _chk(t, t.dtype, "timesteps")
     B = t.shape[0]
     mc, ted = w0t.shape
     if ws is None:
         ws = torch.empty((B * (mc + ted),), dtype=torch.float32, device=t.device)
     assert ws.numel() >= B * (mc + ted)
-    check(lib().stedm_time_embed(t.data_ptr(), freqs.data_ptr(), w0t.data_ptr(), b0.data_ptr(), w2t.data_ptr(), b2.data_ptr(),
-                                 out.data_ptr(), ws.data_ptr(), B, mc, ted, _stream()), "stedm_time_embed")
+    check(fn(t.data_ptr(), freqs.data_ptr(), w0t.data_ptr(), b0.data_ptr(), w2t.data_ptr(), b2.data_ptr(),
+             out.data_ptr(), ws.data_ptr(), B, mc, ted, _stream()), name)
     return out
 
 
@@ -997,10 +1004,38 @@ def step_advance(step_idx: torch.Tensor, delta: int = 1) -> None:
 
 
 def step_set_t(ts_table: torch.Tensor, step_idx: torch.Tensor, t_buf: torch.Tensor) -> None:
-    _chk(ts_table, torch.int64, "ts_table")
-    _chk(t_buf, torch.int64, "t_buf")
-    check(lib().stedm_step_set_t(ts_table.data_ptr(), step_idx.data_ptr(), t_buf.data_ptr(), t_buf.shape[0], _stream()),
-          "stedm_step_set_t")
+    """t_buf[:] = ts_table[step_idx[0]]; int64 tables (DDIM) or float32 tables (DPM-Solver's model times, stedm_step_set_t_f32)."""
+    dt = torch.float32 if ts_table.dtype == torch.float32 else torch.int64
+    _chk(ts_table, dt, "ts_table")
+    _chk(t_buf, dt, "t_buf")
+    _chk(step_idx, torch.int32, "step_idx")
+    fn, name = (lib().stedm_step_set_t_f32, "stedm_step_set_t_f32") if dt == torch.float32 else (lib().stedm_step_set_t, "stedm_step_set_t")
+    check(fn(ts_table.data_ptr(), step_idx.data_ptr(), t_buf.data_ptr(), t_buf.shape[0], _stream()), name)
+
+
+# ------------------------------------------------------------------------------------------- DPM-Solver++(2M)
+DPM_NCOEF = 6       # STEDM_DPM_NCOEF: {alpha_i, sigma_i, r, A, inv_r0, 0.5 A}
+
+
+def dpm_step(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], x0_prev: torch.Tensor, coefs: torch.Tensor,
+             step_idx: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, pred_x0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One DPM-Solver++(2M) step in place on x and x0_prev (stedm_dpm_step): eps = e_u + s (e_c - e_u) (e_u None: e_c),
+    x0 = (x - sigma eps) / alpha, x = (r x - A x0) - 0.5 A inv_r0 (x0 - x0_prev), x0_prev = x0 (pred_x0, if given, = x0).
+    coefs: device float32 [S, DPM_NCOEF]; step_idx: device int32 [1] selecting the row (None: row 0)."""
+    _chk(x, name="x"); _chk(e_c, name="e_c"); _chk(x0_prev, name="x0_prev"); _chk(coefs, name="coefs")
+    shp = tuple(x.shape)
+    for t, nm in ((e_c, "e_c"), (e_u, "e_u"), (x0_prev, "x0_prev"), (pred_x0, "pred_x0")):
+        if t is not None:
+            _chk(t, name=nm)
+            if tuple(t.shape) != shp:
+                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {shp}")
+    if coefs.dim() != 2 or coefs.shape[1] != DPM_NCOEF:
+        raise ValueError(f"coefs must be [S, {DPM_NCOEF}], got {tuple(coefs.shape)}")
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+    check(lib().stedm_dpm_step(x.data_ptr(), e_c.data_ptr(), _ptr(e_u), x0_prev.data_ptr(), _ptr(pred_x0), coefs.data_ptr(),
+                               _ptr(step_idx), float(cfg_scale), x.numel(), _stream()), "stedm_dpm_step")
+    return x
 
 
 

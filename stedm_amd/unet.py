@@ -852,7 +852,8 @@ class UNetModel(nn.Module):
     @torch.no_grad()
     def forward(self, x, timesteps=None, context=None, y=None, **kwargs):
         """openaimodel.py:761-806. x [B,C,H,W] fp32 NCHW (already concatenated with c_concat by the
-        DiffusionWrapper), timesteps int64 [B], context [B, 4*model_channels] style vector -> eps [B,out,H,W]."""
+        DiffusionWrapper), timesteps [B] (integer: int64; floating: float32, fractional model times allowed), context [B, 4*model_channels]
+        style vector -> eps [B,out,H,W]."""
         assert (y is not None) == (self.num_classes is not None), \
             "must specify y if and only if the model is class-conditional"
         return self.forward_parts(x, None, timesteps, context)
@@ -925,7 +926,14 @@ class UNetModel(nn.Module):
         assert c1 + c2 == self.in_channels, f"expected {self.in_channels} input channels, got {c1}+{c2}"
         if any(cx is None for cx in contexts):
             raise ValueError("context (style vector) is required: middle_block[1] is a ResBlockStyle (openaimodel.py:636-643)")
-        timesteps = timesteps.to(device=x.device, dtype=torch.int64).contiguous()
+        # integer timesteps run as int64 (training, DDIM); floating ones stay float32: DPM-Solver's fractional model times
+        # (dpm_solver.py:246-253), which timestep_embedding allows (util.py:151-171). No truncation either way.
+        if not isinstance(timesteps, torch.Tensor):
+            timesteps = torch.as_tensor(timesteps)
+        t_float = timesteps.is_floating_point()
+        if t_float and self._tape is not None:
+            raise TypeError("fractional (floating) timesteps are an inference path: the training forward takes integer timesteps")
+        timesteps = timesteps.to(device=x.device, dtype=torch.float32 if t_float else torch.int64).contiguous()
         c = self._consts
         ted = self.model_channels * 4
         for cx in contexts:
