@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 14
+#define STEDM_ABI_VERSION 15
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -378,6 +378,25 @@ int stedm_step_set_t_f32(const float* ts_table, const int32_t* step_idx, float* 
 #define STEDM_DPM_NCOEF 6
 int stedm_dpm_step(float* x, const float* e_c, const float* e_u, float* x0_prev, float* pred_x0, const float* coefs,
                    const int32_t* step_idx, float cfg_scale, long n, void* stream);
+
+/* ---- PLMS update (ABI 15) ------------------------------------------------------------------ */
+/* One update of the reference's PLMS sampler (plms.py:173-239, ddim_eta = 0), elementwise over n fp32 elements:
+ *   e = e_u + s (e_c - e_u)  (e_u NULL: e = e_c; plain CFG, no std rescale, plms.py:178-192)
+ *   e' by phase:  STEDM_PLMS_EULER      e; ring slot 0 = e                  (iteration 0, first half: plms.py:219-221)
+ *                 STEDM_PLMS_HEUN       (ring slot 0 + e) / 2               (iteration 0, second half, e at (x_tmp, t_next): :222-223)
+ *                 STEDM_PLMS_MULTISTEP  i = n_iters - 1 - *step_idx, order min(i, 3) (:224-232), e_{i-j} read from ring slot
+ *                                       (i - j) mod 4, e written to slot i mod 4: (3 e - e_{i-1}) / 2,
+ *                                       (23 e - 16 e_{i-1} + 5 e_{i-2}) / 12, (55 e - 59 e_{i-1} + 37 e_{i-2} - 9 e_{i-3}) / 24
+ *   x0 = (x - sqrt(1 - a_t) e') / sqrt(a_t),  x_prev = sqrt(a_prev) x0 + sqrt(1 - a_prev) e'   (get_x_prev_and_pred_x0, :199-216)
+ * EULER writes x_prev to x_tmp (x untouched, pred_x0 ignored); HEUN and MULTISTEP write it to x in place, pred_x0 (may be NULL) = x0.
+ * ring: DEVICE fp32 [4][n], the CFG-combined eps history the loop keeps in old_eps (:159-162). coefs: the DDIM table [n_iters][4] of
+ * stedm_ddim_step, row *step_idx (DEVICE int32, required; the table index = n_iters - 1 - iteration). The reference's operations in its
+ * order, each rounded once. pred_x0 and x_tmp may alias e_c / e_u element for element. */
+#define STEDM_PLMS_EULER 0
+#define STEDM_PLMS_HEUN 1
+#define STEDM_PLMS_MULTISTEP 2
+int stedm_plms_step(float* x, const float* e_c, const float* e_u, float* ring, const float* coefs, const int32_t* step_idx,
+                    int n_iters, int phase, float cfg_scale, float* pred_x0, float* x_tmp, long n, void* stream);
 
 /* ---- style path: set-ViT encoder (networks/vit_set.py), aggregation blocks, layout rescaler -------------------- */
 /* SPT vit_set.py:84-107 + token assembly :175-186. img [B][ns][H][W][3] fp32 -> x [B][ntok+2][dim]:

@@ -1018,6 +1018,119 @@ extern "C" int stedm_dpm_step(float* x, const float* e_c, const float* e_u, floa
 }
 
 // ------------------------------------------------------------------------------------------------
+// PLMS update (plms.py:173-239, ddim_eta = 0), elementwise over the flat [B*C*H*W] tensors:
+//   e   = e_u + s (e_c - e_u)                              get_model_output (plms.py:178-192; no std rescale); e_u NULL: e = e_c
+//   e'  = phase EULER: e (and ring[0] = e)                 pseudo improved Euler, first half (:219-221)
+//         phase HEUN:  (ring[0] + e) / 2                   second half, e = the model at (x_tmp, t_next) (:222-223)
+//         phase MULTISTEP, i = n_iters - 1 - *step_idx, order min(i, 3), e_{i-j} in ring slot (i - j) mod 4, ring[i mod 4] = e:
+//           (3 e - e1) / 2,  (23 e - 16 e1 + 5 e2) / 12,  (55 e - 59 e1 + 37 e2 - 9 e3) / 24   (:224-232; order 0: e' = e)
+//   x0  = (x - sqrt(1 - a_t) e') / sqrt(a_t);  x_prev = sqrt(a_prev) x0 + sqrt(1 - a_prev) e'   get_x_prev_and_pred_x0 (:199-216), sigma 0
+// EULER writes x_prev to x_tmp and leaves x alone; HEUN and MULTISTEP write it to x (pred_x0 = x0 if given). The reference's operations
+// in its order, each rounded once (no FMA contraction, true divisions), so with equal inputs torch's CPU arithmetic gives the same bits.
+// Row *step_idx of the DDIM table coefs [n_iters][4] = {a_t, a_prev, sigma (0), sqrt(1 - a_t)}. One thread = four consecutive elements:
+// float4 accesses when every pointer (the ring's slots included) is 16-byte aligned, elementwise for the tail and otherwise. pred_x0 and
+// x_tmp may alias e_c / e_u element for element (each element is read before it is written).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float plms_update1(float xv, float ec, float eu, float r0, float r1, float r2, bool cfg, float s, int phase,
+                                              int order, float sqrt_at, float sq1m, float sqrt_ap, float dir_c, float& e, float& x0) {
+#pragma clang fp contract(off)       // every product and sum rounded on its own (HIP's default contracts them into FMAs across statements)
+  e = cfg ? eu + s * (ec - eu) : ec;
+  float ep = e;
+  if (phase == STEDM_PLMS_HEUN) {
+    ep = (r0 + e) / 2.0f;
+  } else if (phase == STEDM_PLMS_MULTISTEP) {
+    if (order == 1) ep = (3.0f * e - r0) / 2.0f;
+    else if (order == 2) ep = (23.0f * e - 16.0f * r0 + 5.0f * r1) / 12.0f;
+    else if (order >= 3) ep = (55.0f * e - 59.0f * r0 + 37.0f * r1 - 9.0f * r2) / 24.0f;
+  }
+  x0 = (xv - sq1m * ep) / sqrt_at;     // IEEE division (HIP's default: correctly rounded fp32 divide)
+  return sqrt_ap * x0 + dir_c * ep;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) plms_step_kernel(float* x, const float* e_c, const float* e_u, float* ring, const float* __restrict__ coefs,
+                                                        const int32_t* __restrict__ step_idx, int n_iters, int phase, float s, float* pred_x0,
+                                                        float* x_tmp, long n) {
+  const long e0 = 4 * ((long)blockIdx.x * 256 + threadIdx.x);
+  if (e0 >= n) return;
+  const int index = *step_idx;
+  const float* row = coefs + (long)index * 4;
+  const float a_t = row[0], a_prev = row[1], sq1m = row[3];
+  const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dir_c = sqrtf(1.0f - a_prev);
+  const int i = phase == STEDM_PLMS_MULTISTEP ? n_iters - 1 - index : 0;
+  const int order = i < 0 ? 0 : (i > 3 ? 3 : i);
+  // slots read: HEUN the e_t of EULER (slot 0); MULTISTEP e_{i-1}, e_{i-2}, e_{i-3}. Slot written: EULER 0, MULTISTEP i mod 4.
+  const float* r0p = ring + (phase == STEDM_PLMS_HEUN ? 0L : (long)((i - 1) & 3) * n);
+  const float* r1p = ring + (long)((i - 2) & 3) * n;
+  const float* r2p = ring + (long)((i - 3) & 3) * n;
+  float* wp = ring + (long)(i & 3) * n;
+  const bool cfg = e_u != nullptr;
+  const bool rd0 = phase == STEDM_PLMS_HEUN || (phase == STEDM_PLMS_MULTISTEP && order >= 1);
+  const bool rd1 = phase == STEDM_PLMS_MULTISTEP && order >= 2, rd2 = phase == STEDM_PLMS_MULTISTEP && order >= 3;
+  const bool wr = phase != STEDM_PLMS_HEUN;
+  float* out = phase == STEDM_PLMS_EULER ? x_tmp : x;
+  float* px = phase == STEDM_PLMS_EULER ? nullptr : pred_x0;
+  float xv[4], ec[4], eu[4], r0[4], r1[4], r2[4], o[4], et[4], q[4];
+  const bool full = VEC && e0 + 4 <= n;
+  const int cnt = full ? 4 : (int)(n - e0 < 4 ? n - e0 : 4);
+  auto ld = [&](const float* p, bool use, float (&v)[4]) {
+    if (!use) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = 0.0f;
+    } else if (full) {
+      const float4 t = *reinterpret_cast<const float4*>(p + e0);
+      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = j < cnt ? p[e0 + j] : 0.0f;
+    }
+  };
+  auto st = [&](float* p, const float (&v)[4]) {
+    if (full) {
+      *reinterpret_cast<float4*>(p + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < cnt) p[e0 + j] = v[j];
+    }
+  };
+  ld(x, true, xv);
+  ld(e_c, true, ec);
+  ld(e_u, cfg, eu);
+  ld(r0p, rd0, r0);
+  ld(r1p, rd1, r1);
+  ld(r2p, rd2, r2);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    o[j] = plms_update1(xv[j], ec[j], eu[j], r0[j], r1[j], r2[j], cfg, s, phase, order, sqrt_at, sq1m, sqrt_ap, dir_c, et[j], q[j]);
+  if (wr) st(wp, et);
+  st(out, o);
+  if (px) st(px, q);
+}
+
+extern "C" int stedm_plms_step(float* x, const float* e_c, const float* e_u, float* ring, const float* coefs, const int32_t* step_idx,
+                               int n_iters, int phase, float cfg_scale, float* pred_x0, float* x_tmp, long n, void* stream) {
+  STEDM_CHECK_ARG(x && e_c && ring && coefs && step_idx, "plms_step: null pointer");
+  STEDM_CHECK_ARG(phase == STEDM_PLMS_EULER || phase == STEDM_PLMS_HEUN || phase == STEDM_PLMS_MULTISTEP, "plms_step: bad phase %d", phase);
+  STEDM_CHECK_ARG(phase != STEDM_PLMS_EULER || x_tmp, "plms_step: the Euler phase needs x_tmp");
+  STEDM_CHECK_ARG(n_iters > 0, "plms_step: bad iteration count %d", n_iters);
+  STEDM_CHECK_ARG(n > 0 && n <= (1L << 40), "plms_step: bad element count %ld", n);
+  const bool aligned = n % 4 == 0 &&
+                       ((uintptr_t)x | (uintptr_t)e_c | (uintptr_t)e_u | (uintptr_t)ring | (uintptr_t)pred_x0 | (uintptr_t)x_tmp) % 16 == 0;
+  const long groups = (n + 3) / 4;
+  const long blocks = (groups + 255) / 256;
+  STEDM_CHECK_ARG(blocks <= 0x7FFFFFFFL, "plms_step: %ld elements exceed one launch", n);
+  if (aligned)
+    plms_step_kernel<true><<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(x, e_c, e_u, ring, coefs, step_idx, n_iters, phase, cfg_scale,
+                                                                            pred_x0, x_tmp, n);
+  else
+    plms_step_kernel<false><<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(x, e_c, e_u, ring, coefs, step_idx, n_iters, phase, cfg_scale,
+                                                                             pred_x0, x_tmp, n);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Graph helpers
 // ------------------------------------------------------------------------------------------------
 extern "C" int stedm_graph_begin(void* stream) {

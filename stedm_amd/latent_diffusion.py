@@ -24,10 +24,11 @@ from . import ops
 from ._lib import StedmHipError
 from .ddim import DDIMSampler
 from .dpm_solver import DPMSolverSampler
+from .plms import PLMSSampler
 from .schedule import NoiseSchedule
 from .unet import UNetModel
 
-SAMPLERS = ("ddim", "dpm_solver")          # sample_log / predict_latents(sampler=...)
+SAMPLERS = ("ddim", "dpm_solver", "plms")          # sample_log / predict_latents(sampler=...)
 
 
 def instantiate_from_config(config):
@@ -568,13 +569,16 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):
         """ddpm.py:1237-1250. sampler: "ddim" (the reference's) or "dpm_solver" (DPMSolverSampler, the reference's
-        ldm/models/diffusion/dpm_solver: DPM-Solver++(2M), ddim_steps model evaluations)."""
+        ldm/models/diffusion/dpm_solver: DPM-Solver++(2M), ddim_steps model evaluations) or "plms" (PLMSSampler, the reference's
+        plms.py: DDIM's schedule, n iterations cost n + 1 model evaluations, mask / x0 as DDIM; returns (x, intermediates))."""
         if not ddim:
             raise NotImplementedError("ancestral DDPM sampling is dead code for the shipped configs (SURVEY.md §2.1 #5)")
         if sampler not in SAMPLERS:
             raise ValueError(f"unknown sampler {sampler!r}; choose from {SAMPLERS}")
         if sampler == "dpm_solver":
             sampler = DPMSolverSampler(self, device=self.device, use_graph=self.use_graph)
+        elif sampler == "plms":
+            sampler = PLMSSampler(self, use_graph=self.use_graph)
         else:
             sampler = DDIMSampler(self, use_graph=self.use_graph)
         shape = (self.channels, self.image_size, self.image_size)
@@ -697,11 +701,17 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
     its kept region is close to x0, not pasted from it.
 
     sampler: "ddim" (default) or "dpm_solver" (DPM-Solver++(2M), stedm_amd/dpm_solver.py): ddim_steps is then the number of model
-    evaluations; it draws no noise after x_T, and eta != 0, noises and mask are refused."""
+    evaluations; it draws no noise after x_T, and eta != 0, noises and mask are refused. "plms" (PLMS, stedm_amd/plms.py): DDIM's
+    schedule and masked sampling, ddim_steps as for DDIM (n iterations, n + 1 model evaluations); it draws no noise after x_T (and the
+    blend's), and eta != 0 (ValueError, as the reference) and noises are refused."""
     if sampler not in SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}; choose from {SAMPLERS}")
     if sampler == "dpm_solver" and (eta != 0.0 or noises is not None or mask is not None):
         raise NotImplementedError("sampler='dpm_solver': eta != 0, per-step noises and masked sampling are DDIM options")
+    if sampler == "plms" and eta != 0.0:
+        raise ValueError("sampler='plms': ddim_eta must be 0 for PLMS")
+    if sampler == "plms" and noises is not None:
+        raise NotImplementedError("sampler='plms': PLMS draws no per-step noise")
     masked = mask is not None
     z, c_0 = model.get_input(ldm_batch, "image", predict_only=not (masked and x0 is None))
     kw = {} if x_T is None else {"x_T": x_T}
@@ -764,7 +774,8 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
     mask / x0 (masked sampling, see predict_latents): given for the global batch (their rows lo:hi are taken), for the shard, or (mask
     only) as one row for every sample. The blend's noise is keyed by (seed, global sample id), like x_T.
 
-    sampler="dpm_solver" (through **kw): DPM-Solver draws nothing after x_T, so the per-sample x_T alone makes the shards invariant."""
+    sampler="dpm_solver" (through **kw): DPM-Solver draws nothing after x_T, so the per-sample x_T alone makes the shards invariant.
+    sampler="plms" likewise, its masked blend keyed by the global sample id as DDIM's."""
     import torch.distributed as dist
     from . import parallel as par
     if rank is None or world is None:

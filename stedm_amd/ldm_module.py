@@ -127,7 +127,8 @@ class LDM_Diffusion(_Base):
         PNG files when `predict_dir` is set. Returns (images [B,H,W,3] uint8, segmentation [B,H,W] uint8) on the host.
 
         The config key `sampler` (optional; "ddim" when absent, as in the reference's configs) selects "dpm_solver" (DPM-Solver++(2M),
-        stedm_amd/dpm_solver.py); `ddim_steps` is then the number of model evaluations (DDIM's uniform stride makes 128 into 143)."""
+        stedm_amd/dpm_solver.py); `ddim_steps` is then the number of model evaluations (DDIM's uniform stride makes 128 into 143). "plms"
+        selects PLMS (stedm_amd/plms.py), DDIM's schedule with n + 1 model evaluations for n iterations."""
         cfg = self._cfg
         ldm_batch = self.prepare_batch(batch)
         sname = cfg.style_sampling["name"] if isinstance(cfg.style_sampling, dict) else cfg.style_sampling.name

@@ -1038,6 +1038,42 @@ def dpm_step(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], x0
     return x
 
 
+# ------------------------------------------------------------------------------------------- PLMS
+PLMS_EULER, PLMS_HEUN, PLMS_MULTISTEP = 0, 1, 2     # STEDM_PLMS_*: the phase argument of stedm_plms_step
+
+
+def plms_step(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], ring: torch.Tensor, coefs: torch.Tensor,
+              step_idx: torch.Tensor, n_iters: int, phase: int, cfg_scale: float = 1.0, pred_x0: Optional[torch.Tensor] = None,
+              x_tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One PLMS update (stedm_plms_step). e = e_u + s (e_c - e_u) (e_u None: e_c); by phase:
+      PLMS_EULER:     ring[0] = e, x_tmp = the DDIM step of x with e (x untouched);
+      PLMS_HEUN:      x = the DDIM step with (ring[0] + e) / 2, in place;
+      PLMS_MULTISTEP: i = n_iters - 1 - step_idx[0], order min(i, 3) over ring slots (i - j) mod 4, ring[i mod 4] = e, x in place.
+    pred_x0 (HEUN / MULTISTEP, optional) = x0. ring: device float32 [4, *x.shape]; coefs: the DDIM table [n_iters, 4]; step_idx: device
+    int32 [1], the table row."""
+    _chk(x, name="x"); _chk(e_c, name="e_c"); _chk(ring, name="ring"); _chk(coefs, name="coefs"); _chk(step_idx, torch.int32, "step_idx")
+    shp = tuple(x.shape)
+    for t, nm in ((e_c, "e_c"), (e_u, "e_u"), (pred_x0, "pred_x0"), (x_tmp, "x_tmp")):
+        if t is not None:
+            _chk(t, name=nm)
+            if tuple(t.shape) != shp:
+                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {shp}")
+    if tuple(ring.shape) != (4,) + shp:
+        raise ValueError(f"ring {tuple(ring.shape)} must be [4, *{shp}]")
+    if coefs.dim() != 2 or coefs.shape[1] != 4 or coefs.shape[0] != int(n_iters):
+        raise ValueError(f"coefs must be the DDIM table [{int(n_iters)}, 4], got {tuple(coefs.shape)}")
+    if tuple(step_idx.shape) != (1,):
+        raise ValueError(f"step_idx must be [1], got {tuple(step_idx.shape)}")
+    if phase not in (PLMS_EULER, PLMS_HEUN, PLMS_MULTISTEP):
+        raise ValueError(f"unknown PLMS phase {phase}")
+    if phase == PLMS_EULER and x_tmp is None:
+        raise ValueError("the Euler phase writes x_tmp")
+    check(lib().stedm_plms_step(x.data_ptr(), e_c.data_ptr(), _ptr(e_u), ring.data_ptr(), coefs.data_ptr(), step_idx.data_ptr(),
+                                int(n_iters), int(phase), float(cfg_scale), _ptr(pred_x0), _ptr(x_tmp), x.numel(), _stream()),
+          "stedm_plms_step")
+    return x
+
+
 
 # ------------------------------------------------------------------------------------------- training step (backward)
 def pack_conv_weight_strided(w: torch.Tensor, sn: int, sc: int, flip: bool, cout: int, cin: int, ks: int, prec: Precision, want_hi: bool = True,
