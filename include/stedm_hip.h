@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 15
+#define STEDM_ABI_VERSION 16
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -613,6 +613,20 @@ int stedm_philox_normal(float* out, int rows, int n, const long* sample_ids, int
 int stedm_ddim_mask_blend(float* img, const float* x0, const float* mask, long mask_bstride, long mask_cstride, const float* noise,
                           const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, const int32_t* step_idx, int B, int C, int HW,
                           long first_id, unsigned long long seed, void* stream);
+/* ---- ancestral DDPM step (ABI 16) ---------------------------------------------------------- */
+/* One iteration of the reference's p_sample_loop after the model call (ddpm.py:1050-1110, 1169-1217), in place on x [B][C][HW] fp32,
+ * t = *step_idx (DEVICE int32; a value outside [0, T) writes nothing):
+ *   x0 = sr x - srm1 eps;  x0 = clamp(x0, -1, 1) if clip;  mean = c1 x0 + c2 x;  x = mean + sigma z
+ * from row t of table [T][5] = {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,
+ * sigma = nonzero(t) exp(0.5 posterior_log_variance_clipped)}. eps [B][C][HW]. noise [B][C][HW], or NULL: z drawn in the kernel as row
+ * first_id + b of stedm_philox_normal with (seed, stream 0x10000 + t). mask (optional; strides as stedm_ddim_mask_blend): after the
+ * step, x = (sqrt_ac[t] x0 + sqrt_1mac[t] z') mask + (1 - mask) x with the given x0 [B][C][HW]; z' = mask_noise, or row first_id + b with
+ * (mask_seed, stream 0x8000 + t) - bit for bit the step followed by stedm_ddim_mask_blend at index t (the blend is that kernel's
+ * arithmetic). The step rounds each product and sum once. */
+int stedm_ddpm_step(float* x, const float* eps, const float* table, const int32_t* step_idx, int T, int clip, const float* noise,
+                    const float* mask, long mask_bstride, long mask_cstride, const float* x0, const float* mask_noise,
+                    const float* sqrt_ac, const float* sqrt_1mac, int B, int C, int HW, long first_id, unsigned long long seed,
+                    unsigned long long mask_seed, void* stream);
 
 /* loss = mean|target - pred| (ddpm.py:282-295 'l1' + :1030-1040), d_pred = grad_scale * sign(pred - target) / n (NULL: skip).
  * ws: 1024 doubles. */

@@ -1281,6 +1281,126 @@ extern "C" int stedm_ddim_mask_blend(float* img, const float* x0, const float* m
 }
 
 
+// ------------------------------------------------------------------------------------------------ ancestral DDPM step
+// One iteration of the reference's p_sample_loop (ddpm.py:1169-1217) after the model call, in place on x [B][C][HW], t = *step_idx:
+//   x0   = sr[t] x - srm1[t] eps                          predict_start_from_noise (ddpm.py:219-223)
+//   x0   = clamp(x0, -1, 1) when clip                     p_mean_variance (:1069-1070)
+//   mean = c1[t] x0 + c2[t] x                             q_posterior (:225-232)
+//   x    = mean + sigma[t] z                              p_sample (:1100-1110); sigma = nonzero(t) exp(0.5 logvar_clipped[t]), from the table
+//   mask (optional): x = (sqrt_ac[t] x0m + sqrt_1mac[t] z') m + (1 - m) x    the blend after the step (:1207-1209)
+// table: [T][5] rows {sr, srm1, c1, c2, sigma}. z: given ([B][C][HW]) or stedm_philox_normal's row of sample first_id + b with stream
+// 0x10000 + t; z': given, or the row with stream 0x8000 + t and mask_seed - what stedm_ddim_mask_blend draws for that index. The step
+// rounds every product and sum on its own (contraction off), so with equal inputs torch's CPU arithmetic gives the same bits. The blend is
+// ddim_mask_blend_kernel's expression compiled the same way as there (HIP's default contraction, which fuses one product of each sum into
+// an FMA), so the fused blend equals the step followed by stedm_ddim_mask_blend bit for bit, and torch's unfused blend to an ulp (exactly
+// where the mask is 0). Launch and layout: those of ddim_mask_blend_kernel (one thread = one group of four elements of a sample's row;
+// float4 when HW % 4 == 0 and every operand is 16-byte aligned, the scalar tail form otherwise). A step index outside [0, T) writes nothing.
+__device__ __forceinline__ float ddpm_update1(float xv, float e, float z, float sr, float srm1, float c1, float c2, float sig, bool clip) {
+#pragma clang fp contract(off)       // every product and sum rounded on its own (HIP's default contracts them into FMAs across statements)
+  float q = sr * xv - srm1 * e;
+  if (clip) q = q < -1.0f ? -1.0f : (q > 1.0f ? 1.0f : q);            // clamp_(-1, 1); NaN passes through, as in torch
+  const float mean = c1 * q + c2 * xv;
+  return mean + sig * z;
+}
+
+__device__ __forceinline__ float ddpm_blend1(float o, float x0, float z, float m, float ca, float cn) {
+  const float q = __fadd_rn(__fmul_rn(ca, x0), __fmul_rn(cn, z));       // ddim_mask_blend_kernel's expression, its contraction mode
+  return __fadd_rn(__fmul_rn(q, m), __fmul_rn(__fsub_rn(1.0f, m), o));
+}
+
+template <bool VEC, bool MASK>
+__global__ void __launch_bounds__(256) ddpm_step_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ table,
+                                                        const int32_t* __restrict__ step_idx, int T, int clip, const float* __restrict__ noise,
+                                                        const float* __restrict__ mask, long mbs, long mcs, const float* __restrict__ x0m,
+                                                        const float* __restrict__ mnoise, const float* __restrict__ sa, const float* __restrict__ s1,
+                                                        int C, int HW, unsigned id0, unsigned seed, unsigned mseed) {
+  const int b = blockIdx.y;
+  const int n = C * HW;
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (4 * g >= n) return;
+  const int t = *step_idx;
+  if (t < 0 || t >= T) return;
+  const float* row = table + (long)t * 5;
+  const float sr = row[0], srm1 = row[1], c1 = row[2], c2 = row[3], sig = row[4];
+  const long base = (long)b * n;
+  auto ld = [&](const float* p, float (&v)[4]) {
+    if (VEC) {
+      const float4 q = *reinterpret_cast<const float4*>(p + base + 4 * g);
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = 4 * g + j < n ? p[base + 4 * g + j] : 0.0f;
+    }
+  };
+  float xv[4], ev[4], z[4], o[4];
+  ld(x, xv);
+  ld(eps, ev);
+  if (noise) ld(noise, z);
+  else philox_normal4((unsigned)g, 0x10000u + (unsigned)t, seed, id0 + (unsigned)b, z);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = ddpm_update1(xv[j], ev[j], z[j], sr, srm1, c1, c2, sig, clip != 0);
+  if (MASK) {
+    const float ca = sa[t], cn = s1[t];
+    float xk[4], m[4], zb[4];
+    ld(x0m, xk);
+    if (mnoise) ld(mnoise, zb);
+    else philox_normal4((unsigned)g, 0x8000u + (unsigned)t, mseed, id0 + (unsigned)b, zb);
+    if (VEC) {                                          // HW % 4 == 0: the group lies in one channel plane
+      const int c = (4 * g) / HW, p = 4 * g - c * HW;
+      const float4 w = *reinterpret_cast<const float4*>(mask + b * mbs + c * mcs + p);
+      m[0] = w.x; m[1] = w.y; m[2] = w.z; m[3] = w.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = 4 * g + j;
+        const bool in = e < n;
+        const int c = in ? e / HW : 0, p = in ? e - c * HW : 0;
+        m[j] = in ? mask[b * mbs + c * mcs + p] : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = ddpm_blend1(o[j], xk[j], zb[j], m[j], ca, cn);
+  }
+  if (VEC) {
+    *reinterpret_cast<float4*>(x + base + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * g + j < n) x[base + 4 * g + j] = o[j];
+  }
+}
+
+extern "C" int stedm_ddpm_step(float* x, const float* eps, const float* table, const int32_t* step_idx, int T, int clip, const float* noise,
+                               const float* mask, long mask_bstride, long mask_cstride, const float* x0, const float* mask_noise,
+                               const float* sqrt_ac, const float* sqrt_1mac, int B, int C, int HW, long first_id, unsigned long long seed,
+                               unsigned long long mask_seed, void* stream) {
+  STEDM_CHECK_ARG(x && eps && table && step_idx, "ddpm_step: null pointer");
+  STEDM_CHECK_ARG(T > 0, "ddpm_step: bad table length %d", T);
+  STEDM_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && HW > 0 && (long)C * HW <= 0x7FFFFFFFL, "ddpm_step: bad shape B=%d C=%d HW=%d", B, C, HW);
+  STEDM_CHECK_ARG(first_id >= 0 && first_id + B <= (1L << 32), "ddpm_step: sample ids %ld + %d outside [0, 2^32]", first_id, B);
+  const bool masked = mask != nullptr;
+  STEDM_CHECK_ARG(!masked || (x0 && sqrt_ac && sqrt_1mac), "ddpm_step: the mask blend needs x0, sqrt_ac and sqrt_1mac");
+  STEDM_CHECK_ARG(!masked || mask_cstride == 0 || mask_cstride == HW, "ddpm_step: mask channel stride %ld (0 or HW=%d)", mask_cstride, HW);
+  STEDM_CHECK_ARG(!masked || mask_bstride == 0 || mask_bstride == (mask_cstride ? (long)C * HW : (long)HW),
+                  "ddpm_step: mask batch stride %ld (0 or the mask's per-sample size)", mask_bstride);
+  const int n = C * HW;
+  const bool aligned = ((uintptr_t)x | (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)mask | (uintptr_t)x0 | (uintptr_t)mask_noise) % 16 == 0;
+  const bool vec = HW % 4 == 0 && aligned;
+  dim3 grid(((n + 3) / 4 + 255) / 256, B);
+  const unsigned id0 = (unsigned)first_id, sd = (unsigned)(seed & 0xFFFFFFFFull), msd = (unsigned)(mask_seed & 0xFFFFFFFFull);
+#define STEDM_DDPM_LAUNCH(V, M)                                                                                                      \
+  ddpm_step_kernel<V, M><<<grid, 256, 0, as_stream(stream)>>>(x, eps, table, step_idx, T, clip, noise, mask, mask_bstride, mask_cstride, \
+                                                              x0, mask_noise, sqrt_ac, sqrt_1mac, C, HW, id0, sd, msd)
+  if (vec && masked) STEDM_DDPM_LAUNCH(true, true);
+  else if (vec) STEDM_DDPM_LAUNCH(true, false);
+  else if (masked) STEDM_DDPM_LAUNCH(false, true);
+  else STEDM_DDPM_LAUNCH(false, false);
+#undef STEDM_DDPM_LAUNCH
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+
 // ------------------------------------------------------------------------------------------------ row-major im2col (16-bit), generic-shape fallback
 // The implicit-GEMM kernels tile the output grid in runs of 128 / 256 pixels that must align with image rows (conv_geometry): latent widths
 // that are not powers of two (96 x 96, 40 x 40, 24 x 24: anything UNetModel of the reference accepts, openaimodel.py:761-806 only needs

@@ -22,13 +22,16 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import StedmHipError
+from .ancestral import AncestralSampler
 from .ddim import DDIMSampler
 from .dpm_solver import DPMSolverSampler
 from .plms import PLMSSampler
-from .schedule import NoiseSchedule
+from .schedule import POSTERIOR_BUFFERS, NoiseSchedule, PosteriorSchedule
 from .unet import UNetModel
 
 SAMPLERS = ("ddim", "dpm_solver", "plms")          # sample_log / predict_latents(sampler=...)
+ANCESTRAL = "ddpm"                                  # the reference's 1000-step ancestral chain: sample_log(ddim=False) / sampler="ddpm"
+ALL_SAMPLERS = SAMPLERS + (ANCESTRAL,)
 
 
 def instantiate_from_config(config):
@@ -159,7 +162,7 @@ class LatentDiffusion(nn.Module):
                  loss_type="l2", image_size=256, channels=3, conditioning_key=None, parameterization="eps",
                  cond_stage_config=None, first_stage_config=None, cond_stage_trainable=False, first_stage_key="image",
                  cond_stage_key="image", log_every_t=100, scale_factor=1.0, use_graph=False, use_ema=True, scale_by_std=False,
-                 l_simple_weight=1.0, original_elbo_weight=0.0, learn_logvar=False, **ignored):
+                 l_simple_weight=1.0, original_elbo_weight=0.0, learn_logvar=False, clip_denoised=True, v_posterior=0., **ignored):
         super().__init__()
         assert parameterization == "eps", "the reference configs use eps-prediction"
         self.parameterization = parameterization
@@ -169,6 +172,10 @@ class LatentDiffusion(nn.Module):
         self.cond_stage_key = cond_stage_key
         self.cond_stage_trainable = cond_stage_trainable
         self.log_every_t = log_every_t
+        self.clip_denoised = bool(clip_denoised)      # ddpm.py:63, 83: the ancestral chain's clamp of the predicted x0
+        if v_posterior != 0.:
+            raise NotImplementedError("v_posterior != 0: no reference config sets it (ddpm.py:69 defaults to 0)")
+        self.v_posterior = 0.
         self.loss_type = loss_type
         if learn_logvar or original_elbo_weight != 0.0 or l_simple_weight != 1.0:
             raise NotImplementedError("learn_logvar / original_elbo_weight / l_simple_weight: the reference configs keep the defaults "
@@ -196,13 +203,18 @@ class LatentDiffusion(nn.Module):
     # ------------------------------------------------------------------------------------------ schedule
     def register_schedule(self, given_betas=None, beta_schedule="linear", timesteps=1000, linear_start=1e-4,
                           linear_end=2e-2, cosine_s=8e-3):
-        """ddpm.py:120-172 (the buffers the hot path reads)."""
+        """ddpm.py:120-172 (the buffers the hot path reads). The ancestral sampler's buffers (POSTERIOR_BUFFERS: posterior mean
+        coefficients and log variance, sqrt_recip(m1)_alphas_cumprod, log_one_minus_alphas_cumprod) are registered non-persistent: the
+        state dict keeps its layout, and a checkpoint's copies of them load as unexpected keys as before."""
         assert given_betas is None
         ns = NoiseSchedule.make(timesteps, linear_start, linear_end, beta_schedule)
         self.num_timesteps = ns.num_timesteps
         self.linear_start, self.linear_end = linear_start, linear_end
         for name in ("betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod"):
             self.register_buffer(name, torch.from_numpy(getattr(ns, name).copy()))
+        ps = PosteriorSchedule.make(timesteps, linear_start, linear_end, beta_schedule, v_posterior=getattr(self, "v_posterior", 0.))
+        for name in POSTERIOR_BUFFERS:
+            self.register_buffer(name, torch.from_numpy(getattr(ps, name).copy()), persistent=False)
 
     @property
     def device(self):
@@ -567,14 +579,39 @@ class LatentDiffusion(nn.Module):
 
     # ------------------------------------------------------------------------------------------ sampling
     @torch.no_grad()
+    def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None, quantize_denoised=False,
+               mask=None, x0=None, shape=None, **kwargs):
+        """ddpm.py:1219-1235: the ancestral chain (stedm_amd/ancestral.py, AncestralSampler.sample). Keywords the reference swallows are
+        ignored (log_every_t, verbose, ddim_steps, callbacks), except those whose effect it drops, which raise: eta != 0, temperature,
+        noise_dropout, score_corrector, quantize_denoised, and guidance (unconditional_guidance_scale != 1 with unconditional_conditioning).
+        Repo keywords: noises, noise_seed, sample_id0, mask_noises, mask_seed (AncestralSampler.p_sample_loop)."""
+        return AncestralSampler(self, use_graph=self.use_graph).sample(cond, batch_size=batch_size, return_intermediates=return_intermediates,
+                                                                       x_T=x_T, verbose=verbose, timesteps=timesteps,
+                                                                       quantize_denoised=quantize_denoised, mask=mask, x0=x0, shape=shape,
+                                                                       **kwargs)
+
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
+                      quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None, log_every_t=None, **kwargs):
+        """ddpm.py:1169-1217 on the HIP path (AncestralSampler.p_sample_loop; kwargs: its repo keywords)."""
+        return AncestralSampler(self, use_graph=self.use_graph).p_sample_loop(
+            cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, callback=callback, timesteps=timesteps,
+            quantize_denoised=quantize_denoised, mask=mask, x0=x0, img_callback=img_callback, start_T=start_T, log_every_t=log_every_t,
+            **kwargs)
+
+    @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):
         """ddpm.py:1237-1250. sampler: "ddim" (the reference's) or "dpm_solver" (DPMSolverSampler, the reference's
         ldm/models/diffusion/dpm_solver: DPM-Solver++(2M), ddim_steps model evaluations) or "plms" (PLMSSampler, the reference's
-        plms.py: DDIM's schedule, n iterations cost n + 1 model evaluations, mask / x0 as DDIM; returns (x, intermediates))."""
-        if not ddim:
-            raise NotImplementedError("ancestral DDPM sampling is dead code for the shipped configs (SURVEY.md §2.1 #5)")
-        if sampler not in SAMPLERS:
-            raise ValueError(f"unknown sampler {sampler!r}; choose from {SAMPLERS}")
+        plms.py: DDIM's schedule, n iterations cost n + 1 model evaluations, mask / x0 as DDIM; returns (x, intermediates)).
+        ddim=False (or sampler="ddpm"): the reference's ancestral chain, self.sample(cond, batch_size, return_intermediates=True,
+        **kwargs); ddim_steps is ignored and intermediates is a list."""
+        if sampler not in ALL_SAMPLERS:
+            raise ValueError(f"unknown sampler {sampler!r}; choose from {ALL_SAMPLERS}")
+        if not ddim or sampler == ANCESTRAL:
+            if sampler not in ("ddim", ANCESTRAL):
+                raise ValueError(f"ddim=False runs the ancestral chain; sampler={sampler!r} contradicts it")
+            return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
         if sampler == "dpm_solver":
             sampler = DPMSolverSampler(self, device=self.device, use_graph=self.use_graph)
         elif sampler == "plms":
@@ -684,7 +721,7 @@ def prepare_batch(batch, device=None) -> dict:
 def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: float = 0.0, cfg_scale: float = 1.0,
                     style_sampling: str = "nearby", x_T: Optional[torch.Tensor] = None, dedup_uncond: bool = True, noises=None,
                     mask: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None, sample_id0: int = 0,
-                    sampler: str = "ddim"):
+                    sampler: str = "ddim", noise_seed: Optional[int] = None):
     """Lightning-free restatement of LDM_Diffusion.predict_step (modules/ldm_diffusion.py:76-91) up to the sampled latents:
     conditional get_input, unconditional batch {image: 0, segmentation: same, style_imgs: -2}, DDIM + CFG.
 
@@ -703,9 +740,16 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
     sampler: "ddim" (default) or "dpm_solver" (DPM-Solver++(2M), stedm_amd/dpm_solver.py): ddim_steps is then the number of model
     evaluations; it draws no noise after x_T, and eta != 0, noises and mask are refused. "plms" (PLMS, stedm_amd/plms.py): DDIM's
     schedule and masked sampling, ddim_steps as for DDIM (n iterations, n + 1 model evaluations); it draws no noise after x_T (and the
-    blend's), and eta != 0 (ValueError, as the reference) and noises are refused."""
-    if sampler not in SAMPLERS:
-        raise ValueError(f"unknown sampler {sampler!r}; choose from {SAMPLERS}")
+    blend's), and eta != 0 (ValueError, as the reference) and noises are refused. "ddpm" (the ancestral chain of sample_log(ddim=False),
+    stedm_amd/ancestral.py): model.num_timesteps unguided steps, ddim_steps ignored; cfg_scale != 1 with style_sampling != "none" raises
+    (the reference's ancestral path has no guidance), as does eta != 0. Its step noise is drawn from (noise_seed, sample_id0 + b);
+    `noises` (optional) holds one N(0,1) tensor per step."""
+    if sampler not in ALL_SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}; choose from {ALL_SAMPLERS}")
+    if sampler == ANCESTRAL and cfg_scale != 1 and style_sampling != "none":
+        raise NotImplementedError("sampler='ddpm': the reference's ancestral chain has no classifier-free guidance (cfg_scale must be 1)")
+    if sampler == ANCESTRAL and eta != 0.0:
+        raise NotImplementedError("sampler='ddpm': eta is a DDIM option")
     if sampler == "dpm_solver" and (eta != 0.0 or noises is not None or mask is not None):
         raise NotImplementedError("sampler='dpm_solver': eta != 0, per-step noises and masked sampling are DDIM options")
     if sampler == "plms" and eta != 0.0:
@@ -719,6 +763,10 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
         kw["noises"] = noises
     if masked:
         kw.update(mask=latent_mask(model, mask, len(z)), x0=z if x0 is None else x0, mask_seed=mask_seed, sample_id0=int(sample_id0))
+    if sampler == ANCESTRAL:
+        kw.update(noise_seed=noise_seed, sample_id0=int(sample_id0))
+        out, _ = model.sample_log(c_0, batch_size=len(z), ddim=False, ddim_steps=ddim_steps, **kw)
+        return out
     if sampler != "ddim":
         kw["sampler"] = sampler
     if cfg_scale == 1 or style_sampling == "none":
@@ -775,7 +823,8 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
     only) as one row for every sample. The blend's noise is keyed by (seed, global sample id), like x_T.
 
     sampler="dpm_solver" (through **kw): DPM-Solver draws nothing after x_T, so the per-sample x_T alone makes the shards invariant.
-    sampler="plms" likewise, its masked blend keyed by the global sample id as DDIM's."""
+    sampler="plms" likewise, its masked blend keyed by the global sample id as DDIM's. sampler="ddpm": every step's noise is drawn in
+    the kernel from (seed, global sample id), so the ancestral chain is shard-invariant too."""
     import torch.distributed as dist
     from . import parallel as par
     if rank is None or world is None:
@@ -801,6 +850,8 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
     if mask is not None:
         rows = lambda a: a[lo:hi] if (a.shape[0] == int(global_batch) and a.shape[0] != n) else a
         kw.update(mask=rows(mask), x0=None if x0 is None else rows(x0), mask_seed=int(seed), sample_id0=lo)
+    if kw.get("sampler") == ANCESTRAL:
+        kw.update(noise_seed=int(seed), sample_id0=lo)
     from ._lib import StedmHipError
     err: Optional[StedmHipError] = None
     lat = None

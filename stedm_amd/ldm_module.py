@@ -128,7 +128,8 @@ class LDM_Diffusion(_Base):
 
         The config key `sampler` (optional; "ddim" when absent, as in the reference's configs) selects "dpm_solver" (DPM-Solver++(2M),
         stedm_amd/dpm_solver.py); `ddim_steps` is then the number of model evaluations (DDIM's uniform stride makes 128 into 143). "plms"
-        selects PLMS (stedm_amd/plms.py), DDIM's schedule with n + 1 model evaluations for n iterations."""
+        selects PLMS (stedm_amd/plms.py), DDIM's schedule with n + 1 model evaluations for n iterations. "ddpm" runs the reference's
+        ancestral chain (stedm_amd/ancestral.py: model.num_timesteps unguided steps, ddim_steps ignored; cfg_scale must then be 1)."""
         cfg = self._cfg
         ldm_batch = self.prepare_batch(batch)
         sname = cfg.style_sampling["name"] if isinstance(cfg.style_sampling, dict) else cfg.style_sampling.name

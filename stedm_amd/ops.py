@@ -999,6 +999,50 @@ def ddim_mask_blend(img: torch.Tensor, x0: torch.Tensor, mask: torch.Tensor, t: 
     return img
 
 
+def ddpm_step(x: torch.Tensor, eps: torch.Tensor, table: torch.Tensor, step_idx: torch.Tensor, clip_denoised: bool = True,
+              noise: Optional[torch.Tensor] = None, seed: int = 0, first_id: int = 0, mask: Optional[torch.Tensor] = None,
+              x0: Optional[torch.Tensor] = None, mask_noise: Optional[torch.Tensor] = None, mask_seed: int = 0,
+              sqrt_ac: Optional[torch.Tensor] = None, sqrt_1mac: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ancestral step in place on x [B, C, h, w] (stedm_ddpm_step), t = step_idx[0] (device int32 [1]):
+    x0 = sr x - srm1 eps, clamped to [-1, 1] if clip_denoised; x = c1 x0 + c2 x + sigma z with row t of table [T, 5] {sr, srm1, c1, c2,
+    sigma} (schedule.ddpm_step_table). z: noise, or row first_id + b of ops.philox_normal(seed, stream 0x10000 + t), drawn in the kernel.
+    mask [B|1, 1|C, h, w] with x0 (and the schedule buffers sqrt_ac / sqrt_1mac): then x = q_sample(x0, t) mask + (1 - mask) x, q_sample's
+    noise mask_noise or the draw of ops.ddim_mask_blend at index t with mask_seed."""
+    _chk(x, name="x"); _chk(eps, name="eps"); _chk(table, name="table"); _chk(step_idx, torch.int32, "step_idx")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, C, h, w], got {tuple(x.shape)}")
+    B, Cc, H, W = x.shape
+    shp = tuple(x.shape)
+    for t, nm in ((eps, "eps"), (noise, "noise"), (x0, "x0"), (mask_noise, "mask_noise")):
+        if t is not None:
+            _chk(t, name=nm)
+            if tuple(t.shape) != shp:
+                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {shp}")
+    if table.dim() != 2 or table.shape[1] != 5:
+        raise ValueError(f"table must be [T, 5], got {tuple(table.shape)}")
+    if tuple(step_idx.shape) != (1,):
+        raise ValueError(f"step_idx must be [1], got {tuple(step_idx.shape)}")
+    HW = H * W
+    bstride = cstride = 0
+    if mask is not None:
+        _chk(mask, name="mask")
+        if x0 is None or sqrt_ac is None or sqrt_1mac is None:
+            raise ValueError("the mask blend needs x0, sqrt_ac and sqrt_1mac")
+        _chk(sqrt_ac, name="sqrt_ac"); _chk(sqrt_1mac, name="sqrt_1mac")
+        if sqrt_ac.numel() < table.shape[0] or sqrt_1mac.numel() < table.shape[0]:
+            raise ValueError("sqrt_ac / sqrt_1mac must hold a value for every row of the table")
+        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cc) or tuple(mask.shape[2:]) != (H, W):
+            raise ValueError(f"mask {tuple(mask.shape)} must be [B|1, 1|C, h, w] for x {shp}")
+        cstride = HW if mask.shape[1] == Cc else 0
+        bstride = 0 if mask.shape[0] == 1 else mask.shape[1] * HW
+    check(lib().stedm_ddpm_step(x.data_ptr(), eps.data_ptr(), table.data_ptr(), step_idx.data_ptr(), int(table.shape[0]),
+                                1 if clip_denoised else 0, _ptr(noise), _ptr(mask), bstride, cstride, _ptr(x0) if mask is not None else None,
+                                _ptr(mask_noise) if mask is not None else None, _ptr(sqrt_ac) if mask is not None else None,
+                                _ptr(sqrt_1mac) if mask is not None else None, B, Cc, HW, int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                int(mask_seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "stedm_ddpm_step")
+    return x
+
+
 def step_advance(step_idx: torch.Tensor, delta: int = 1) -> None:
     check(lib().stedm_step_advance(step_idx.data_ptr(), delta, _stream()), "stedm_step_advance")
 

@@ -79,3 +79,47 @@ def make_ddim_tables(alphas_cumprod_f32: np.ndarray, S: int, eta: float = 0.0) -
     sig64 = eta * np.sqrt(recip32 * (1.0 - ap64) * (1.0 - ratio))
     sq32 = np.sqrt(one_minus_a).astype(np.float32)                   # np.sqrt on the f32 tensor (ddim.py:49)
     return DDIMTables(ts, a32, ap64.astype(np.float32), sig64.astype(np.float32), sq32)
+
+
+# ------------------------------------------------------------------------------------------------ ancestral (DDPM) sampling
+POSTERIOR_BUFFERS = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_variance", "posterior_log_variance_clipped",
+                     "posterior_mean_coef1", "posterior_mean_coef2", "log_one_minus_alphas_cumprod")
+
+
+@dataclass
+class PosteriorSchedule:
+    """The fp32 buffers of DDPM.register_schedule (ddpm.py:147-163) that the ancestral sampler reads (p_mean_variance / q_posterior,
+    ddpm.py:219-232, 1050-1080): each evaluated in f64 numpy from the f64 betas, then narrowed to fp32 as `to_torch` does."""
+    sqrt_recip_alphas_cumprod: np.ndarray       # f32 sqrt(1 / a)
+    sqrt_recipm1_alphas_cumprod: np.ndarray     # f32 sqrt(1 / a - 1)
+    posterior_variance: np.ndarray              # f32 (1 - v) b (1 - a_prev) / (1 - a) + v b
+    posterior_log_variance_clipped: np.ndarray  # f32 log(max(posterior_variance, 1e-20))
+    posterior_mean_coef1: np.ndarray            # f32 b sqrt(a_prev) / (1 - a)
+    posterior_mean_coef2: np.ndarray            # f32 (1 - a_prev) sqrt(1 - b) / (1 - a)
+    log_one_minus_alphas_cumprod: np.ndarray    # f32 log(1 - a)
+
+    @staticmethod
+    def make(timesteps: int = 1000, linear_start: float = 1e-4, linear_end: float = 2e-2, beta_schedule: str = "linear",
+             v_posterior: float = 0.0) -> "PosteriorSchedule":
+        betas = make_beta_schedule(timesteps, linear_start, linear_end, beta_schedule)
+        alphas = 1. - betas
+        ac = np.cumprod(alphas, axis=0)
+        ac_prev = np.append(1., ac[:-1])
+        f32 = lambda a: np.asarray(a, dtype=np.float64).astype(np.float32)
+        pv = (1 - v_posterior) * betas * (1. - ac_prev) / (1. - ac) + v_posterior * betas       # ddpm.py:156-157, in its order
+        return PosteriorSchedule(f32(np.sqrt(1. / ac)), f32(np.sqrt(1. / ac - 1)), f32(pv), f32(np.log(np.maximum(pv, 1e-20))),
+                                 f32(betas * np.sqrt(ac_prev) / (1. - ac)), f32((1. - ac_prev) * np.sqrt(alphas) / (1. - ac)),
+                                 f32(np.log(1. - ac)))
+
+
+def ddpm_step_table(sqrt_recip, sqrt_recipm1, coef1, coef2, log_var_clipped) -> np.ndarray:
+    """[T][5] fp32 rows {sr, srm1, c1, c2, sigma} of stedm_ddpm_step, from the fp32 buffers (numpy or CPU tensors). sigma_t =
+    nonzero(t) exp(0.5 logvar_clipped[t]) is evaluated with torch's fp32 exp on the CPU, the expression of p_sample (ddpm.py:1100-1110),
+    so that sigma_t * noise rounds as the reference's `nonzero_mask * (0.5 * model_log_variance).exp() * noise`; sigma_0 = 0."""
+    import torch
+    as32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32))
+    lv = as32(log_var_clipped)
+    sigma = (0.5 * lv).exp()
+    sigma[0] = 0.0
+    cols = [as32(sqrt_recip), as32(sqrt_recipm1), as32(coef1), as32(coef2), sigma]
+    return torch.stack(cols, dim=1).numpy().astype(np.float32)
