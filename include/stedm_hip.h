@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 16
+#define STEDM_ABI_VERSION 17
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -359,6 +359,22 @@ int stedm_attn_legacy16(const void* qkv, int qkv_is16, void* out16, int B, int T
 int stedm_ddim_step(const float* x, const float* e_c, const float* e_u, const float* noise,
                     const float* coefs, const int32_t* step_idx, float cfg_scale, float rescale_phi,
                     float* x_prev, float* pred_x0, int B, int C, int H, int W, void* stream);
+/* The same update with the reference's temperature and noise dropout and a noise drawn in the kernel (ABI 17; ddim.py:201-210). The CFG
+ * combine, the rescale and x0 / dir are stedm_ddim_step's. The noise term, each product rounded on its own in the reference's order:
+ *   noise = ((sigma_t z) temperature) keep / (1 - p);   x_prev = (sqrt(a_prev) x0 + dir) + noise
+ * z: noise [B][C][H][W] (given), or with draw != 0 element e of row first_id + b of stedm_philox_normal with (seed, stream 1 + iteration),
+ * iteration = n_iters - 1 - *step_idx (the stream predict_latents_sharded gives iteration i's noise); neither: no noise term.
+ * noise_dropout p in [0, 1): element e (index in its sample's row) of sample first_id + b is kept iff u16 >= lrint(p * 65536),
+ * u16 = 16-bit field (e & 7) - half (j & 1) of output word j >> 1 - of Philox4x32-10(counter {e >> 3, 0x20000 + iteration, 0x44524F50, 0},
+ * key {seed (low 32 bits), first_id + b}); kept values are scaled by (float)(1 / (1 - p)) (the train-mode dropout convention above)
+ * whenever p > 0, also below p = 2^-17, where the threshold rounds to 0 and every element is kept.
+ * draw and the dropout need step_idx and n_iters > 0. With temperature 1, p = 0 and no eps_out / noise_out the result equals
+ * stedm_ddim_step fed the same z, bit for bit (both compute sqrt(a_prev) x0 + dir with each product rounded, then fma(sigma, z, .)). eps_out (may be NULL, may alias e_c): the guided eps after the rescale (ddim.py:184).
+ * noise_out (may be NULL): the noise term above, what stedm_ddim_quantize_x0 adds. */
+int stedm_ddim_step_ex(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs, const int32_t* step_idx,
+                       int n_iters, float cfg_scale, float rescale_phi, int draw, float temperature, float noise_dropout, long first_id,
+                       unsigned long long seed, float* x_prev, float* pred_x0, float* eps_out, float* noise_out, int B, int C, int H, int W,
+                       void* stream);
 /* *step_idx += delta (device-side loop counter for graph replay). */
 int stedm_step_advance(int32_t* step_idx, int delta, void* stream);
 /* t_buf[0..B) = ts_table[*step_idx] : ts = torch.full((b,), step) of ddim.py:141, device-side so that one
@@ -673,6 +689,12 @@ int stedm_ema_update(const void* table, const int* chunk_tensor, const long* chu
  * [B][e_dim][HW], codebook [n_e][e_dim] -> idx[B*HW] = argmin_n (|z|^2 + |e_n|^2 - 2 z.e_n) (fp32, no FMA contraction, sums left to
  * right, first index on ties: an integer result) and zq NCHW = z + (e_idx - z) (the straight-through form's forward value). */
 int stedm_vq_nearest(const float* z, const float* codebook, int n_e, int e_dim, int B, long HW, long long* idx, float* zq, void* stream);
+/* quantize_x0 of a DDIM step (ddim.py:201-203, ABI 17), after stedm_ddim_step_ex: pred_x0 NCHW [B][e_dim][HW] is replaced in place by
+ * z + (e_idx - z) with idx the index stedm_vq_nearest gives (same arithmetic: bit for bit), then x_prev = (sqrt(a_prev) pred_x0 + dir eps)
+ * + noise with row *step_idx of the DDIM table of stedm_ddim_step (step_idx NULL: row 0). eps: the guided eps (stedm_ddim_step_ex's eps_out);
+ * noise: its noise_out, or NULL (no noise term). idx (may be NULL): int64 [B * HW]. e_dim in 1..8. */
+int stedm_ddim_quantize_x0(float* pred_x0, const float* eps, const float* noise, const float* coefs, const int32_t* step_idx,
+                           const float* codebook, int n_e, int e_dim, int B, long HW, float* x_prev, long long* idx, void* stream);
 /* quant_conv / post_quant_conv (autoencoder.py:42-43, 268, 280): 1x1 conv over a few channels (cin, cout <= 16), NCHW -> NCHW,
  * w [cout][cin], bias [cout] or NULL. */
 int stedm_conv1x1_nchw(const float* x, const float* w, const float* bias, float* out, int B, int cin, int cout, long HW, void* stream);

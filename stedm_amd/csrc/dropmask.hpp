@@ -64,4 +64,20 @@ __device__ __forceinline__ void philox_normal4(uint32_t g, uint32_t stream, uint
   z[2] = rb * __cosf(6.283185307179586f * u3); z[3] = rb * __sinf(6.283185307179586f * u3);
 }
 
+// element e of a sample's row of stedm_philox_normal (the value philox_normal4 gives it in its group of four)
+__device__ __forceinline__ float philox_normal1(uint32_t e, uint32_t stream, uint32_t seed, uint32_t sid) {
+  float z[4];
+  philox_normal4(e >> 2, stream, seed, sid, z);
+  const uint32_t j = e & 3u;
+  return j == 0 ? z[0] : j == 1 ? z[1] : j == 2 ? z[2] : z[3];
+}
+
+// DDIM noise dropout (stedm_ddim_step_ex, include/stedm_hip.h): the 16-bit uniform of element e of sample `sid`'s row at iteration `iter` =
+// field (e & 7) of Philox4x32-10(counter {e >> 3, 0x20000 + iter, 0x44524F50, 0}, key {seed, sid}); the element is kept iff u16 >= thr16.
+constexpr uint32_t DDIM_DROP_WORD = 0x44524F50u;      // "DROP"
+__device__ __forceinline__ bool ddim_drop_keep(uint32_t e, uint32_t iter, uint32_t seed, uint32_t sid, uint32_t thr16) {
+  const U4 r = philox4x32_10(U4{e >> 3, 0x20000u + iter, DDIM_DROP_WORD, 0u}, seed, sid);
+  return drop_u16(r, (int)(e & 7u)) >= thr16;
+}
+
 }  // namespace stedm

@@ -729,12 +729,60 @@ extern "C" int stedm_emb_proj(const float* emb, const float* wt, const float* bi
 
 // ------------------------------------------------------------------------------------------------
 // DDIM update + rescaled CFG. One block per sample; thread = (w, part) with part striding (c,h).
+// Template flags (stedm_ddim_step runs <false, false>; stedm_ddim_step_ex picks the others):
+//   DRAW  the step noise z of element e of sample b is drawn here: row first_id + b of stedm_philox_normal, stream 1 + iteration
+//         (iteration = n_iters - 1 - *step_idx), instead of being read from `noise`;
+//   EXT   the reference's temperature and noise dropout (ddim.py:206-208, each product rounded on its own: ((sigma z) T) keep / (1 - p)),
+//         then x_prev = (sqrt(a_prev) x0 + dir) + noise; optional outputs of the guided eps and of that noise term.
 // ------------------------------------------------------------------------------------------------
+struct DdimEx {
+  float* eps_out;            // guided eps after the rescale (ddim.py:184); may alias e_c element for element
+  float* noise_out;          // the noise term that was added (EXT only)
+  float temperature, drop_scale;
+  uint32_t thr16, seed, id0;
+  int n_iters;
+  int drop;                  // noise_dropout > 0 (thr16 may still be 0 for p < 2^-17: then every element is kept, and scaled)
+};
+
+// sqrt(a_prev) x0 + dir e as stedm_ddim_step has always computed it (both products rounded, then the sum; the compiler issued the two
+// products as one packed multiply). Spelled out so that no form of either kernel, and no later compiler, contracts it into an FMA.
+__device__ __forceinline__ float ddim_base_rounded(float sqrt_ap, float x0, float dir_c, float e) {
+#pragma clang fp contract(off)
+  return sqrt_ap * x0 + dir_c * e;
+}
+
+__device__ __forceinline__ float ddim_shaped_noise(float xp, float sigma, float z, float temperature, float keep_scale) {
+#pragma clang fp contract(off)       // every product and sum rounded on its own, as torch does (ddim.py:206-210)
+  return xp + ((sigma * z) * temperature) * keep_scale;
+}
+
+// x_prev of element o (element e of sample b's row) from xp = sqrt(a_prev) x0 + dir; the noise, temperature and dropout of DRAW / EXT
+template <bool DRAW, bool EXT>
+__device__ __forceinline__ float ddim_add_noise(float xp, float sigma, const float* noise, float nzv, long o, int e, int b, float eg,
+                                                const DdimEx& ex, int idx) {
+  if constexpr (EXT) {
+    if (ex.eps_out) ex.eps_out[o] = eg;
+  }
+  if (!(DRAW || noise)) return xp;
+  const uint32_t iter = (uint32_t)(ex.n_iters - 1 - idx), sid = ex.id0 + (uint32_t)b;
+  float z = nzv;
+  if constexpr (DRAW) z = philox_normal1((uint32_t)e, 1u + iter, ex.seed, sid);
+  if constexpr (!EXT) {
+    return __builtin_fmaf(sigma, z, xp);      // what both forms of stedm_ddim_step compile `xp += sigma * noise` to
+  } else {
+    const float ks = !ex.drop ? 1.0f : ddim_drop_keep((uint32_t)e, iter, ex.seed, sid, ex.thr16) ? ex.drop_scale : 0.0f;
+    const float out = ddim_shaped_noise(xp, sigma, z, ex.temperature, ks);
+    if (ex.noise_out) ex.noise_out[o] = ddim_shaped_noise(0.0f, sigma, z, ex.temperature, ks);
+    return out;
+  }
+}
+
+template <bool DRAW, bool EXT>
 __global__ void __launch_bounds__(256) ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ e_c,
                                                         const float* __restrict__ e_u, const float* __restrict__ noise,
                                                         const float* __restrict__ coefs, const int32_t* __restrict__ step_idx,
                                                         float s, float phi, float* __restrict__ x_prev,
-                                                        float* __restrict__ pred_x0, int C, int H, int W) {
+                                                        float* __restrict__ pred_x0, int C, int H, int W, DdimEx ex) {
   __shared__ float red[2][256];
   __shared__ float ratio_w[256];
   const int b = blockIdx.x;
@@ -801,8 +849,8 @@ __global__ void __launch_bounds__(256) ddim_step_kernel(const float* __restrict_
         e = (ew * ratio_w[w]) * phi + (1.0f - phi) * e;
       }
       const float x0 = (x[o] - sq1m * e) / sqrt_at;
-      float xp = sqrt_ap * x0 + dir_c * e;
-      if (noise) xp += sigma * noise[o];
+      float xp = ddim_base_rounded(sqrt_ap, x0, dir_c, e);
+      xp = ddim_add_noise<DRAW, EXT>(xp, sigma, noise, (!DRAW && noise) ? noise[o] : 0.0f, o, r * W + w, b, e, ex, idx);
       x_prev[o] = xp;
       if (pred_x0) pred_x0[o] = x0;
     }
@@ -811,11 +859,11 @@ __global__ void __launch_bounds__(256) ddim_step_kernel(const float* __restrict_
 // The same update with a thread's R = C H / (256 / W) elements of every operand held in registers: one round of independent loads instead of
 // three dependent passes over e_c / e_u (the kernel above is one block per sample, i.e. 64 busy CUs at the bench batch: all latency, 24 us per
 // step). Same operations in the same order as above (the sums run over r = part, part + parts, ...), so the results are the same bits.
-template <int R>
+template <int R, bool DRAW, bool EXT>
 __global__ void __launch_bounds__(256) ddim_step_reg_kernel(const float* __restrict__ x, const float* __restrict__ e_c, const float* __restrict__ e_u,
                                                             const float* __restrict__ noise, const float* __restrict__ coefs,
                                                             const int32_t* __restrict__ step_idx, float s, float phi, float* __restrict__ x_prev,
-                                                            float* __restrict__ pred_x0, int C, int H, int W) {
+                                                            float* __restrict__ pred_x0, int C, int H, int W, DdimEx ex) {
   __shared__ float red[2][256];
   __shared__ float ratio_w[256];
   const int b = blockIdx.x;
@@ -834,7 +882,7 @@ __global__ void __launch_bounds__(256) ddim_step_reg_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < R; ++j) eu[j] = e_u[base + (long)(part + j * parts) * W + w];
   }
-  if (noise) {
+  if (!DRAW && noise) {
 #pragma unroll
     for (int j = 0; j < R; ++j) nz[j] = noise[base + (long)(part + j * parts) * W + w];
   }
@@ -888,11 +936,25 @@ __global__ void __launch_bounds__(256) ddim_step_reg_kernel(const float* __restr
       e = (ew * ratio_w[w]) * phi + (1.0f - phi) * e;
     }
     const float x0 = (xv[j] - sq1m * e) / sqrt_at;
-    float xp = sqrt_ap * x0 + dir_c * e;
-    if (noise) xp += sigma * nz[j];
+    float xp = ddim_base_rounded(sqrt_ap, x0, dir_c, e);
+    xp = ddim_add_noise<DRAW, EXT>(xp, sigma, noise, (!DRAW && noise) ? nz[j] : 0.0f, o, (part + j * parts) * W + w, b, e, ex, idx);
     x_prev[o] = xp;
     if (pred_x0) pred_x0[o] = x0;
   }
+}
+
+template <bool DRAW, bool EXT>
+static void launch_ddim_step(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs, const int32_t* step_idx,
+                             float s, float phi, float* x_prev, float* pred_x0, int B, int C, int H, int W, const DdimEx& ex, hipStream_t st) {
+  const int parts = 256 / W;
+  const bool reg = 256 % W == 0 && (C * H) % parts == 0;
+  const int per = reg ? C * H / parts : 0;
+#define DDIM_REG(RR) ddim_step_reg_kernel<RR, DRAW, EXT><<<B, 256, 0, st>>>(x, e_c, e_u, noise, coefs, step_idx, s, phi, x_prev, pred_x0, C, H, W, ex)
+  if (per == 16) DDIM_REG(16);          // 32 x 32 x 4 latents (the bench's)
+  else if (per == 4) DDIM_REG(4);       // 16 x 16 x 4
+  else if (per == 8) DDIM_REG(8);
+  else ddim_step_kernel<DRAW, EXT><<<B, 256, 0, st>>>(x, e_c, e_u, noise, coefs, step_idx, s, phi, x_prev, pred_x0, C, H, W, ex);
+#undef DDIM_REG
 }
 
 extern "C" int stedm_ddim_step(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
@@ -901,17 +963,34 @@ extern "C" int stedm_ddim_step(const float* x, const float* e_c, const float* e_
   STEDM_CHECK_ARG(x && e_c && coefs && x_prev, "ddim_step: null pointer");
   STEDM_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && W <= 256, "ddim_step: bad shape B=%d C=%d H=%d W=%d (W <= 256)", B, C, H, W);
   STEDM_CHECK_ARG(!e_u || C * H > 1, "ddim_step: std over (C,H) needs C*H > 1");
-  const int parts = 256 / W;
-  const bool reg = 256 % W == 0 && (C * H) % parts == 0;
-  const int per = reg ? C * H / parts : 0;
-#define DDIM_REG(RR) ddim_step_reg_kernel<RR><<<B, 256, 0, as_stream(stream)>>>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, C, H, W)
-  if (per == 16) DDIM_REG(16);          // 32 x 32 x 4 latents (the bench's)
-  else if (per == 4) DDIM_REG(4);       // 16 x 16 x 4
-  else if (per == 8) DDIM_REG(8);
-  else
-    ddim_step_kernel<<<B, 256, 0, as_stream(stream)>>>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev,
-                                                       pred_x0, C, H, W);
-#undef DDIM_REG
+  launch_ddim_step<false, false>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, DdimEx{},
+                                 as_stream(stream));
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int stedm_ddim_step_ex(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
+                                  const int32_t* step_idx, int n_iters, float cfg_scale, float rescale_phi, int draw, float temperature,
+                                  float noise_dropout, long first_id, unsigned long long seed, float* x_prev, float* pred_x0, float* eps_out,
+                                  float* noise_out, int B, int C, int H, int W, void* stream) {
+  STEDM_CHECK_ARG(x && e_c && coefs && x_prev, "ddim_step_ex: null pointer");
+  STEDM_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && H > 0 && W > 0 && W <= 256, "ddim_step_ex: bad shape B=%d C=%d H=%d W=%d (W <= 256)", B, C, H, W);
+  STEDM_CHECK_ARG(!e_u || C * H > 1, "ddim_step_ex: std over (C,H) needs C*H > 1");
+  STEDM_CHECK_ARG(!(draw && noise), "ddim_step_ex: a given noise tensor and the in-kernel draw exclude each other");
+  STEDM_CHECK_ARG(noise_dropout >= 0.0f && noise_dropout < 1.0f, "ddim_step_ex: noise_dropout %g outside [0, 1)", (double)noise_dropout);
+  const unsigned thr = (unsigned)lrint((double)noise_dropout * 65536.0);
+  const bool drop = noise_dropout > 0.0f;
+  STEDM_CHECK_ARG(!((draw || drop) && !step_idx), "ddim_step_ex: the in-kernel draw and the dropout need the device step index");
+  STEDM_CHECK_ARG(!((draw || drop) && n_iters <= 0), "ddim_step_ex: the in-kernel draw and the dropout need n_iters > 0 (got %d)", n_iters);
+  STEDM_CHECK_ARG(first_id >= 0 && first_id + B <= (1L << 32), "ddim_step_ex: sample ids %ld + %d outside [0, 2^32]", first_id, B);
+  DdimEx ex{eps_out, noise_out, temperature, (float)(1.0 / (1.0 - (double)noise_dropout)), thr, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)first_id, n_iters,
+           drop ? 1 : 0};
+  const bool ext = temperature != 1.0f || drop || eps_out || noise_out;
+  hipStream_t st = as_stream(stream);
+  if (draw && ext) launch_ddim_step<true, true>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, ex, st);
+  else if (draw) launch_ddim_step<true, false>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, ex, st);
+  else if (ext) launch_ddim_step<false, true>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, ex, st);
+  else launch_ddim_step<false, false>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, ex, st);
   STEDM_LAUNCH_CHECK();
   return 0;
 }

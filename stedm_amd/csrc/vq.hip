@@ -2,6 +2,8 @@
 //   vq_nearest       taming VectorQuantizer2.forward as VQModelInterface.decode calls it (ldm/models/autoencoder.py:274-282): nearest codebook
 //                    entry per latent pixel (integer result: index of the minimum of |z|^2 + |e|^2 - 2 z.e, first index on ties) and
 //                    the straight-through output z + (e - z)
+//   ddim_quantize_x0 p_sample_ddim's quantize_denoised (ldm/models/diffusion/ddim.py:201-203) inside a DDIM step: pred_x0 snapped to the
+//                    codebook with vq_nearest's arithmetic, x_prev recomputed from it
 //   conv1x1_nchw     quant_conv / post_quant_conv (autoencoder.py:42-43): 1x1 convolutions over a handful of channels, NCHW
 //   softmax_rows16   the softmax of AttnBlock (ldm/modules/diffusionmodules/model.py:143-199: single head of width C, logits scaled by
 //                    C^-0.5) written as 16-bit operand planes for the P @ V GEMM
@@ -14,29 +16,38 @@ namespace {
 
 constexpr int VQ_MAXE = 8;       // embedding width (3 in conf/diffusion/first_stage_config/vq-f4.yaml; 4 for the 4-channel synthetic latents)
 
-// codebook [n_e][e] fp32, z NCHW [B][e][HW]. One thread per latent pixel; the codebook walks through LDS in tiles of 1024 entries
-// (+ the squared norm).
-template <int E>
-__global__ void __launch_bounds__(256) vq_nearest_kernel(const float* __restrict__ z, const float* __restrict__ cb, int n_e, long npix, long HW,
-                                                         long long* __restrict__ idx_out, float* __restrict__ zq) {
+__device__ __forceinline__ float vq_straight_through(float z, float e) {
 #pragma clang fp contract(off)
-  constexpr int TILE = 1024;
-  __shared__ float scb[TILE][E + 1];
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  const bool live = p < npix;
-  const long b = live ? p / HW : 0, hw = live ? p - b * HW : 0;
-  float zv[E];
+  return z + (e - z);
+}
+__device__ __forceinline__ float vq_add_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+// sqrt(a_prev) x0 + dir e with both products rounded, then the sum: the update kernel's form (ddim_base_rounded in misc.hip)
+__device__ __forceinline__ float vq_ddim_base(float sqrt_ap, float x0, float dir_c, float e) {
+#pragma clang fp contract(off)
+  return sqrt_ap * x0 + dir_c * e;
+}
+
+constexpr int VQ_TILE = 1024;   // codebook entries staged in LDS at a time (+ their squared norms)
+
+// The nearest codebook entry of the pixel zv (argmin of |z|^2 + |e|^2 - 2 z.e, first index on ties), codebook [n_e][E] fp32 walked through
+// LDS (scb) in tiles of VQ_TILE entries. Every thread of the block must call it (it synchronises); `live` false: the thread only helps to
+// stage the tiles (returns -1). Shared by stedm_vq_nearest and stedm_ddim_quantize_x0, so their indices are the same bits.
+template <int E>
+__device__ __forceinline__ int vq_nearest_index(const float (&zv)[E], bool live, const float* __restrict__ cb, int n_e, float (*scb)[E + 1]) {
+#pragma clang fp contract(off)
   float zz = 0.f;
 #pragma unroll
   for (int c = 0; c < E; ++c) {
-    zv[c] = live ? z[(b * E + c) * HW + hw] : 0.f;
     const float sq = zv[c] * zv[c];
     zz = c == 0 ? sq : zz + sq;                      // torch.sum(z**2, dim=1): left-to-right fp32 sum
   }
   float best = 0.f;
   int bi = -1;
-  for (int t0 = 0; t0 < n_e; t0 += TILE) {
-    const int nt = min(TILE, n_e - t0);
+  for (int t0 = 0; t0 < n_e; t0 += VQ_TILE) {
+    const int nt = min(VQ_TILE, n_e - t0);
     __syncthreads();
     for (int i = threadIdx.x; i < nt; i += 256) {
       float ee = 0.f;
@@ -63,6 +74,22 @@ __global__ void __launch_bounds__(256) vq_nearest_kernel(const float* __restrict
       }
     }
   }
+  return bi;
+}
+
+// codebook [n_e][e] fp32, z NCHW [B][e][HW]. One thread per latent pixel.
+template <int E>
+__global__ void __launch_bounds__(256) vq_nearest_kernel(const float* __restrict__ z, const float* __restrict__ cb, int n_e, long npix, long HW,
+                                                         long long* __restrict__ idx_out, float* __restrict__ zq) {
+#pragma clang fp contract(off)
+  __shared__ float scb[VQ_TILE][E + 1];
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  const bool live = p < npix;
+  const long b = live ? p / HW : 0, hw = live ? p - b * HW : 0;
+  float zv[E];
+#pragma unroll
+  for (int c = 0; c < E; ++c) zv[c] = live ? z[(b * E + c) * HW + hw] : 0.f;
+  const int bi = vq_nearest_index<E>(zv, live, cb, n_e, scb);
   if (!live) return;
   idx_out[p] = bi;
 #pragma unroll
@@ -71,6 +98,39 @@ __global__ void __launch_bounds__(256) vq_nearest_kernel(const float* __restrict
     zq[(b * E + c) * HW + hw] = zv[c] + (e - zv[c]);    // z + (z_q - z).detach(): the straight-through form's forward value
   }
 }
+
+// quantize_x0 of p_sample_ddim (ddim.py:201-203) after the update kernel (stedm_ddim_step_ex): per latent pixel, pred_x0 -> z + (e - z) of its
+// nearest entry (vq_nearest_index), then x_prev = (sqrt(a_prev) x0q + dir eps) + noise, the scalars of row *step_idx of the DDIM table computed
+// with ddim_step_kernel's expressions. One thread per pixel over the whole batch.
+template <int E>
+__global__ void __launch_bounds__(256) ddim_quantize_kernel(float* __restrict__ pred_x0, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                            const float* __restrict__ coefs, const int32_t* __restrict__ step_idx,
+                                                            const float* __restrict__ cb, int n_e, long npix, long HW, float* __restrict__ x_prev,
+                                                            long long* __restrict__ idx_out) {
+  __shared__ float scb[VQ_TILE][E + 1];
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  const bool live = p < npix;
+  const long b = live ? p / HW : 0, hw = live ? p - b * HW : 0;
+  float zv[E];
+#pragma unroll
+  for (int c = 0; c < E; ++c) zv[c] = live ? pred_x0[(b * E + c) * HW + hw] : 0.f;
+  const int bi = vq_nearest_index<E>(zv, live, cb, n_e, scb);
+  if (!live) return;
+  if (idx_out) idx_out[p] = bi;
+  const int idx = step_idx ? *step_idx : 0;
+  const float a_prev = coefs[idx * 4 + 1], sigma = coefs[idx * 4 + 2];
+  const float dir_c = sqrtf(1.0f - a_prev - sigma * sigma);
+  const float sqrt_ap = sqrtf(a_prev);
+#pragma unroll
+  for (int c = 0; c < E; ++c) {
+    const long o = (b * E + c) * HW + hw;
+    const float q = vq_straight_through(zv[c], cb[(long)bi * E + c]);
+    pred_x0[o] = q;
+    const float xp = vq_ddim_base(sqrt_ap, q, dir_c, eps[o]);
+    x_prev[o] = noise ? vq_add_rounded(xp, noise[o]) : xp;
+  }
+}
+
 // out[b][co][p] = bias[co] + sum_ci w[co][ci] * x[b][ci][p]; cin, cout <= 16
 __global__ void __launch_bounds__(256) conv1x1_nchw_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                            float* __restrict__ out, int cin, int cout, long HW, long npix) {
@@ -124,6 +184,22 @@ extern "C" int stedm_vq_nearest(const float* z, const float* codebook, int n_e, 
   hipStream_t st = as_stream(stream);
   switch (e_dim) {
 #define CASE(E) case E: vq_nearest_kernel<E><<<grid, 256, 0, st>>>(z, codebook, n_e, npix, HW, idx, zq); break;
+    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+  }
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int stedm_ddim_quantize_x0(float* pred_x0, const float* eps, const float* noise, const float* coefs, const int32_t* step_idx,
+                                      const float* codebook, int n_e, int e_dim, int B, long HW, float* x_prev, long long* idx, void* stream) {
+  STEDM_CHECK_ARG(pred_x0 && eps && coefs && codebook && x_prev && n_e > 0 && B > 0 && HW > 0, "ddim_quantize_x0: bad args");
+  STEDM_CHECK_ARG(e_dim >= 1 && e_dim <= VQ_MAXE, "ddim_quantize_x0: embedding width %d unsupported (1..%d)", e_dim, VQ_MAXE);
+  const long npix = (long)B * HW;
+  const int grid = (int)((npix + 255) / 256);
+  hipStream_t st = as_stream(stream);
+  switch (e_dim) {
+#define CASE(E) case E: ddim_quantize_kernel<E><<<grid, 256, 0, st>>>(pred_x0, eps, noise, coefs, step_idx, codebook, n_e, npix, HW, x_prev, idx); break;
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
   }

@@ -11,7 +11,9 @@ operation of the loop body runs in HIP kernels:
   * masked sampling, ddim.py:143-146 (q_sample of x0 blended into img before the U-Net call) -> one kernel
     (stedm_ddim_mask_blend) whose noise is drawn in it from the device step index, so it is captured with the step;
   * with `use_graph=True` the whole step (timestep fill, U-Net, update, counter decrement) is captured
-    once in a hipGraph and replayed per step, per-step scalars coming from a device table.
+    once in a hipGraph and replayed per step, per-step scalars coming from a device table;
+  * temperature / noise_dropout (ddim.py:206-208) and the step noise drawn from (noise_seed, sample id) -> stedm_ddim_step_ex, the same
+    kernel with compile-time options; quantize_x0 (ddim.py:201-203) -> one more kernel after it (stedm_ddim_quantize_x0).
 """
 from __future__ import annotations
 
@@ -22,6 +24,15 @@ import torch
 
 from . import ops
 from .schedule import DDIMTables, make_ddim_tables
+
+
+class _StepOpts:
+    """What stedm_ddim_step_ex needs beyond stedm_ddim_step: iterations of the run, temperature, noise dropout, the in-kernel draw, the
+    seed of the draw and of the keep bits, the first global sample id, the codebook of quantize_x0 (or None)."""
+
+    def __init__(self, n_iters, temperature, noise_dropout, draw, seed, first_id, codebook):
+        self.n_iters, self.temperature, self.noise_dropout, self.draw = n_iters, temperature, noise_dropout, draw
+        self.seed, self.first_id, self.codebook = seed, first_id, codebook
 
 
 class DDIMSampler(object):
@@ -68,19 +79,55 @@ class DDIMSampler(object):
         [B, C, H, W] (a batch-1 x0 is refused: the reference's one batch-shaped noise draw shared by every sample cannot be reproduced by
         per-sample streams); mask is [B|1, 1|C, H, W]. Repo-specific keywords: `mask_noises` (one N(0,1) tensor per iteration in place
         of q_sample's draw; eager loop), else the draw is made in the kernel from `mask_seed` (default: one draw from torch's CPU
-        generator per call) and the global sample id `sample_id0 + b` (ops.ddim_mask_blend)."""
-        if quantize_x0 or score_corrector is not None or noise_dropout > 0. or temperature != 1.:
-            raise NotImplementedError("quantize_x0 / score_corrector / noise_dropout / temperature: "
-                                      "unused by the reference drivers (ldm_diffusion.py:82,90), not implemented")
+        generator per call) and the global sample id `sample_id0 + b` (ops.ddim_mask_blend).
+
+        temperature / noise_dropout (ddim.py:206-208): noise = ((sigma_t z) temperature), then dropout with keep bits drawn in the kernel
+        (include/stedm_hip.h, stedm_ddim_step_ex; torch's F.dropout stream cannot be reproduced, its rule and scale are kept). quantize_x0
+        (ddim.py:202-203): pred_x0 snapped to the first stage's codebook every step (needs first_stage_model.quantize.embedding, width C).
+        With eta == 0 the noise term is zero, so temperature and noise_dropout change nothing. `noise_seed` (repo-specific, the ancestral
+        sampler's name): the step noise of eta > 0 is drawn in the kernel as row sample_id0 + b of ops.philox_normal(noise_seed, stream
+        1 + iteration) - what predict_latents_sharded fed as `noises` - and the loop can be graphed; without it the step noise comes from
+        torch.randn per step (or `noises`) and the dropout bits from a seed drawn once per call from torch's CPU generator."""
+        if score_corrector is not None:
+            raise NotImplementedError("score_corrector: unused by the reference drivers (ldm_diffusion.py:82,90), not implemented")
+        if not 0.0 <= float(noise_dropout) < 1.0:
+            raise ValueError(f"noise_dropout {noise_dropout} outside [0, 1)")
+        codebook = self._codebook(shape[0]) if quantize_x0 else None
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
         masking = {}
         if mask is not None:
             masking = self._mask_args(size, mask, x0, kwargs.get("mask_noises"), kwargs.get("mask_seed"), kwargs.get("sample_id0", 0))
+        masking.setdefault("sample_id0", int(kwargs.get("sample_id0", 0)))
         return self.ddim_sampling(conditioning, size, callback=callback, img_callback=img_callback, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, noises=kwargs.get("noises"), **masking)
+                                  unconditional_conditioning=unconditional_conditioning, noises=kwargs.get("noises"),
+                                  quantize_denoised=quantize_x0, temperature=temperature, noise_dropout=noise_dropout,
+                                  noise_seed=kwargs.get("noise_seed"), _codebook=codebook, **masking)
+
+    def _codebook(self, C):
+        """The first stage's codebook [n_e, C] fp32 on the model's device, for quantize_x0 (raises before any device work)."""
+        emb = getattr(getattr(getattr(self.model, "first_stage_model", None), "quantize", None), "embedding", None)
+        if emb is None:
+            raise NotImplementedError("quantize_x0 needs a VQ first stage (first_stage_model.quantize.embedding)")
+        w = emb.weight
+        if w.dim() != 2 or int(w.shape[1]) != int(C):
+            raise ValueError(f"quantize_x0: codebook {tuple(w.shape)} has width {w.shape[-1]}, the latents have {C} channels")
+        return w.detach().to(self.model.device).float().contiguous()
+
+    def _step_opts(self, temperature, noise_dropout, codebook, noise_seed, draw_ok, sample_id0):
+        """The options of stedm_ddim_step_ex for this run, or None for stedm_ddim_step (the path and bits of a plain call)."""
+        if self._eta == 0.0:                         # sigma == 0: the noise term of ddim.py:206-208 is zero whatever its options
+            temperature, noise_dropout, noise_seed = 1.0, 0.0, None
+        draw = noise_seed is not None and draw_ok
+        if temperature == 1.0 and noise_dropout == 0.0 and codebook is None and not draw:
+            return None
+        seed = noise_seed
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if noise_dropout > 0.0 else 0
+        return _StepOpts(int(self.ddim_timesteps.shape[0]), float(temperature), float(noise_dropout), draw, int(seed), int(sample_id0),
+                         codebook)
 
     def _mask_args(self, size, mask, x0, mask_noises, mask_seed, sample_id0):
         """Checks and device placement of the masked-sampling inputs (see `sample`)."""
@@ -113,12 +160,16 @@ class DDIMSampler(object):
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, noises=None, mask=None, x0=None,
-                      mask_noises=None, mask_seed=None, sample_id0=0, **kwargs):
+                      mask_noises=None, mask_seed=None, sample_id0=0, quantize_denoised=False, temperature=1., noise_dropout=0.,
+                      noise_seed=None, _codebook=None, **kwargs):
         """ddim.py:113-162. `noises` (optional list, one N(0,1) tensor per iteration) replaces the global-RNG
         draw of ddim.py:206 so that runs are reproducible across devices and shard counts. mask / x0 / mask_noises / mask_seed /
-        sample_id0: masked sampling, checked and placed by `sample` (the blend runs before the U-Net call; x_inter logs unblended img)."""
+        sample_id0: masked sampling, checked and placed by `sample` (the blend runs before the U-Net call; x_inter logs unblended img).
+        quantize_denoised / temperature / noise_dropout / noise_seed: see `sample`."""
         device = self.model.device
         b = shape[0]
+        if quantize_denoised and _codebook is None:
+            _codebook = self._codebook(shape[1])
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().clone()
         timesteps = self.ddim_timesteps
         total_steps = timesteps.shape[0]
@@ -127,11 +178,13 @@ class DDIMSampler(object):
         need_inter = lambda index: index % log_every_t == 0 or index == total_steps - 1
 
         blend = None if mask is None else (mask, x0, mask_seed, int(sample_id0))
+        opts = self._step_opts(temperature, noise_dropout, _codebook if quantize_denoised else None, noise_seed, noises is None,
+                               sample_id0)
 
-        if self.use_graph and callback is None and img_callback is None and self._eta == 0.0 \
-                and hasattr(self.model, "apply_model_cfg") and mask_noises is None:
+        if self.use_graph and callback is None and img_callback is None and hasattr(self.model, "apply_model_cfg") \
+                and mask_noises is None and (self._eta == 0.0 or (opts is not None and opts.draw)):
             out = self._sample_graph(img, cond, unconditional_conditioning, unconditional_guidance_scale, cfg,
-                                     total_steps, log_every_t, intermediates, blend)
+                                     total_steps, log_every_t, intermediates, blend, opts)
             ops.f16_guard_check("the DDIM sampling loop")       # fp16 modes: raise rather than return samples computed through an inf
             return out
 
@@ -145,11 +198,11 @@ class DDIMSampler(object):
             nz = None
             if noises is not None:
                 nz = noises[i].to(device).float().contiguous()
-            elif self._eta != 0.0:
+            elif self._eta != 0.0 and not (opts is not None and opts.draw):
                 nz = torch.randn(shape, device=device)     # ddim.py:206 (when sigma == 0 the draw cannot change x)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning, _noise=nz, _out=(img, pred_x0),
-                                              _uniform_t=True)
+                                              _uniform_t=True, _opts=opts)
             if callback:
                 callback(i)
             if img_callback:
@@ -164,10 +217,15 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, rescale_phi=0.7,
-                      _noise: Optional[torch.Tensor] = None, _out=None, _uniform_t: bool = False):
-        """ddim.py:164-210. Returns (x_prev, pred_x0)."""
-        if use_original_steps or quantize_denoised or score_corrector is not None or repeat_noise:
-            raise NotImplementedError("use_original_steps / quantize_denoised / score_corrector / repeat_noise not implemented")
+                      _noise: Optional[torch.Tensor] = None, _out=None, _uniform_t: bool = False, _opts=None):
+        """ddim.py:164-210. Returns (x_prev, pred_x0). The step noise is `_noise` (None: no noise term); temperature, noise_dropout
+        (keep bits from a seed drawn per call) and quantize_denoised as in `sample`. _opts: the loop's options (they take precedence)."""
+        if use_original_steps or score_corrector is not None or repeat_noise:
+            raise NotImplementedError("use_original_steps / score_corrector / repeat_noise not implemented")
+        if _opts is None and (quantize_denoised or temperature != 1. or noise_dropout != 0.):
+            if not 0.0 <= float(noise_dropout) < 1.0:
+                raise ValueError(f"noise_dropout {noise_dropout} outside [0, 1)")
+            _opts = self._step_opts(temperature, noise_dropout, self._codebook(x.shape[1]) if quantize_denoised else None, None, False, 0)
         x = x.float().contiguous()
         e_u = None
         ours = hasattr(self.model, "apply_model_cfg")
@@ -181,14 +239,33 @@ class DDIMSampler(object):
             e_u = self.model.apply_model(x, t, unconditional_conditioning)
         x_prev, pred_x0 = _out if _out is not None else (torch.empty_like(x), torch.empty_like(x))
         step = self._idx_all[index:index + 1]   # device-resident loop index (no H2D copy per step)
-        ops.ddim_step(x, e_c.contiguous(), None if e_u is None else e_u.contiguous(), self._coefs, x_prev, pred_x0=pred_x0,
-                      noise=_noise, step_idx=step, cfg_scale=float(unconditional_guidance_scale), rescale_phi=float(rescale_phi))
+        self._update(x, e_c.contiguous(), None if e_u is None else e_u.contiguous(), x_prev, pred_x0, step,
+                     float(unconditional_guidance_scale), float(rescale_phi), _noise, _opts)
         return x_prev, pred_x0
 
+    def _update(self, x, e_c, e_u, x_prev, pred_x0, step, scale, phi, noise=None, opts=None, noise_buf=None):
+        """ddim.py:179-210 after the model call: stedm_ddim_step, or with options stedm_ddim_step_ex (+ stedm_ddim_quantize_x0)."""
+        if opts is None:
+            ops.ddim_step(x, e_c, e_u, self._coefs, x_prev, pred_x0=pred_x0, noise=noise, step_idx=step, cfg_scale=scale, rescale_phi=phi)
+            return
+        quant = opts.codebook is not None
+        noisy = self._eta != 0.0 and (noise is not None or opts.draw)
+        nbuf = None
+        if quant and noisy:
+            nbuf = noise_buf if noise_buf is not None else torch.empty_like(x)
+        ops.ddim_step_ex(x, e_c, e_u, self._coefs, x_prev, pred_x0=pred_x0, noise=noise if self._eta != 0.0 else None,
+                         draw=opts.draw and self._eta != 0.0, step_idx=step, n_iters=opts.n_iters, cfg_scale=scale, rescale_phi=phi,
+                         temperature=opts.temperature, noise_dropout=opts.noise_dropout, seed=opts.seed, first_id=opts.first_id,
+                         eps_out=e_c if quant else None, noise_out=nbuf)
+        if quant:                                # ddim.py:202-203, then x_prev again from the quantized pred_x0 (ddim.py:205-209)
+            ops.ddim_quantize_x0(pred_x0, e_c, self._coefs, opts.codebook, x_prev, noise=nbuf, step_idx=step)
+
+
     # ------------------------------------------------------------------------------------------------ graph replay
-    def _sample_graph(self, img, cond, uncond, scale, cfg, total_steps, log_every_t, intermediates, blend=None):
-        """Only taken for eta == 0 (sigma == 0: the noise term of ddim.py:206 is identically zero)."""
-        sg = StepGraph(self, img, cond, uncond if cfg else None, scale, blend=blend)
+    def _sample_graph(self, img, cond, uncond, scale, cfg, total_steps, log_every_t, intermediates, blend=None, opts=None):
+        """Taken for eta == 0 (sigma == 0: the noise term of ddim.py:206 is identically zero) and for eta > 0 with the noise drawn in the
+        kernel from noise_seed (opts.draw)."""
+        sg = StepGraph(self, img, cond, uncond if cfg else None, scale, blend=blend, opts=opts)
 
         def log(index):
             if index % log_every_t == 0 or index == total_steps - 1:
@@ -210,13 +287,15 @@ class DDIMSampler(object):
 
 class StepGraph:
     """One denoising step = {t fill from the device table, [masked sampling: blend of q_sample(x0, t) into `img`, noise drawn in the
-    kernel from the device index], U-Net (shared-encoder CFG pass), fused DDIM/CFG update in place on `img`, device index decrement},
+    kernel from the device index], U-Net (shared-encoder CFG pass), fused DDIM/CFG update in place on `img` [with opts: stedm_ddim_step_ex,
+    its noise drawn in the kernel from the device index, then stedm_ddim_quantize_x0 for quantize_x0], device index decrement},
     capturable once in a hipGraph and replayed for every step. blend: None or (mask, x0, seed, first sample id)."""
 
-    def __init__(self, sampler: DDIMSampler, img: torch.Tensor, cond, uncond, scale: float, rescale_phi: float = 0.7, blend=None):
+    def __init__(self, sampler: DDIMSampler, img: torch.Tensor, cond, uncond, scale: float, rescale_phi: float = 0.7, blend=None, opts=None):
         self.s = sampler
         self.img = img
         self.blend = blend
+        self.opts = opts            # _StepOpts of stedm_ddim_step_ex (in-kernel noise, temperature, dropout, quantize_x0) or None
         self.cond, self.uncond, self.scale, self.phi = cond, uncond, float(scale), float(rescale_phi)
         dev = img.device
         b = img.shape[0]
@@ -225,6 +304,7 @@ class StepGraph:
         self.t_buf = torch.empty((b,), dtype=torch.int64, device=dev)
         self.pred_x0 = torch.empty_like(img)
         self.eps = torch.empty((2 * b if self.cfg else b,) + tuple(img.shape[1:]), dtype=torch.float32, device=dev)
+        self.noise_buf = torch.empty_like(img) if (opts is not None and opts.codebook is not None and opts.draw) else None
         self.graph = None
         self.side = None
 
@@ -241,8 +321,7 @@ class StepGraph:
             e_c, e_u = m.apply_model_cfg(self.img, self.t_buf, self.cond, self.uncond, out=self.eps, uniform_t=True)
         else:
             e_c, e_u = m.apply_model(self.img, self.t_buf, self.cond, out=self.eps, uniform_t=True), None
-        ops.ddim_step(self.img, e_c, e_u, s._coefs, self.img, pred_x0=self.pred_x0, step_idx=self.step,
-                      cfg_scale=self.scale, rescale_phi=self.phi)
+        s._update(self.img, e_c, e_u, self.img, self.pred_x0, self.step, self.scale, self.phi, opts=self.opts, noise_buf=self.noise_buf)
         ops.step_advance(self.step, -1)
 
     def stream_ctx(self):

@@ -743,7 +743,11 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
     blend's), and eta != 0 (ValueError, as the reference) and noises are refused. "ddpm" (the ancestral chain of sample_log(ddim=False),
     stedm_amd/ancestral.py): model.num_timesteps unguided steps, ddim_steps ignored; cfg_scale != 1 with style_sampling != "none" raises
     (the reference's ancestral path has no guidance), as does eta != 0. Its step noise is drawn from (noise_seed, sample_id0 + b);
-    `noises` (optional) holds one N(0,1) tensor per step."""
+    `noises` (optional) holds one N(0,1) tensor per step.
+
+    noise_seed with sampler="ddim" and eta != 0: every step's noise is drawn in the DDIM kernel as row sample_id0 + b of
+    ops.philox_normal(noise_seed, stream 1 + iteration) (DDIMSampler.sample), so the loop can be graphed; given `noises` take precedence.
+    Without it (or with eta == 0) the DDIM noise is torch's, as before."""
     if sampler not in ALL_SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}; choose from {ALL_SAMPLERS}")
     if sampler == ANCESTRAL and cfg_scale != 1 and style_sampling != "none":
@@ -769,6 +773,8 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
         return out
     if sampler != "ddim":
         kw["sampler"] = sampler
+    elif eta != 0.0 and noise_seed is not None:
+        kw.update(noise_seed=int(noise_seed), sample_id0=int(sample_id0))
     if cfg_scale == 1 or style_sampling == "none":
         out, _ = model.sample_log(c_0, batch_size=len(z), ddim=True, ddim_steps=ddim_steps, eta=eta, log_every_t=1000, **kw)
     else:
@@ -817,7 +823,7 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
     parallel.shard_range(global_batch, rank, world) of the global batch. Latents are independent, so nothing is exchanged inside the loop;
     the initial noise x_T (ddim.py:122) and, for eta > 0, every step's noise (ddim.py:206) come from per-SAMPLE streams keyed by the global
     sample id (parallel.per_sample_normal), so sample i is the same for every world size, which the reference's batch-shaped global-RNG
-    draw cannot give. gather: all-gather the shards (RCCL over xGMI with backend "nccl") -> [global_batch, C, H, W] on every rank.
+    draw cannot give. (On the GPU the step noise of eta > 0 is drawn inside the DDIM kernel from the same key and stream, 1 + iteration.) gather: all-gather the shards (RCCL over xGMI with backend "nccl") -> [global_batch, C, H, W] on every rank.
 
     mask / x0 (masked sampling, see predict_latents): given for the global batch (their rows lo:hi are taken), for the shard, or (mask
     only) as one row for every sample. The blend's noise is keyed by (seed, global sample id), like x_T.
@@ -843,7 +849,9 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
            (lambda st: par.per_sample_normal(seed, ids, shape, stream=st).to(dev))
     x_T = draw(0)
     noises = None
-    if eta != 0.0 and kw.get("sampler", "ddim") == "ddim":
+    if eta != 0.0 and kw.get("sampler", "ddim") == "ddim" and on_gpu:
+        kw.update(noise_seed=int(seed), sample_id0=lo)      # drawn in the DDIM kernel: the same rows draw(1 + i) gives, bit for bit
+    elif eta != 0.0 and kw.get("sampler", "ddim") == "ddim":
         from .schedule import make_ddim_timesteps
         n_iter = int(make_ddim_timesteps(int(ddim_steps), model.num_timesteps).shape[0])      # (S = 6 -> 7 iterations: ddim.py's uniform stride)
         noises = [draw(1 + i) for i in range(n_iter)]

@@ -966,6 +966,66 @@ def ddim_step(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], c
     return x_prev
 
 
+
+def ddim_step_ex(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], coefs: torch.Tensor, x_prev: torch.Tensor,
+                 pred_x0: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, draw: bool = False,
+                 step_idx: Optional[torch.Tensor] = None, n_iters: int = 0, cfg_scale: float = 1.0, rescale_phi: float = 0.7,
+                 temperature: float = 1.0, noise_dropout: float = 0.0, seed: int = 0, first_id: int = 0,
+                 eps_out: Optional[torch.Tensor] = None, noise_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ddim_step with the reference's temperature and noise dropout (stedm_ddim_step_ex): noise = ((sigma z) temperature) keep / (1 - p),
+    x_prev = (sqrt(a_prev) x0 + dir) + noise. z: `noise`, or with draw=True row first_id + b of ops.philox_normal(seed, stream
+    1 + n_iters - 1 - step_idx[0]) drawn in the kernel. The keep bits come from (seed, first_id + b, iteration); see include/stedm_hip.h.
+    eps_out: the guided eps (may be e_c); noise_out: the noise term (both [B, C, H, W] fp32)."""
+    _chk(x, name="x")
+    _chk(e_c, name="e_c")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, C, H, W], got {tuple(x.shape)}")
+    B, Cc, H, W = x.shape
+    for t, nm in ((e_u, "e_u"), (noise, "noise"), (x_prev, "x_prev"), (pred_x0, "pred_x0"), (eps_out, "eps_out"), (noise_out, "noise_out")):
+        if t is not None:
+            _chk(t, name=nm)
+            if tuple(t.shape) != tuple(x.shape):
+                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {tuple(x.shape)}")
+    if draw and noise is not None:
+        raise ValueError("a given noise tensor and the in-kernel draw exclude each other")
+    if not 0.0 <= float(noise_dropout) < 1.0:
+        raise ValueError(f"noise_dropout {noise_dropout} outside [0, 1)")
+    if (draw or noise_dropout > 0) and (step_idx is None or int(n_iters) <= 0):
+        raise ValueError("the in-kernel draw and the noise dropout need step_idx (device int32) and n_iters > 0")
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+    check(lib().stedm_ddim_step_ex(x.data_ptr(), e_c.data_ptr(), _ptr(e_u), _ptr(noise), coefs.data_ptr(), _ptr(step_idx), int(n_iters),
+                                   float(cfg_scale), float(rescale_phi), 1 if draw else 0, float(temperature), float(noise_dropout),
+                                   int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, x_prev.data_ptr(), _ptr(pred_x0), _ptr(eps_out),
+                                   _ptr(noise_out), B, Cc, H, W, _stream()), "stedm_ddim_step_ex")
+    return x_prev
+
+
+def ddim_quantize_x0(pred_x0: torch.Tensor, eps: torch.Tensor, coefs: torch.Tensor, codebook: torch.Tensor, x_prev: torch.Tensor,
+                     noise: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None,
+                     idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """quantize_x0 inside a DDIM step (stedm_ddim_quantize_x0): pred_x0 [B, C, H, W] -> its nearest codebook rows in place (straight-through
+    value, the indices of vq_nearest), x_prev = (sqrt(a_prev) pred_x0 + dir eps) + noise. codebook [n_e, C]; idx: optional int64 [B, H, W]."""
+    _chk(pred_x0, name="pred_x0"); _chk(eps, name="eps"); _chk(codebook, name="codebook"); _chk(x_prev, name="x_prev")
+    if pred_x0.dim() != 4:
+        raise ValueError(f"pred_x0 must be [B, C, H, W], got {tuple(pred_x0.shape)}")
+    B, Cc, H, W = pred_x0.shape
+    if codebook.dim() != 2 or codebook.shape[1] != Cc:
+        raise ValueError(f"codebook {tuple(codebook.shape)} must be [n_e, {Cc}]")
+    for t, nm in ((eps, "eps"), (noise, "noise"), (x_prev, "x_prev")):
+        if t is not None:
+            _chk(t, name=nm)
+            if tuple(t.shape) != tuple(pred_x0.shape):
+                raise ValueError(f"{nm} {tuple(t.shape)} must have pred_x0's shape {tuple(pred_x0.shape)}")
+    if idx is not None:
+        _chk(idx, torch.int64, "idx")
+        assert idx.numel() == B * H * W
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+    check(lib().stedm_ddim_quantize_x0(pred_x0.data_ptr(), eps.data_ptr(), _ptr(noise), coefs.data_ptr(), _ptr(step_idx), codebook.data_ptr(),
+                                       int(codebook.shape[0]), Cc, B, H * W, x_prev.data_ptr(), _ptr(idx), _stream()), "stedm_ddim_quantize_x0")
+    return x_prev
+
 def ddim_mask_blend(img: torch.Tensor, x0: torch.Tensor, mask: torch.Tensor, t: torch.Tensor, sqrt_ac: torch.Tensor, sqrt_1mac: torch.Tensor,
                     noise: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None, seed: int = 0, first_id: int = 0) -> torch.Tensor:
     """ddim.py:143-146 in place: img = q_sample(x0, t) * mask + (1 - mask) * img (stedm_ddim_mask_blend). img, x0 [B, C, h, w]; mask
