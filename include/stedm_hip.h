@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 17
+#define STEDM_ABI_VERSION 18
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -394,6 +394,30 @@ int stedm_step_set_t_f32(const float* ts_table, const int32_t* step_idx, float* 
 #define STEDM_DPM_NCOEF 6
 int stedm_dpm_step(float* x, const float* e_c, const float* e_u, float* x0_prev, float* pred_x0, const float* coefs,
                    const int32_t* step_idx, float cfg_scale, long n, void* stream);
+
+/* ---- General DPM-Solver (ABI 18) ---------------------------------------------------------- */
+/* One model evaluation (NFE) of the reference's DPM_Solver.sample (dpm_solver.py: multistep / singlestep / singlestep_fixed, orders 1-3,
+ * noise or data prediction, 'dpm_solver' or 'taylor', denoise_to_zero), elementwise over n fp32 elements, from row *step_idx (DEVICE
+ * int32; NULL: row 0) of the plan rows [R][STEDM_DPMU_NCOEF] (stedm_amd/dpm_solver.py, dpm_plan; the layout and the update kinds are
+ * listed there):
+ *   eps = e_u + s (e_c - e_u)  (e_u NULL: eps = e_c)          m = to_x0 ? (x - sigma eps) / alpha : eps      slot[w] = m
+ *   out = the row's linear form over the base and slots 0..2 (first order; one difference; multistep third order; singlestep taylor
+ *         third order; copy)                                    x = out; base = out when the row commits; pred_x0 (may be NULL) = x0
+ * slots: 3 slots of n elements at slots + j * slot_stride. mode STEDM_DPMU_ALL does both halves; MODEL only writes slot[w]; COMBINE only
+ * computes out (from slot[w] as stored, e.g. after stedm_dpm_threshold). The reference's operations in its order, each rounded once.
+ * x, base, the slots and pred_x0 may alias one another element for element (each element is read before it is written). */
+#define STEDM_DPMU_NCOEF 24
+#define STEDM_DPMU_ALL 0
+#define STEDM_DPMU_MODEL 1
+#define STEDM_DPMU_COMBINE 2
+int stedm_dpm_update(float* x, float* base, const float* e_c, const float* e_u, float* slots, long slot_stride, float* pred_x0,
+                     const float* rows, const int32_t* step_idx, float cfg_scale, int mode, long n, void* stream);
+/* Dynamic thresholding (data_prediction_fn, dpm_solver.py:361-374) in place on B samples of n elements of slot w: s_b =
+ * max(torch.quantile(|x0_b|, 0.995), max_val) bit for bit, x0_b = clamp(x0_b, -s_b, s_b) / s_b. rows / step_idx given: w and whether to
+ * act at all come from the row (a row without thresholding leaves the slot alone); rows NULL: slot 0, always. q_out (may be NULL): the
+ * B quantiles before the max. One workgroup per sample; no allocation, no global atomics, graph-capturable. */
+int stedm_dpm_threshold(float* slots, long slot_stride, const float* rows, const int32_t* step_idx, float max_val, int B, long n,
+                        float* q_out, void* stream);
 
 /* ---- PLMS update (ABI 15) ------------------------------------------------------------------ */
 /* One update of the reference's PLMS sampler (plms.py:173-239, ddim_eta = 0), elementwise over n fp32 elements:

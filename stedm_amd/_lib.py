@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 
@@ -100,6 +100,8 @@ SIGNATURES = {
     "stedm_step_set_t": (_I, [_P, _P, _P, _I, _P]),
     "stedm_step_set_t_f32": (_I, [_P, _P, _P, _I, _P]),
     "stedm_dpm_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, C.c_long, _P]),
+    "stedm_dpm_update": (_I, [_P, _P, _P, _P, _P, C.c_long, _P, _P, _P, _F, _I, C.c_long, _P]),
+    "stedm_dpm_threshold": (_I, [_P, C.c_long, _P, _P, _F, _I, C.c_long, _P, _P]),
     "stedm_plms_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, C.c_long, _P]),
     "stedm_svit_patch_embed": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _P]),
     "stedm_svit_patch_ln16": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _I, _P]),

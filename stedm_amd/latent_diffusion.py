@@ -30,6 +30,8 @@ from .schedule import POSTERIOR_BUFFERS, NoiseSchedule, PosteriorSchedule
 from .unet import UNetModel
 
 SAMPLERS = ("ddim", "dpm_solver", "plms")          # sample_log / predict_latents(sampler=...)
+DPM_OPTIONS = ("order", "method", "skip_type", "predict_x0", "solver_type", "lower_order_final", "denoise_to_zero", "thresholding", "max_val",
+               "t_start", "t_end")                  # predict_latents(sampler="dpm_solver", dpm_solver={...}): DPMSolverSampler.sample keywords
 ANCESTRAL = "ddpm"                                  # the reference's 1000-step ancestral chain: sample_log(ddim=False) / sampler="ddpm"
 ALL_SAMPLERS = SAMPLERS + (ANCESTRAL,)
 
@@ -602,7 +604,9 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):
         """ddpm.py:1237-1250. sampler: "ddim" (the reference's) or "dpm_solver" (DPMSolverSampler, the reference's
-        ldm/models/diffusion/dpm_solver: DPM-Solver++(2M), ddim_steps model evaluations) or "plms" (PLMSSampler, the reference's
+        ldm/models/diffusion/dpm_solver: DPM-Solver++(2M), ddim_steps model evaluations; the keywords order, method, skip_type,
+        predict_x0, solver_type, lower_order_final, denoise_to_zero, thresholding, max_val, t_start and t_end select the rest of the
+        reference's DPM_Solver.sample, e.g. order=3 for DPM-Solver++(3M) or method="singlestep" for DPM-Solver-fast) or "plms" (PLMSSampler, the reference's
         plms.py: DDIM's schedule, n iterations cost n + 1 model evaluations, mask / x0 as DDIM; returns (x, intermediates)).
         ddim=False (or sampler="ddpm"): the reference's ancestral chain, self.sample(cond, batch_size, return_intermediates=True,
         **kwargs); ddim_steps is ignored and intermediates is a list."""
@@ -721,7 +725,7 @@ def prepare_batch(batch, device=None) -> dict:
 def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: float = 0.0, cfg_scale: float = 1.0,
                     style_sampling: str = "nearby", x_T: Optional[torch.Tensor] = None, dedup_uncond: bool = True, noises=None,
                     mask: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None, mask_seed: Optional[int] = None, sample_id0: int = 0,
-                    sampler: str = "ddim", noise_seed: Optional[int] = None):
+                    sampler: str = "ddim", noise_seed: Optional[int] = None, dpm_solver: Optional[dict] = None):
     """Lightning-free restatement of LDM_Diffusion.predict_step (modules/ldm_diffusion.py:76-91) up to the sampled latents:
     conditional get_input, unconditional batch {image: 0, segmentation: same, style_imgs: -2}, DDIM + CFG.
 
@@ -747,9 +751,19 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
 
     noise_seed with sampler="ddim" and eta != 0: every step's noise is drawn in the DDIM kernel as row sample_id0 + b of
     ops.philox_normal(noise_seed, stream 1 + iteration) (DDIMSampler.sample), so the loop can be graphed; given `noises` take precedence.
-    Without it (or with eta == 0) the DDIM noise is torch's, as before."""
+    Without it (or with eta == 0) the DDIM noise is torch's, as before.
+
+    dpm_solver (sampler="dpm_solver" only, ValueError otherwise): a dict of DPMSolverSampler.sample's solver options (DPM_OPTIONS:
+    order, method, skip_type, predict_x0, solver_type, lower_order_final, denoise_to_zero, thresholding, max_val, t_start, t_end);
+    None or {} keeps DPM-Solver++(2M)."""
     if sampler not in ALL_SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}; choose from {ALL_SAMPLERS}")
+    if dpm_solver is not None:
+        if sampler != "dpm_solver":
+            raise ValueError(f"dpm_solver options are for sampler='dpm_solver', got sampler={sampler!r}")
+        bad = sorted(set(dpm_solver) - set(DPM_OPTIONS))
+        if bad:
+            raise ValueError(f"unknown dpm_solver option(s) {bad}; choose from {DPM_OPTIONS}")
     if sampler == ANCESTRAL and cfg_scale != 1 and style_sampling != "none":
         raise NotImplementedError("sampler='ddpm': the reference's ancestral chain has no classifier-free guidance (cfg_scale must be 1)")
     if sampler == ANCESTRAL and eta != 0.0:
@@ -773,6 +787,7 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
         return out
     if sampler != "ddim":
         kw["sampler"] = sampler
+        kw.update(dpm_solver or {})
     elif eta != 0.0 and noise_seed is not None:
         kw.update(noise_seed=int(noise_seed), sample_id0=int(sample_id0))
     if cfg_scale == 1 or style_sampling == "none":

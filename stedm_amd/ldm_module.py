@@ -129,12 +129,16 @@ class LDM_Diffusion(_Base):
         The config key `sampler` (optional; "ddim" when absent, as in the reference's configs) selects "dpm_solver" (DPM-Solver++(2M),
         stedm_amd/dpm_solver.py); `ddim_steps` is then the number of model evaluations (DDIM's uniform stride makes 128 into 143). "plms"
         selects PLMS (stedm_amd/plms.py), DDIM's schedule with n + 1 model evaluations for n iterations. "ddpm" runs the reference's
-        ancestral chain (stedm_amd/ancestral.py: model.num_timesteps unguided steps, ddim_steps ignored; cfg_scale must then be 1)."""
+        ancestral chain (stedm_amd/ancestral.py: model.num_timesteps unguided steps, ddim_steps ignored; cfg_scale must then be 1).
+        The optional mapping `dpm_solver` (with sampler "dpm_solver") holds DPM-Solver options (latent_diffusion.DPM_OPTIONS, e.g.
+        {order: 3} or {method: singlestep, order: 3}); configs without it run exactly as before."""
         cfg = self._cfg
         ldm_batch = self.prepare_batch(batch)
         sname = cfg.style_sampling["name"] if isinstance(cfg.style_sampling, dict) else cfg.style_sampling.name
+        dpm = getattr(cfg, "dpm_solver", None)
+        extra = {} if dpm is None else {"dpm_solver": dict(dpm.items() if hasattr(dpm, "items") else vars(dpm).items())}
         lat = predict_latents(self._model, ldm_batch, ddim_steps=cfg.ddim_steps, eta=cfg.eta, cfg_scale=cfg.cfg_scale, style_sampling=sname,
-                              sampler=getattr(cfg, "sampler", None) or "ddim")
+                              sampler=getattr(cfg, "sampler", None) or "ddim", **extra)
         dec = self._model.decode_first_stage(lat)
         img, seg = images_for_saving(dec, ldm_batch["segmentation"])
         img, seg = img.cpu().numpy(), seg.cpu().numpy()

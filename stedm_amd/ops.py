@@ -1119,6 +1119,7 @@ def step_set_t(ts_table: torch.Tensor, step_idx: torch.Tensor, t_buf: torch.Tens
 
 # ------------------------------------------------------------------------------------------- DPM-Solver++(2M)
 DPM_NCOEF = 6       # STEDM_DPM_NCOEF: {alpha_i, sigma_i, r, A, inv_r0, 0.5 A}
+DPMU_NCOEF = 24     # STEDM_DPMU_NCOEF: one row of the general DPM-Solver plan (dpm_solver.R_* layout)
 
 
 def dpm_step(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], x0_prev: torch.Tensor, coefs: torch.Tensor,
@@ -1140,6 +1141,69 @@ def dpm_step(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], x0
     check(lib().stedm_dpm_step(x.data_ptr(), e_c.data_ptr(), _ptr(e_u), x0_prev.data_ptr(), _ptr(pred_x0), coefs.data_ptr(),
                                _ptr(step_idx), float(cfg_scale), x.numel(), _stream()), "stedm_dpm_step")
     return x
+
+
+DPMU_ALL, DPMU_MODEL, DPMU_COMBINE = 0, 1, 2      # STEDM_DPMU_*: the mode argument of stedm_dpm_update
+
+
+def dpm_update(x: torch.Tensor, base: torch.Tensor, e_c: Optional[torch.Tensor], e_u: Optional[torch.Tensor], slots: torch.Tensor,
+               rows: torch.Tensor, step_idx: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, mode: int = DPMU_ALL,
+               pred_x0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One NFE of the general DPM-Solver (stedm_dpm_update) from row step_idx[0] of the plan rows (dpm_solver.dpm_plan): the model output
+    m = e_u + s (e_c - e_u) (e_u None: e_c), as x0 = (x - sigma eps) / alpha when the row asks, into slots[w]; then the row's update of the
+    base and the slots into x (and into base when the row commits); pred_x0, if given, = the x0 of this NFE. x and base may be one tensor.
+    slots: [3, *x.shape]; rows: device float32 [R, DPMU_NCOEF]; mode DPMU_ALL / DPMU_MODEL (slot only) / DPMU_COMBINE (update only)."""
+    _chk(x, name="x"); _chk(base, name="base"); _chk(slots, name="slots"); _chk(rows, name="rows")
+    shp = tuple(x.shape)
+    if mode not in (DPMU_ALL, DPMU_MODEL, DPMU_COMBINE):
+        raise ValueError(f"mode must be DPMU_ALL / DPMU_MODEL / DPMU_COMBINE, got {mode!r}")
+    if e_c is None and mode != DPMU_COMBINE:
+        raise ValueError("e_c is required unless mode is DPMU_COMBINE")
+    for t, nm in ((base, "base"), (e_c, "e_c"), (e_u, "e_u"), (pred_x0, "pred_x0")):
+        if t is not None:
+            _chk(t, name=nm)
+            if tuple(t.shape) != shp:
+                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {shp}")
+    if tuple(slots.shape) != (3,) + shp:
+        raise ValueError(f"slots must be [3, *x.shape] = {(3,) + shp}, got {tuple(slots.shape)}")
+    if rows.dim() != 2 or rows.shape[1] != DPMU_NCOEF:
+        raise ValueError(f"rows must be [R, {DPMU_NCOEF}], got {tuple(rows.shape)}")
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+    check(lib().stedm_dpm_update(x.data_ptr(), base.data_ptr(), _ptr(e_c), _ptr(e_u), slots.data_ptr(), x.numel(), _ptr(pred_x0),
+                                 rows.data_ptr(), _ptr(step_idx), float(cfg_scale), int(mode), x.numel(), _stream()), "stedm_dpm_update")
+    return x
+
+
+def dpm_threshold(slots: torch.Tensor, max_val: float, rows: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None,
+                  q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dynamic thresholding in place (stedm_dpm_threshold): per sample b of the slot, s = max(torch.quantile(|x0_b|, 0.995), max_val)
+    (the quantile bit for bit) and x0_b = clamp(x0_b, -s, s) / s. slots: [3, B, ...] with rows (the slot and whether to act come from
+    row step_idx[0]), or [B, ...] without rows (acts on it). q_out: device float32 [B] for the quantiles before the max."""
+    _chk(slots, name="slots")
+    if rows is not None:
+        _chk(rows, name="rows")
+        if slots.dim() < 3 or slots.shape[0] != 3:
+            raise ValueError(f"with rows, slots must be [3, B, ...], got {tuple(slots.shape)}")
+        if rows.dim() != 2 or rows.shape[1] != DPMU_NCOEF:
+            raise ValueError(f"rows must be [R, {DPMU_NCOEF}], got {tuple(rows.shape)}")
+        B = int(slots.shape[1])
+        stride = slots[0].numel()
+    else:
+        if slots.dim() < 2:
+            raise ValueError(f"slots must be [B, ...], got {tuple(slots.shape)}")
+        B = int(slots.shape[0])
+        stride = slots.numel()
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+    if q_out is not None:
+        _chk(q_out, name="q_out")
+        if tuple(q_out.shape) != (B,):
+            raise ValueError(f"q_out must be [{B}], got {tuple(q_out.shape)}")
+    n = stride // B
+    check(lib().stedm_dpm_threshold(slots.data_ptr(), stride, _ptr(rows), _ptr(step_idx), float(max_val), B, n, _ptr(q_out), _stream()),
+          "stedm_dpm_threshold")
+    return slots
 
 
 # ------------------------------------------------------------------------------------------- PLMS
