@@ -41,23 +41,32 @@ class DPMTables:
 
 
 class _VPSchedule:
-    """NoiseScheduleVP('discrete', alphas_cumprod=...) (dpm_solver.py:7-132) on fp32 CPU tensors: log(alpha_t) is the piecewise-linear
-    interpolation of 0.5 log(alphas_cumprod) over the keypoints t_n = (n + 1) / N, extended linearly beyond the ends."""
+    """NoiseScheduleVP('discrete', alphas_cumprod=...) (dpm_solver.py:7-152) on fp32 CPU tensors of any shape: log(alpha_t) is the
+    piecewise-linear interpolation of 0.5 log(alphas_cumprod) over the keypoints t_n = (n + 1) / N, extended linearly beyond the ends;
+    inverse_lambda (:140-152) is log_alpha = -0.5 logaddexp(0, -2 lambda), then the same interpolation over the flipped keypoints (t as
+    a function of log_alpha)."""
 
     def __init__(self, alphas_cumprod):
         ac = torch.as_tensor(alphas_cumprod).detach().to("cpu", torch.float32)
         self.log_alpha = 0.5 * torch.log(ac)
         self.N = int(ac.shape[0])
         self.t_keys = torch.linspace(0., 1., self.N + 1)[1:]
+        self.la_flip = torch.flip(self.log_alpha, [0])
+        self.t_flip = torch.flip(self.t_keys, [0])
 
-    def log_mean_coeff(self, t: torch.Tensor) -> torch.Tensor:
-        # segment j holds t: the last keypoint strictly below t, clamped to the first / last segment (the reference's sort-based search
-        # places t ahead of an equal keypoint); then y_j + (t - x_j) (y_{j+1} - y_j) / (x_{j+1} - x_j), in that order
-        xp, yp = self.t_keys, self.log_alpha
-        j = (xp[None, :] < t[:, None]).sum(1) - 1
-        j = j.clamp(0, self.N - 2)
+    @staticmethod
+    def _interp(x, xp, yp):
+        # segment j holds x: the last keypoint strictly below x, clamped to the first / last segment (the reference's sort-based search
+        # places x ahead of an equal keypoint); then y_j + (x - x_j) (y_{j+1} - y_j) / (x_{j+1} - x_j), in that order
+        K = xp.shape[0]
+        shp = x.shape
+        x = x.reshape(-1)
+        j = ((xp[None, :] < x[:, None]).sum(1) - 1).clamp(0, K - 2)
         x0, x1, y0, y1 = xp[j], xp[j + 1], yp[j], yp[j + 1]
-        return y0 + (t - x0) * (y1 - y0) / (x1 - x0)
+        return (y0 + (x - x0) * (y1 - y0) / (x1 - x0)).reshape(shp)
+
+    def log_mean_coeff(self, t):
+        return self._interp(t, self.t_keys, self.log_alpha)
 
     def alpha(self, t):
         return torch.exp(self.log_mean_coeff(t))
@@ -68,6 +77,10 @@ class _VPSchedule:
     def lam(self, t):
         lmc = self.log_mean_coeff(t)
         return lmc - 0.5 * torch.log(1. - torch.exp(2. * lmc))
+
+    def inverse_lambda(self, lamb):
+        log_alpha = -0.5 * torch.logaddexp(torch.zeros((1,)), -2. * lamb)
+        return self._interp(log_alpha.reshape(-1), self.la_flip, self.t_flip).reshape((-1,))
 
 
 def dpm_tables(alphas_cumprod, S: int, lower_order_final: bool = True) -> DPMTables:
@@ -121,32 +134,6 @@ K_FIRST, K_DIFF, K_MS3, K_SS3T, K_COPY = range(5)
 #   K_COPY   m_P
 
 
-class _VPRef(_VPSchedule):
-    """NoiseScheduleVP('discrete') on fp32 tensors of any shape, inverse_lambda included (dpm_solver.py:140-152): log_alpha =
-    -0.5 logaddexp(0, -2 lambda), then interpolate_fn over the flipped keypoints (t as a function of log_alpha)."""
-
-    def __init__(self, alphas_cumprod):
-        super().__init__(alphas_cumprod)
-        self.la_flip = torch.flip(self.log_alpha, [0])
-        self.t_flip = torch.flip(self.t_keys, [0])
-
-    @staticmethod
-    def _interp(x, xp, yp):
-        K = xp.shape[0]
-        shp = x.shape
-        x = x.reshape(-1)
-        j = ((xp[None, :] < x[:, None]).sum(1) - 1).clamp(0, K - 2)
-        x0, x1, y0, y1 = xp[j], xp[j + 1], yp[j], yp[j + 1]
-        return (y0 + (x - x0) * (y1 - y0) / (x1 - x0)).reshape(shp)
-
-    def log_mean_coeff(self, t):
-        return self._interp(t, self.t_keys, self.log_alpha)
-
-    def inverse_lambda(self, lamb):
-        log_alpha = -0.5 * torch.logaddexp(torch.zeros((1,)), -2. * lamb)
-        return self._interp(log_alpha.reshape(-1), self.la_flip, self.t_flip).reshape((-1,))
-
-
 @dataclass
 class DPMPlan:
     """Host plan of a general DPM-Solver run, one row per model evaluation (NFE). t_input: fp32 [R] model times; rows: fp32
@@ -160,7 +147,7 @@ class DPMPlan:
     max_val: float
 
 
-def _get_time_steps(ns: _VPRef, skip_type, t_T, t_0, N):
+def _get_time_steps(ns: _VPSchedule, skip_type, t_T, t_0, N):
     """DPM_Solver.get_time_steps (dpm_solver.py:396-421) on the CPU."""
     if skip_type == "logSNR":
         lambda_T = ns.lam(torch.tensor(t_T).reshape(1)).reshape(())
@@ -221,7 +208,7 @@ def dpm_plan(alphas_cumprod, steps, order=2, method="multistep", skip_type="time
     its 3-entry model list into two names and raises; here it reads the last two entries, as later DPM-Solver releases do."""
     check_dpm_options(steps, order, method, skip_type, solver_type)
     steps = int(steps)
-    ns = _VPRef(alphas_cumprod)
+    ns = _VPSchedule(alphas_cumprod)
     t_0 = 1. / ns.N if t_end is None else float(t_end)
     t_T = 1. if t_start is None else float(t_start)
     one = lambda v: torch.as_tensor(v, dtype=torch.float32).reshape(1)
@@ -584,6 +571,9 @@ class DPMPlanGraph:
         self.threshold, self.max_val = plan.threshold, plan.max_val
         self.graph = None
         self.side = None
+
+    def reset(self, index: int):
+        self.step.fill_(int(index))
 
     def nfe(self, pred_x0=None, eager_t=None):
         s = self.s

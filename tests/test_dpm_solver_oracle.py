@@ -4,6 +4,8 @@ closed-form eps model (tests/golden/make_golden_dpm.py).
   * `ref_dpm_sample`, a test-local fp32 restatement of the reference's multistep loop, reproduces every call's input and the final x —
     it is the yardstick the GPU tier runs over the oracle U-Net;
   * the product's coefficient table, through `dpm_update_ref` (stedm_dpm_step's formula in torch), reproduces the same loop;
+  * the general plan with the default keywords (dpm_plan) holds the same rows and model times as `dpm_tables` bit for bit, and its loop
+    (`plan_sample`, stedm_dpm_update's formula) returns the bits of the 2M loop (`table_dpm_sample`);
   * the options the sampler does not build, and S < 2, raise before any device work."""
 import numpy as np
 import pytest
@@ -106,6 +108,13 @@ def table_dpm_sample(eps_fn, x_T, coefs, t_input, scale=1.0, cond=None, uncond=N
     return x
 
 
+def rows_2m(plan):
+    """The 2M coefficient rows {alpha, sigma, r, A, inv_r0, 0.5 A} from the columns of a default plan (K_DIFF stores c = -(0.5 A))."""
+    from stedm_amd import dpm_solver as D
+    r = plan.rows
+    return torch.stack([r[:, D.R_ALPHA], r[:, D.R_SIGMA], r[:, D.R_A], r[:, D.R_B], r[:, D.R_K0], -r[:, D.R_C]], 1)
+
+
 def rel(a, b):
     a, b = torch.as_tensor(a).double(), torch.as_tensor(b).double()
     assert a.shape == b.shape, (a.shape, b.shape)
@@ -158,6 +167,37 @@ def test_coefficient_table_reproduces_the_loop(golden, name):
     out = table_dpm_sample(toy, c["xT"], tb.coefs, tb.t_input, c["scale"], c["cond"], c["uncond"])
     assert rel(out, c["out"]) <= 1e-6
     assert rel(out, ref_dpm_sample(toy, c["xT"], c["ac"], c["S"], c["scale"], c["cond"], c["uncond"])) <= 1e-6
+
+
+@pytest.mark.parametrize("scale", [1.0, 1.5])
+@pytest.mark.parametrize("S", [2, 3, 5, 14, 15, 20, 33])
+def test_default_plan_is_the_2m_update_bitwise(golden, S, scale):
+    """The default keywords' plan: first order at step 0 (and at the last step when S < 15), K_DIFF elsewhere, data prediction, every
+    row commits, model j in ring slot j mod 3 and the difference against slot (j - 1) mod 3. Its columns are dpm_tables' rows and its
+    loop (plan_sample) returns the bits of the 2M expression (table_dpm_sample): (a x - b m) + (-(0.5 A)) D is (r x - A x0) - (0.5 A) D."""
+    from stedm_amd import dpm_solver as D
+    from tests.test_dpm_solver_general_oracle import plan_sample
+    c = f18_case(golden, "s20")
+    p, tb = D.dpm_plan(c["ac"], S), D.dpm_tables(c["ac"], S)
+    first = [j == 0 or (S < 15 and j == S - 1) for j in range(S)]
+    assert p.rows.shape == (S, 24) and not p.threshold
+    assert p.orders == tb.orders == [1 if f else 2 for f in first] and p.commits == [True] * S
+    col = lambda i: [int(v) for v in p.rows[:, i]]
+    assert col(D.R_KIND) == [D.K_FIRST if f else D.K_DIFF for f in first]
+    assert col(D.R_TO_X0) == [1] * S and col(D.R_THRESH) == [0] * S and col(D.R_COMMIT) == [1] * S
+    assert col(D.R_W) == col(D.R_P) == [j % 3 for j in range(S)]
+    for j in range(S):
+        if not first[j]:
+            assert (int(p.rows[j, D.R_U0]), int(p.rows[j, D.R_V0])) == (j % 3, (j - 1) % 3), j
+    coefs = rows_2m(p)
+    assert torch.equal(p.t_input, tb.t_input)
+    assert torch.equal(coefs[:, :4], tb.coefs[:, :4])
+    assert torch.equal(coefs[:, 5], tb.coefs[:, 5]) and bool((coefs[:, 5] == 0).eq(torch.tensor(first)).all())
+    assert all(torch.equal(coefs[j, 4], tb.coefs[j, 4]) for j in range(S) if not first[j])       # inv_r0: unused at first order
+    want = table_dpm_sample(toy, c["xT"], tb.coefs, tb.t_input, scale, c["cond"], c["uncond"])
+    assert torch.equal(table_dpm_sample(toy, c["xT"], coefs, p.t_input, scale, c["cond"], c["uncond"]), want)
+    got = plan_sample(p, toy, c["xT"], scale, c["cond"], c["uncond"])
+    assert bool(torch.isfinite(want).all()) and torch.equal(got, want)
 
 
 class _NoDeviceModel:

@@ -76,6 +76,37 @@ def test_dpm_update_kernel_matches_torch_bitwise(dev, shape):
                 ops.dpm_update(xm, bm, None, None, sm, rows, step_idx=step, mode=ops.DPMU_COMBINE, pred_x0=pm)
                 assert torch.equal(xm.cpu(), want_x) and torch.equal(bm.cpu(), want_b) and torch.equal(pm.cpu(), want_p), (i, cfg)
     assert kinds == {D.K_FIRST, D.K_DIFF, D.K_MS3, D.K_SS3T, D.K_COPY}
+    # the default keywords (DPM-Solver++(2M)) as a multistep run has them: base IS x; rows 0 (first order), 2 (second order) and 4 (the
+    # first-order final step) of a 5-step plan, against this file's restatement and against the 2M expression stated on its own
+    from oracle import ddim as od
+    from tests.test_dpm_solver_oracle import dpm_update_ref as dpm_2m_ref, rows_2m
+    p = D.dpm_plan(od.Schedule().alphas_cumprod, 5)
+    rows, coefs = p.rows.to(dev), rows_2m(p)
+    assert p.orders == [1, 2, 2, 2, 1]
+    g = lambda k: prng.normal(70, k, shape)
+    x, ec, eu, x0_prev = g("k.x"), g("k.ec"), g("k.eu"), g("k.x0p")
+    for i in (0, 2, 4):
+        row, w = p.rows[i], i % 3
+        step = torch.tensor([i], dtype=torch.int32, device=dev)
+        sl = [torch.full(shape, float("nan"))] * 3          # a first-order row reads no stored slot, a second-order row slot (i - 1) mod 3
+        if p.orders[i] == 2:
+            sl[(i - 1) % 3] = x0_prev
+        for cfg in (False, True):
+            s = 1.5 if cfg else 1.0
+            want_sl = list(sl)
+            want_x, want_b, want_p = dpm_update_ref(row, x, x, want_sl, ec, eu if cfg else None, s)
+            x_2m, x0_2m = dpm_2m_ref(x, ec, eu if cfg else None, x0_prev, coefs[i], s)
+            assert torch.equal(want_x, x_2m) and torch.equal(want_sl[w], x0_2m) and want_b is want_x and torch.equal(want_p, x0_2m)
+            xd, sd, pd = x.to(dev), torch.stack(sl).to(dev), torch.empty(shape, device=dev)
+            ops.dpm_update(xd, xd, ec.to(dev), eu.to(dev) if cfg else None, sd, rows, step_idx=step, cfg_scale=s, pred_x0=pd)
+            for got, want, nm in ((xd, x_2m, "x"), (sd[w], x0_2m, "slot"), (pd, x0_2m, "pred")):
+                assert torch.equal(got.cpu(), want), (i, cfg, nm, float((got.cpu() - want).abs().max()))
+            # pred_x0 aliasing the written slot, and e_c / e_u slices off the 16-byte grid (the elementwise form)
+            buf = torch.cat([torch.zeros(1), ec.flatten(), eu.flatten()]).to(dev)
+            ec_m, eu_m = buf[1:1 + n].view(shape), buf[1 + n:].view(shape)
+            xd2, sd2 = x.to(dev), torch.stack(sl).to(dev)
+            ops.dpm_update(xd2, xd2, ec_m, eu_m if cfg else None, sd2, rows, step_idx=step, cfg_scale=s, pred_x0=sd2[w])
+            assert torch.equal(xd2, xd) and torch.equal(sd2[w], sd[w]), (i, cfg)
 
 
 @pytest.mark.parametrize("n,B", [(256, 64), (2304, 3), (4096, 64), (65536, 1), (65536, 3)])

@@ -2,6 +2,7 @@
 """The general DPM-Solver on the graphed sampling loop (NS32 32x32 latents, CFG 1.5, 20 model evaluations (NFE), one captured NFE replayed
 per row), variants alternating round for round in one process:
   * 2m:        DPM-Solver++(2M) as shipped (the default keywords: dpm_tables, stedm_dpm_step, DPMStepGraph);
+  * 2m_plan:   the same keywords through the plan path (dpm_plan, stedm_dpm_update, DPMPlanGraph): the rows of 2m, bit for bit;
   * 3m:        order=3 (multistep, stedm_dpm_update);
   * ss3:       method="singlestep", order=3;
   * 2m_thr:    order=2 with thresholding (stedm_dpm_update split around stedm_dpm_threshold);
@@ -22,7 +23,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 
-VARIANTS = {"2m": {}, "3m": dict(order=3), "ss3": dict(method="singlestep", order=3), "2m_thr": dict(thresholding=True),
+VARIANTS = {"2m": {}, "2m_plan": {}, "3m": dict(order=3), "ss3": dict(method="singlestep", order=3), "2m_thr": dict(thresholding=True),
             "ss2_noise": dict(method="singlestep", order=2, predict_x0=False)}
 
 
@@ -50,7 +51,7 @@ def build(ld, dev, B, steps, name):
         R = int(plan.rows.shape[0])
 
         def reset():
-            g.step.fill_(0)
+            g.reset(0)
             img.copy_(xT)
             if g.base is not img:
                 g.base.copy_(xT)
