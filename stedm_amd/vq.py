@@ -8,6 +8,10 @@ arguments (`embed_dim, n_embed, ddconfig, lossconfig, ckpt_path, ...`), same `en
 same state-dict names (`encoder.down.0.block.0.norm1.weight`, `decoder.up.2.upsample.conv.weight`, `quantize.embedding.weight`,
 `quant_conv.*`, `post_quant_conv.*`), so the reference's `vq-f4.ckpt` loads with `load_state_dict`.
 
+The architecture is written down once: `first_stage_layout(**ddconfig)` lists, for the encoder and for the decoder, the rows that run
+(ResNet block, attention block, downsample, upsample) in execution order with their state-dict prefixes and channel counts.
+`_containers` builds the parameter containers from it, `_prepare` packs the weights row by row and `_walk` runs the rows.
+
 torch.nn modules are parameter containers; the arithmetic runs in the kernels the U-Net uses: GroupNorm(+SiLU) from producer-side
 channel statistics into 16-bit operand planes (stedm_gn_apply16c), 3x3 / 1x1 / fused-shortcut / sub-pixel-upsample /
 space-to-depth-downsample convolutions on MFMA (stedm_conv_igemm), the boundary convs (stedm_conv_in / stedm_conv_out), and for the
@@ -15,7 +19,7 @@ single-head attention of width C two GEMMs around a row softmax (stedm_softmax_r
 surface like the reference."""
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -25,158 +29,108 @@ from ._lib import CONV_S2D, CONV_UP_SUBPIXEL, StedmHipError
 from .ops import Precision
 
 
-def Normalize(in_channels, num_groups=32):
-    """model.py:38-39."""
-    return nn.GroupNorm(num_groups=num_groups, num_channels=in_channels, eps=1e-6, affine=True)
+class Row(NamedTuple):
+    """One step of the encoder or of the decoder."""
+    kind: str        # "res" | "attn" | "down" | "up": VQModelInterface._res / _attn / _down / _up runs it
+    prefix: str      # where its parameters live in the state dict, under `encoder.` / `decoder.` (`down.1.block.0`, `mid.attn_1`, ...)
+    cin: int
+    cout: int
 
 
-class Upsample(nn.Module):
-    """model.py:43-57 (container)."""
-
-    def __init__(self, in_channels, with_conv):
-        super().__init__()
-        self.with_conv = with_conv
-        if not with_conv:
-            raise NotImplementedError("Upsample without conv (resamp_with_conv=False) is not used by vq-f4.yaml")
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
+class Half(NamedTuple):
+    """The encoder or the decoder: conv_in, the rows in execution order, GroupNorm + SiLU + conv_out."""
+    stack: str                   # name of its list of levels: "down" (registered before `mid`) or "up" (after it)
+    conv_in: Tuple[int, int]     # channels in, out
+    rows: Tuple[Row, ...]
+    norm_out: int
+    conv_out: Tuple[int, int]
 
 
-class Downsample(nn.Module):
-    """model.py:59-79 (container): F.pad(x, (0,1,0,1)) then conv 3x3 stride 2 padding 0."""
-
-    def __init__(self, in_channels, with_conv):
-        super().__init__()
-        self.with_conv = with_conv
-        if not with_conv:
-            raise NotImplementedError("Downsample without conv (resamp_with_conv=False) is not used by vq-f4.yaml")
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
+class Layout(NamedTuple):
+    levels: int                  # resolutions; the stage's downsampling factor is 2 ** (levels - 1)
+    encoder: Half
+    decoder: Half
 
 
-class ResnetBlock(nn.Module):
-    """model.py:82-140 (container; temb_channels = 0 in Encoder / Decoder, so there is no temb_proj)."""
+def first_stage_layout(*, ch, out_ch, num_res_blocks, attn_resolutions, in_channels, resolution, z_channels, ch_mult=(1, 2, 4, 8), dropout=0.0,
+                       resamp_with_conv=True, double_z=True, give_pre_end=False, tanh_out=False, use_linear_attn=False, attn_type="vanilla",
+                       **unused) -> Layout:
+    """The first stage's architecture from its `ddconfig` (the keyword arguments of the reference's Encoder / Decoder), written down once:
+    the containers, the weight packing and the forward walk all read it. Pure Python, no tensors. Options the kernels do not cover are
+    refused here, before any module or device work."""
+    widths = [ch * m for m in ch_mult]
+    n = len(widths)
+    for option, refused in (("resamp_with_conv=False", n > 1 and not resamp_with_conv), ("use_linear_attn=True", use_linear_attn),
+                            ('attn_type="linear"', attn_type == "linear"),
+                            (f"attn_type={attn_type!r} (unknown)", attn_type not in ("vanilla", "linear", "none")),
+                            ("give_pre_end", give_pre_end), ("tanh_out", tanh_out), (f"dropout={dropout}", dropout != 0)):
+        if refused:
+            raise NotImplementedError(f"first stage ddconfig: {option} is not supported (vq-f4.yaml does not use it)")
+    attends = attn_type == "vanilla"
 
-    def __init__(self, *, in_channels, out_channels=None, conv_shortcut=False, dropout, temb_channels=512):
-        super().__init__()
-        if conv_shortcut or temb_channels > 0 or dropout != 0.0:
-            raise NotImplementedError("ResnetBlock: conv_shortcut / temb / dropout are not used by the first stage (vq-f4.yaml)")
-        self.in_channels = in_channels
-        out_channels = in_channels if out_channels is None else out_channels
-        self.out_channels = out_channels
-        self.use_conv_shortcut = conv_shortcut
-        self.norm1 = Normalize(in_channels)
-        self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1)
-        self.norm2 = Normalize(out_channels)
-        self.dropout = nn.Dropout(dropout)
-        self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1)
-        if self.in_channels != self.out_channels:
-            self.nin_shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, padding=0)
+    def level(name, k, c, blocks, side):
+        """level k of `down` / `up` at image side `side`: (its rows, its output width)"""
+        rows = []
+        for b in range(blocks):
+            rows.append(Row("res", f"{name}.{k}.block.{b}", c, widths[k]))
+            c = widths[k]
+            if attends and side in attn_resolutions:
+                rows.append(Row("attn", f"{name}.{k}.attn.{b}", c, c))
+        return rows, c
 
+    def mid(c):
+        attn = [Row("attn", "mid.attn_1", c, c)] if attends else []
+        return [Row("res", "mid.block_1", c, c)] + attn + [Row("res", "mid.block_2", c, c)]
 
-class AttnBlock(nn.Module):
-    """model.py:143-199 (container)."""
-
-    def __init__(self, in_channels):
-        super().__init__()
-        self.in_channels = in_channels
-        self.norm = Normalize(in_channels)
-        self.q = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.k = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.v = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.proj_out = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-
-
-def make_attn(in_channels, attn_type="vanilla"):
-    assert attn_type in ["vanilla", "linear", "none"], f'attn_type {attn_type} unknown'
-    if attn_type == "vanilla":
-        return AttnBlock(in_channels)
-    if attn_type == "none":
-        return nn.Identity(in_channels)
-    raise NotImplementedError("LinAttnBlock is not used by vq-f4.yaml")
-
-
-class Encoder(nn.Module):
-    """model.py:368-459 (container)."""
-
-    def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0, resamp_with_conv=True, in_channels,
-                 resolution, z_channels, double_z=True, use_linear_attn=False, attn_type="vanilla", **ignore_kwargs):
-        super().__init__()
-        if use_linear_attn:
-            attn_type = "linear"
-        self.ch, self.temb_ch = ch, 0
-        self.num_resolutions = len(ch_mult)
-        self.num_res_blocks = num_res_blocks
-        self.resolution = resolution
-        self.in_channels = in_channels
-        self.conv_in = nn.Conv2d(in_channels, self.ch, kernel_size=3, stride=1, padding=1)
-        curr_res = resolution
-        in_ch_mult = (1,) + tuple(ch_mult)
-        self.in_ch_mult = in_ch_mult
-        self.down = nn.ModuleList()
-        block_in = ch
-        for i_level in range(self.num_resolutions):
-            block, attn = nn.ModuleList(), nn.ModuleList()
-            block_in = ch * in_ch_mult[i_level]
-            block_out = ch * ch_mult[i_level]
-            for _ in range(self.num_res_blocks):
-                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, temb_channels=self.temb_ch, dropout=dropout))
-                block_in = block_out
-                if curr_res in attn_resolutions:
-                    attn.append(make_attn(block_in, attn_type=attn_type))
-            down = nn.Module()
-            down.block, down.attn = block, attn
-            if i_level != self.num_resolutions - 1:
-                down.downsample = Downsample(block_in, resamp_with_conv)
-                curr_res = curr_res // 2
-            self.down.append(down)
-        self.mid = nn.Module()
-        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch, dropout=dropout)
-        self.mid.attn_1 = make_attn(block_in, attn_type=attn_type)
-        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch, dropout=dropout)
-        self.norm_out = Normalize(block_in)
-        self.conv_out = nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, kernel_size=3, stride=1, padding=1)
+    enc = []
+    for k in range(n):                             # finest level first; every level but the coarsest ends in a stride-2 conv
+        rows, c = level("down", k, widths[k - 1] if k else ch, num_res_blocks, resolution >> k)
+        enc += rows + ([Row("down", f"down.{k}.downsample", c, c)] if k < n - 1 else [])
+    encoder = Half("down", (in_channels, ch), tuple(enc + mid(c)), c, (c, 2 * z_channels if double_z else z_channels))
+    c = widths[-1]
+    dec = mid(c)
+    for k in reversed(range(n)):                   # coarsest level first: `up.{n-1}` runs first though the state dict lists `up.0` first
+        rows, c = level("up", k, c, num_res_blocks + 1, (resolution // 2 ** (n - 1)) << (n - 1 - k))
+        dec += rows + ([Row("up", f"up.{k}.upsample", c, c)] if k else [])
+    return Layout(n, encoder, Half("up", (z_channels, widths[-1]), tuple(dec), c, (c, out_ch)))
 
 
-class Decoder(nn.Module):
-    """model.py:462-568 (container)."""
-
-    def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0, resamp_with_conv=True, in_channels,
-                 resolution, z_channels, give_pre_end=False, tanh_out=False, use_linear_attn=False, attn_type="vanilla", **ignorekwargs):
-        super().__init__()
-        if use_linear_attn:
-            attn_type = "linear"
-        if give_pre_end or tanh_out:
-            raise NotImplementedError("Decoder: give_pre_end / tanh_out are not used by vq-f4.yaml")
-        self.ch, self.temb_ch = ch, 0
-        self.num_resolutions = len(ch_mult)
-        self.num_res_blocks = num_res_blocks
-        self.resolution = resolution
-        self.in_channels = in_channels
-        self.give_pre_end, self.tanh_out = give_pre_end, tanh_out
-        block_in = ch * ch_mult[self.num_resolutions - 1]
-        curr_res = resolution // 2 ** (self.num_resolutions - 1)
-        self.z_shape = (1, z_channels, curr_res, curr_res)
-        self.conv_in = nn.Conv2d(z_channels, block_in, kernel_size=3, stride=1, padding=1)
-        self.mid = nn.Module()
-        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch, dropout=dropout)
-        self.mid.attn_1 = make_attn(block_in, attn_type=attn_type)
-        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch, dropout=dropout)
-        self.up = nn.ModuleList()
-        for i_level in reversed(range(self.num_resolutions)):
-            block, attn = nn.ModuleList(), nn.ModuleList()
-            block_out = ch * ch_mult[i_level]
-            for _ in range(self.num_res_blocks + 1):
-                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, temb_channels=self.temb_ch, dropout=dropout))
-                block_in = block_out
-                if curr_res in attn_resolutions:
-                    attn.append(make_attn(block_in, attn_type=attn_type))
-            up = nn.Module()
-            up.block, up.attn = block, attn
-            if i_level != 0:
-                up.upsample = Upsample(block_in, resamp_with_conv)
-                curr_res = curr_res * 2
-            self.up.insert(0, up)
-        self.norm_out = Normalize(block_in)
-        self.conv_out = nn.Conv2d(block_in, out_ch, kernel_size=3, stride=1, padding=1)
+def _containers(name: str, half: Half, levels: int):
+    """The parameter containers of one half (`name`: encoder / decoder) under the reference's state-dict names, and
+    [(buffer tag, row, the row's leaves)] in execution order. Levels are registered by index, not in row order, so `state_dict()`
+    lists `up.0` first."""
+    gn = lambda c: nn.GroupNorm(32, c, eps=1e-6)
+    net, stack = nn.Module(), nn.ModuleList()
+    for _ in range(levels):
+        lv = nn.Module()
+        lv.block, lv.attn = nn.ModuleList(), nn.ModuleList()
+        stack.append(lv)
+    net.conv_in = nn.Conv2d(*half.conv_in, 3, padding=1)
+    for child in ("down", "mid") if half.stack == "down" else ("mid", "up"):
+        setattr(net, child, stack if child == half.stack else nn.Module())
+    steps = []
+    for row in half.rows:
+        m, ci, co = nn.Module(), row.cin, row.cout
+        if row.kind == "res":
+            m.norm1, m.conv1, m.norm2, m.conv2 = gn(ci), nn.Conv2d(ci, co, 3, padding=1), gn(co), nn.Conv2d(co, co, 3, padding=1)
+            if ci != co:
+                m.nin_shortcut = nn.Conv2d(ci, co, 1)
+        elif row.kind == "attn":
+            m.norm = gn(ci)
+            m.q, m.k, m.v, m.proj_out = (nn.Conv2d(ci, ci, 1) for _ in range(4))
+        else:                                      # "down": zero pad bottom / right by one, then 3x3 stride 2; "up": nearest x2, then 3x3
+            m.conv = nn.Conv2d(ci, ci, 3, stride=2, padding=0) if row.kind == "down" else nn.Conv2d(ci, ci, 3, padding=1)
+        where = row.prefix.split(".")
+        if where[0] == "mid":
+            setattr(net.mid, where[1], m)
+        elif len(where) == 4:                      # down.1.block.0: the blocks of a level come in index order
+            getattr(stack[int(where[1])], where[2]).append(m)
+        else:                                      # up.2.upsample
+            setattr(stack[int(where[1])], where[2], m)
+        steps.append((f"{name}.{row.prefix}", row, m))
+    net.norm_out = gn(half.norm_out)
+    net.conv_out = nn.Conv2d(*half.conv_out, 3, padding=1)
+    return net, steps
 
 
 class VectorQuantizer(nn.Module):
@@ -228,8 +182,12 @@ class VQModelInterface(nn.Module):
             raise NotImplementedError("use_ema / colorize_nlabels / batch_resize_range: training-side options of VQModel, unused by the frozen stage")
         self.embed_dim, self.n_embed, self.image_key = embed_dim, n_embed, image_key
         dd = dict(ddconfig)
-        self.encoder = Encoder(**dd)
-        self.decoder = Decoder(**dd)
+        self.layout = first_stage_layout(**dd)
+        self._steps = {}                              # per half: [(buffer tag, row, leaves)] in execution order
+        for name in ("encoder", "decoder"):
+            net, self._steps[name] = _containers(name, getattr(self.layout, name), self.layout.levels)
+            setattr(self, name, net)
+        self.encoder.num_resolutions = self.layout.levels      # latent_diffusion.latent_mask checks an image mask's factor against it
         self.loss = nn.Identity()                     # lossconfig: torch.nn.Identity (vq-f4.yaml:22-23)
         self.quantize = VectorQuantizer(n_embed, embed_dim, beta=0.25, remap=remap, sane_index_shape=sane_index_shape)
         self.quant_conv = nn.Conv2d(dd["z_channels"], embed_dim, 1)
@@ -340,25 +298,24 @@ class VQModelInterface(nn.Module):
             self._packed[id(conv)] = _Packed(hi, lo, None if conv.bias is None else conv.bias.detach().float().contiguous(), frag, None, frag16,
                                              extra_src=w4 if (prec.npass == 3 and ks == 3) else None)
 
-        for m in self.modules():
-            if isinstance(m, ResnetBlock):
+        for _, row, m in self._steps["encoder"] + self._steps["decoder"]:
+            if row.kind == "res":
                 pack(m.conv1); pack(m.conv2)
-                if m.in_channels != m.out_channels:
+                if row.cin != row.cout:
                     pack(m.nin_shortcut)
-            elif isinstance(m, AttnBlock):
+            elif row.kind == "attn":
                 for c in (m.q, m.k, m.v, m.proj_out):
                     pack(c)
-            elif isinstance(m, Upsample):
-                w = m.conv.weight.detach().float().contiguous()
-                hi, lo = ops.pack_conv_weight_up(w, prec)
-                frag = ops.pack_conv_weight_up_frag(w, prec) if prec.npass == 1 and m.conv.in_channels % 32 == 0 else None
-                self._packed[id(m.conv)] = _Packed(hi, lo, m.conv.bias.detach().float().contiguous(), frag)
+            elif row.kind == "up":
                 pack(m.conv)                                   # the plain 3x3 form, for inputs too wide for the sub-pixel kernel's LDS ring
                 self._packed[("plain", id(m.conv))] = self._packed.pop(id(m.conv))
+                w = m.conv.weight.detach().float().contiguous()
+                hi, lo = ops.pack_conv_weight_up(w, prec)
+                frag = ops.pack_conv_weight_up_frag(w, prec) if prec.npass == 1 and row.cin % 32 == 0 else None
                 self._packed[id(m.conv)] = _Packed(hi, lo, m.conv.bias.detach().float().contiguous(), frag)
-            elif isinstance(m, Downsample):
-                # bottom/right-padded stride-2 conv as a 2x2 conv over space-to-depth planes (register-streamed kernel, single product);
-                # the 3-product parity mode runs it as hi*hi + lo*hi + hi*lo with the residual weights packed beside
+            else:
+                # "down": bottom/right-padded stride-2 conv as a 2x2 conv over space-to-depth planes (register-streamed kernel, single
+                # product); the 3-product parity mode runs it as hi*hi + lo*hi + hi*lo with the residual weights packed beside
                 w = m.conv.weight.detach().float().contiguous()
                 frag = ops.pack_conv_weight_s2d_frag(w, one, pad_br=True)
                 extra = None
@@ -402,11 +359,11 @@ class VQModelInterface(nn.Module):
                               chan_stats=self._cs_new(out) if (stats and out is not None) else None, ws=self._ws(nel),
                               w_frag16=pk.frag16 if ks == 3 else None, **kw)
 
-    def _res(self, tag, rb: ResnetBlock, x):
+    def _res(self, tag, row, rb, x):
         """ResnetBlock.forward model.py:117-140 with temb None."""
         B, H, W, _ = x.shape
-        co = rb.out_channels
-        has_skip = rb.in_channels != rb.out_channels
+        co = row.cout
+        has_skip = row.cin != co
         if has_skip:
             a16, x16 = self._norm16(rb.norm1, 1, x, want_raw=True)
         else:
@@ -436,7 +393,7 @@ class VQModelInterface(nn.Module):
             return self._wide3(pk2, h16, out, out, True)
         return ops.conv_igemm(None, pk2.hi, pk2.lo, out, res=out, **kw)
 
-    def _attn(self, tag, ab: AttnBlock, x):
+    def _attn(self, tag, row, ab, x):
         """AttnBlock.forward model.py:168-199: single head of width C over T = H*W tokens, logits scaled by C^-0.5, fp32 softmax.
         Per sample: S = Q K^T and O = P V as GEMMs on the convolution kernels (K and V^T packed as their weight operand), the
         T x T logits materialised once per sample (as the reference's bmm does)."""
@@ -478,7 +435,7 @@ class VQModelInterface(nn.Module):
         out = self._buf(tag + ".out", (B, H, W, C))
         return self._conv(self._packed[id(ab.proj_out)], self._norm16(None, 0, att, kind="att16"), out, ks=1, res=x)
 
-    def _up(self, tag, up: Upsample, x):
+    def _up(self, tag, row, up, x):
         """Upsample.forward model.py:53-57: nearest x2 then conv 3x3, evaluated in the sub-pixel form (4 output parities x 2x2 taps)."""
         B, H, W, C = x.shape
         pk = self._packed[id(up.conv)]
@@ -495,7 +452,7 @@ class VQModelInterface(nn.Module):
         return ops.conv_igemm(None, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_UP_SUBPIXEL, src16=src16,
                               bias=pk.bias, w_frag=pk.frag, chan_stats=self._cs_new(out, 4 * ops.gn_chan_nslab(H * W)))
 
-    def _down(self, tag, dn: Downsample, x):
+    def _down(self, tag, row, dn, x):
         """Downsample.forward model.py:69-79: zero pad bottom/right by one, conv 3x3 stride 2."""
         B, H, W, C = x.shape
         if H % 2 or W % 2:
@@ -516,61 +473,40 @@ class VQModelInterface(nn.Module):
         return ops.conv_igemm(None, None, None, out, prec=one, mode=CONV_S2D, src16=(hi, None), bias=pk.bias, w_frag=pk.frag, res=out,
                               chan_stats=self._cs_new(out), ws=ws, pad_br=True)
 
-    def _maybe_attn(self, tag, attn_list, i, h):
-        if len(attn_list) > 0:
-            h = self._attn(f"{tag}.attn{i}", attn_list[i], h)
-        return h
-
     # ------------------------------------------------------------------------------------------------ encoder / decoder
+    def _walk(self, name, h):
+        """the rows of one half in execution order, then GroupNorm + SiLU + conv_out; NHWC in, NCHW out"""
+        for tag, row, m in self._steps[name]:
+            h = getattr(self, "_" + row.kind)(tag, row, m, h)
+        net = getattr(self, name)
+        n, co = net.norm_out, net.conv_out
+        out = torch.empty((h.shape[0], co.out_channels, h.shape[1], h.shape[2]), dtype=torch.float32, device=h.device)
+        return ops.conv_out(h, n.weight, n.bias, n.eps, n.num_groups, self._out_w[id(co)], co.bias, out, self._chan_stats(h))
+
     @torch.no_grad()
     def _encoder(self, x):
         """Encoder.forward model.py:433-459. x [B,3,H,W] NCHW -> [B,z,H/4,W/4] NCHW."""
-        enc = self.encoder
+        ci = self.encoder.conv_in
         B, _, H, W = x.shape
-        h = self._buf("enc.in", (B, H, W, enc.ch))
+        h = self._buf("enc.in", (B, H, W, ci.out_channels))
         cs = self._cs_new(h, H // 2) if H % 2 == 0 else None
-        if not ops.conv_in(x, None, enc.conv_in.weight, enc.conv_in.bias, h, chan_stats=cs) and cs is not None:
+        if not ops.conv_in(x, None, ci.weight, ci.bias, h, chan_stats=cs) and cs is not None:
             del self._cs[h.data_ptr()]
-        for i_level in range(enc.num_resolutions):
-            lv = enc.down[i_level]
-            for i_block in range(enc.num_res_blocks):
-                h = self._res(f"enc.d{i_level}.b{i_block}", lv.block[i_block], h)
-                h = self._maybe_attn(f"enc.d{i_level}", lv.attn, i_block, h)
-            if i_level != enc.num_resolutions - 1:
-                h = self._down(f"enc.d{i_level}.down", lv.downsample, h)
-        h = self._res("enc.mid1", enc.mid.block_1, h)
-        if isinstance(enc.mid.attn_1, AttnBlock):
-            h = self._attn("enc.mid.attn", enc.mid.attn_1, h)
-        h = self._res("enc.mid2", enc.mid.block_2, h)
-        out = torch.empty((h.shape[0], enc.conv_out.out_channels, h.shape[1], h.shape[2]), dtype=torch.float32, device=h.device)
-        n = enc.norm_out
-        return ops.conv_out(h, n.weight, n.bias, n.eps, n.num_groups, self._out_w[id(enc.conv_out)], enc.conv_out.bias, out, self._chan_stats(h))
+        return self._walk("encoder", h)
 
     @torch.no_grad()
     def _decoder(self, z):
         """Decoder.forward model.py:528-568. z [B,zc,h,w] NCHW -> [B,out_ch,4h,4w] NCHW."""
-        dec = self.decoder
+        ci = self.decoder.conv_in
         B, _, H, W = z.shape
-        h = self._buf("dec.in", (B, H, W, dec.conv_in.out_channels))
-        # z_channels (3 or 4) -> block_in: zero-padded to 32 channels (layout shuffle) and run on the MFMA kernels like every other conv
+        h = self._buf("dec.in", (B, H, W, ci.out_channels))
+        # z_channels (3 or 4) -> the coarsest level's width: zero-padded to 32 channels (layout shuffle) and run on the MFMA kernels like
+        # every other conv
         zp = self._buf("dec.zpad", (B, H, W, 32))
         zp.zero_()
         zp[..., :z.shape[1]].copy_(z.permute(0, 2, 3, 1))
-        self._conv(self._packed[id(dec.conv_in)], self._norm16(None, 0, zp, kind="z16"), h)
-        h = self._res("dec.mid1", dec.mid.block_1, h)
-        if isinstance(dec.mid.attn_1, AttnBlock):
-            h = self._attn("dec.mid.attn", dec.mid.attn_1, h)
-        h = self._res("dec.mid2", dec.mid.block_2, h)
-        for i_level in reversed(range(dec.num_resolutions)):
-            lv = dec.up[i_level]
-            for i_block in range(dec.num_res_blocks + 1):
-                h = self._res(f"dec.u{i_level}.b{i_block}", lv.block[i_block], h)
-                h = self._maybe_attn(f"dec.u{i_level}", lv.attn, i_block, h)
-            if i_level != 0:
-                h = self._up(f"dec.u{i_level}.up", lv.upsample, h)
-        out = torch.empty((h.shape[0], dec.conv_out.out_channels, h.shape[1], h.shape[2]), dtype=torch.float32, device=h.device)
-        n = dec.norm_out
-        return ops.conv_out(h, n.weight, n.bias, n.eps, n.num_groups, self._out_w[id(dec.conv_out)], dec.conv_out.bias, out, self._chan_stats(h))
+        self._conv(self._packed[id(ci)], self._norm16(None, 0, zp, kind="z16"), h)
+        return self._walk("decoder", h)
 
     # ------------------------------------------------------------------------------------------------ the reference's surface
     @torch.no_grad()

@@ -39,19 +39,6 @@ def rel(a, b):
     return float((a - b).abs().max()) / (float(b.std()) + 1e-12)
 
 
-def test_state_dict_names_match_reference_layout():
-    """same names / shapes as ldm.models.autoencoder.VQModelInterface's state dict (vq-f4.ckpt loads with load_state_dict)"""
-    from oracle import vq as ovq
-    from stedm_amd.vq import VQModelInterface
-    m = VQModelInterface(embed_dim=3, n_embed=8192, ddconfig=DD_F4, lossconfig={"target": "torch.nn.Identity"})
-    sh = ovq.shapes(ovq.VQConfig())
-    sd = m.state_dict()
-    assert set(sd) == set(sh)
-    for k, v in sd.items():
-        assert tuple(v.shape) == tuple(sh[k]), k
-    assert not any(p.requires_grad for p in m.parameters())
-
-
 @pytest.mark.parametrize("e_dim,n_e,B,H", [(3, 8192, 2, 32), (4, 8192, 3, 16), (3, 100, 1, 8)])
 def test_nearest_codebook_indices_bit_exact(dev, e_dim, n_e, B, H):
     """integer result: indices equal the oracle's (pinned-down fp32 arithmetic, first index on ties) bit for bit, incl. duplicated

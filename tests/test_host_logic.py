@@ -1,5 +1,9 @@
 """CPU tier: product host logic (schedules, DDIM tables, module surface) against the reference's golden vectors."""
+import json
+import os
+
 import numpy as np
+import pytest
 import torch
 
 from stedm_amd import schedule as sch
@@ -228,3 +232,68 @@ def test_bench_dump_outputs_caps_size_with_a_seeded_row_sample(tmp_path):
     rows = x1[:, 0, 0, 0].astype(np.int64) // (4 * 32 * 32)
     assert np.all(np.diff(rows) > 0) and np.array_equal(p1, -x1)
     assert np.array_equal(x1, np.load(tmp_path / "big2" / "x_prev.npy"))
+
+
+# the first stage's state-dict contract (stedm_amd.vq.first_stage_layout): the ddconfigs of tests/golden/make_golden_vq.py::NAME_CASES
+DD_TINY = dict(double_z=False, z_channels=3, resolution=64, in_channels=3, out_ch=3, ch=32, ch_mult=[1, 2, 4], num_res_blocks=1,
+               attn_resolutions=[], dropout=0.0)
+VQ_NAME_CASES = {
+    "tiny": DD_TINY,
+    "f4": dict(DD_TINY, ch=128, num_res_blocks=2, resolution=512),
+    "attn16": dict(DD_TINY, attn_resolutions=[16]),
+    "attn_all": dict(DD_TINY, ch_mult=[1, 2], num_res_blocks=2, attn_resolutions=[64, 32]),
+    "double_z": dict(DD_TINY, double_z=True, z_channels=4),
+    "one_level": dict(DD_TINY, ch_mult=[2]),
+    "mult4": dict(DD_TINY, ch_mult=[1, 1, 2, 2], num_res_blocks=2, z_channels=4, in_channels=1, out_ch=1),
+    "attn_none": dict(DD_TINY, attn_type="none"),
+}
+
+
+@pytest.mark.parametrize("case", list(VQ_NAME_CASES))
+def test_vq_state_dict_equals_reference_names_in_order(case):
+    """encoder.* / decoder.* of VQModelInterface.state_dict(): the names, shapes and ORDER of the reference's own Encoder(**dd) /
+    Decoder(**dd) (f15_vq_names.json, written by make_golden_vq.py), then the quantiser and the two 1x1 glue convs; all frozen."""
+    from stedm_amd.vq import VQModelInterface
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f15_vq_names.json")) as f:
+        fx = json.load(f)
+    assert list(fx) == list(VQ_NAME_CASES)
+    dd = VQ_NAME_CASES[case]
+    assert fx[case]["ddconfig"] == dd
+    want = [(k, tuple(shape)) for k, shape in fx[case]["params"]]
+    assert 90 <= len(want) <= 252
+    m = VQModelInterface(embed_dim=3, n_embed=64, ddconfig=dd, lossconfig={"target": "torch.nn.Identity"})
+    got = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
+    halves = [e for e in got if e[0].startswith(("encoder.", "decoder."))]
+    assert halves == want
+    assert [k for k, _ in got if not k.startswith(("encoder.", "decoder."))] == [
+        "quantize.embedding.weight", "quant_conv.weight", "quant_conv.bias", "post_quant_conv.weight", "post_quant_conv.bias"]
+    assert got[:len(want)] == want                        # the halves come first, the glue after them
+    assert [k for k, _ in m.named_parameters()] == [k for k, _ in got]
+    assert all(p.dtype == torch.float32 and not p.requires_grad for p in m.parameters())
+    assert m.encoder.num_resolutions == len(dd["ch_mult"])
+
+
+def test_state_dict_names_match_reference_layout():
+    """same names / shapes as ldm.models.autoencoder.VQModelInterface's state dict (vq-f4.ckpt loads with load_state_dict); ties the
+    oracle's restatement (oracle.vq.shapes) to the product"""
+    from oracle import vq as ovq
+    from stedm_amd.vq import VQModelInterface
+    m = VQModelInterface(embed_dim=3, n_embed=8192, ddconfig=VQ_NAME_CASES["f4"], lossconfig={"target": "torch.nn.Identity"})
+    sh = ovq.shapes(ovq.VQConfig())
+    sd = m.state_dict()
+    assert set(sd) == set(sh)
+    for k, v in sd.items():
+        assert tuple(v.shape) == tuple(sh[k]), k
+    assert not any(p.requires_grad for p in m.parameters())
+
+
+@pytest.mark.parametrize("option,named", [
+    (dict(resamp_with_conv=False), "resamp_with_conv"), (dict(use_linear_attn=True), "use_linear_attn"), (dict(attn_type="linear"), "attn_type"),
+    (dict(attn_type="flash"), "attn_type"), (dict(give_pre_end=True), "give_pre_end"), (dict(tanh_out=True), "tanh_out"),
+    (dict(dropout=0.1), "dropout")])
+def test_vq_refuses_unsupported_ddconfig_options_at_construction(option, named):
+    """options of the reference's Encoder / Decoder that the HIP first stage does not cover are refused when the model is built (CPU, no
+    device work yet), by name; attn_type="none" is not one of them (VQ_NAME_CASES)"""
+    from stedm_amd.vq import VQModelInterface
+    with pytest.raises(NotImplementedError, match=named):
+        VQModelInterface(embed_dim=3, n_embed=64, ddconfig=dict(DD_TINY, **option), lossconfig={"target": "torch.nn.Identity"})
