@@ -11,9 +11,27 @@ using namespace stedm;
 
 namespace {
 
+// sigmoid(y) / down, with down = 2^-32 below y = -64 and 1 elsewhere. v_rcp_f32 flushes a denormal result and v_exp_f32 overflows past
+// 88.7, so the plain rcp(1 + exp(-y)) is 0 below y = -87.3, where y * sigmoid(y) and silu'(y) are still normal numbers (down to y = -92.5).
+// Scaling the denominator by a power of two keeps the reciprocal normal down to y = -110 and changes no bit for y >= -64.
+__device__ __forceinline__ float sigmoid_up(float y, float& down) {
+  const bool tail = y < -64.0f;
+  down = tail ? 0x1p-32f : 1.0f;
+  const float e = __builtin_amdgcn_exp2f(fmaf(-y, 1.44269504088896340736f, tail ? -32.0f : 0.0f));   // exp(-y) * down
+  return __builtin_amdgcn_rcpf(down + e);
+}
+
+// y * sigmoid(y), accurate in the negative tail too (common.hpp's silu_f, which the fused forward epilogues use, flushes to 0 there)
+__device__ __forceinline__ float silu_tail_f(float y) {
+  float down;
+  const float su = sigmoid_up(y, down);
+  return (y * su) * down;
+}
+
 __device__ __forceinline__ float silu_grad(float y) {
-  const float s = __builtin_amdgcn_rcpf(1.0f + __expf(-y));
-  return s * (1.0f + y * (1.0f - s));
+  float down;
+  const float su = sigmoid_up(y, down);
+  return (su * (1.0f + y * (1.0f - su * down))) * down;
 }
 
 // ------------------------------------------------------------------------------------------------ GroupNorm statistics
@@ -847,7 +865,7 @@ __global__ void gemm_f32_reduce_kernel(const float* __restrict__ part, int ks, f
 __global__ void silu_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ out, long n, int mode) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  out[i] = mode == 0 ? silu_f(x[i]) : dy[i] * silu_grad(x[i]);
+  out[i] = mode == 0 ? silu_tail_f(x[i]) : dy[i] * silu_grad(x[i]);
 }
 
 // y = alpha * x + beta * y (gradient accumulation over micro-batches: accumulate_grad_batches of the reference's Trainer)
