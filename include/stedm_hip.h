@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 18
+#define STEDM_ABI_VERSION 19
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -735,6 +735,19 @@ int stedm_image_to_uint8(const float* x, unsigned char* out, int B, int C, int H
 int stedm_seg_merge(const float* seg, float* out, int B, int K, int H, int W, void* stream);
 /* modules/ldm_diffusion.py:98: torch.argmax(segmentation, dim=-1).astype(uint8): seg [N][ncls] fp32 -> out [N] (first maximum). */
 int stedm_argmax_u8(const float* seg, unsigned char* out, long N, int ncls, void* stream);
+
+/* ---- patch-distributed first stage (ABI 19): ddpm.py:567-654, 709-766, 829-866 (`split_input_params`); host plan in stedm_amd/tiling.py ----
+ * Crops of kh x kw at steps (sy, sx) over an H x W input: Ly = (H - kh) / sy + 1, Lx likewise, crop l = ly * Lx + lx (nn.Unfold's order).
+ * Gathers crops l0 .. l0+nl-1 of x [B][C][H][W] fp32 into tiles [nl][B][C][kh][kw] (crop-major: a run of crops is one contiguous first-stage
+ * batch). Copies only: bit-exact. */
+int stedm_unfold_tiles(const float* x, float* tiles, int B, int C, int H, int W, int kh, int kw, int sy, int sx, int l0, int nl, void* stream);
+/* Stitches tiles [Ly*Lx][B][C][th][tw] (the first stage's outputs) into out [B][C][Ho][Wo], Ho = (Ly-1)*sy + th, Wo = (Lx-1)*sx + tw:
+ *   out[b][c][Y][X] = sum_l o[l][b][c][Y - ly*sy][X - lx*sx] * (w_tile[y][x] * w_tie[l]) / sum_l (w_tile[y][x] * w_tie[l])
+ * over the crops l covering (Y, X), in ascending (ly, lx): no atomics, deterministic. w_tile [th][tw], w_tie [Ly*Lx] fp32. out_u8 (may be
+ * NULL): [B][Ho][Wo][C], stedm_image_to_uint8's conversion of the same value taken from the register; out may be NULL when out_u8 is given.
+ * A stride larger than the tile (pixels no crop covers) is refused. */
+int stedm_fold_blend(const float* tiles, const float* w_tile, const float* w_tie, float* out, unsigned char* out_u8, int B, int C, int th, int tw,
+                     int sy, int sx, int Ly, int Lx, void* stream);
 
 /* ---- HIP graph capture helpers (plumbing for the sampling loop) ---------------------------- */
 int stedm_graph_begin(void* stream);

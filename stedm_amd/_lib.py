@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 
@@ -165,6 +165,8 @@ SIGNATURES = {
     "stedm_image_to_uint8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "stedm_seg_merge": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "stedm_argmax_u8": (_I, [_P, _P, C.c_long, _I, _P]),
+    "stedm_unfold_tiles": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "stedm_fold_blend": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "stedm_graph_begin": (_I, [_P]),
     "stedm_graph_end": (_I, [_P, C.POINTER(C.c_void_p)]),
     "stedm_graph_launch": (_I, [_P, _P]),

@@ -27,6 +27,7 @@ from .ddim import DDIMSampler
 from .dpm_solver import DPMSolverSampler
 from .plms import PLMSSampler
 from .schedule import POSTERIOR_BUFFERS, NoiseSchedule, PosteriorSchedule
+from .tiling import TilePlan, fold_blend_cpu, image_to_uint8_cpu, unfold_tiles_cpu
 from .unet import UNetModel
 
 SAMPLERS = ("ddim", "dpm_solver", "plms")          # sample_log / predict_latents(sampler=...)
@@ -241,12 +242,22 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def apply_model(self, x_noisy, t, cond, return_ids=False, out=None, uniform_t=False):
         """ddpm.py:894-903 + 989-995. uniform_t: all entries of t are equal (the DDIM loop, ddim.py:141)."""
+        self._refuse_tiled_unet()
         return self.model(x_noisy, t, **self._as_cond_dict(cond), out=out, uniform_t=uniform_t)
 
     @torch.no_grad()
     def apply_model_cfg(self, x_noisy, t, cond, uncond, out=None, uniform_t=False):
         """(e_t, e_t_uncond) of ddim.py:177-178 in one pass (see UNetModel.forward_cfg)."""
+        self._refuse_tiled_unet()
         return self.model.forward_cfg(x_noisy, t, self._as_cond_dict(cond), self._as_cond_dict(uncond), out=out, uniform_t=uniform_t)
+
+    def _refuse_tiled_unet(self):
+        """ddpm.py:905-906: with `split_input_params` set the reference tiles the U-Net call too and asserts a single conditioning entry;
+        STEDM's hybrid conditioning has two, and a tiled U-Net is not built."""
+        if getattr(self, "split_input_params", None) is not None:
+            raise NotImplementedError("apply_model with split_input_params set: the reference's tiled U-Net call asserts len(cond) == 1 "
+                                      "(ddpm.py:906) and hybrid conditioning has two entries; to tile the first stage only, pass split= to "
+                                      "decode_first_stage / encode_first_stage instead of setting the attribute")
 
     # ------------------------------------------------------------------------------------------ training-side forward values
     @torch.no_grad()
@@ -338,11 +349,78 @@ class LatentDiffusion(nn.Module):
             out.append(xc)
         return out
 
-    def encode_first_stage(self, x):
-        """ddpm.py:828-866 (no fold/unfold tiling: `split_input_params` is never set)."""
+    def encode_first_stage(self, x, split=None, tile_batch=None):
+        """ddpm.py:828-866. split (a dict with the reference's `split_input_params` keys) or, when it is None, the attribute
+        `split_input_params` set by the caller selects the patch-distributed path while its `patch_distributed_vq` is true: overlapping
+        crops of ks / stride IMAGE pixels are encoded `tile_batch` crops at a time and blended (_tiled_first_stage). Neither: one call."""
         if self.first_stage_model is None:
             raise StedmHipError("no first stage: latents cannot be produced from images (pass first_stage_config)")
-        return self.first_stage_model.encode(x)
+        params = self._split_params(split)
+        if params is None:
+            return self.first_stage_model.encode(x)
+        if split is None:
+            self.split_input_params['original_image_size'] = x.shape[-2:]       # ddpm.py:835
+        return self._tiled_first_stage(x, params, True, tile_batch)
+
+    # ------------------------------------------------------------------------------------------ patch-distributed first stage
+    def _split_params(self, split):
+        """the dict that drives the tiled path, or None for the one-call path (ddpm.py:718-719, 830-831)"""
+        params = split if split is not None else getattr(self, "split_input_params", None)
+        if params is None or not params["patch_distributed_vq"]:
+            return None
+        return params
+
+    @torch.no_grad()
+    def _tiled_first_stage(self, x, params, encode: bool, tile_batch=None, out_u8: bool = False):
+        """ddpm.py:720-755 / 832-861: unfold -> first stage over the crops -> weighted fold / normalisation, with the crops run as batches of
+        `tile_batch` crops x B samples (the reference runs one call per crop). tile_batch None: TilePlan.default_tile_batch, which keeps one
+        call within tiling.CALL_LATENT_PIXELS (16 latents of 128 x 128: half of what the VQ-f4 decoder's 32-bit plane offsets admit). The plan refuses unusable settings before any device work.
+        Works with any first stage exposing `.encode` / `.decode` on NCHW fp32. GPU tensors run the HIP kernels (ops.unfold_tiles,
+        ops.fold_blend); other tensors the same plan in torch (tiling.unfold_tiles_cpu, fold_blend_cpu)."""
+        x = x.float().contiguous()
+        B, _, h, w = x.shape
+        plan = TilePlan.from_split(params, h, w, encode)
+        nb = plan.default_tile_batch(B) if tile_batch is None else int(tile_batch)
+        if nb < 1:
+            raise ValueError(f"tile_batch must be at least 1, got {tile_batch}")
+        fs = self.first_stage_model
+        run = fs.encode if encode else fs.decode
+        gpu = x.is_cuda
+        th, tw = plan.tile
+        # a stage whose arithmetic depends on the batch of a call (VQModelInterface: split-K by launch size) is asked for its batch-invariant
+        # mode, so that the result does not depend on tile_batch
+        switch = isinstance(getattr(fs, "batch_invariant", None), bool) and not fs.batch_invariant
+        if switch:
+            fs.batch_invariant = True
+        try:
+            stack = self._run_crops(x, plan, run, nb, gpu, params)
+        finally:
+            if switch:
+                fs.batch_invariant = False
+        if gpu:
+            w_tile, w_tie = plan.weights(x.device)
+            out, out8 = ops.fold_blend(stack, w_tile, w_tie, plan.out_stride, (plan.Ly, plan.Lx), want_f32=not out_u8, want_u8=out_u8)
+            return out8 if out_u8 else out
+        out = fold_blend_cpu(stack, plan)
+        return image_to_uint8_cpu(out) if out_u8 else out
+
+    @staticmethod
+    def _run_crops(x, plan, run, nb, gpu, params):
+        """the first stage over the crops of x, nb crops per call -> the tile stack [L, B, C, th, tw]"""
+        B = x.shape[0]
+        th, tw = plan.tile
+        stack = None
+        for l0 in range(0, plan.L, nb):
+            nl = min(nb, plan.L - l0)
+            crops = ops.unfold_tiles(x, plan.ks, plan.stride, l0, nl) if gpu else unfold_tiles_cpu(x, plan, l0, nl)
+            o = run(crops.view((nl * B,) + tuple(crops.shape[2:])))
+            if o.dim() != 4 or o.shape[0] != nl * B or tuple(o.shape[2:]) != (th, tw):
+                raise StedmHipError(f"tiled first stage: crops of {plan.ks} gave {tuple(o.shape)}, the plan (vqf = {params['vqf']}) expects "
+                                    f"[{nl * B}, C, {th}, {tw}]")
+            if stack is None:
+                stack = torch.empty((plan.L, B, o.shape[1], th, tw), dtype=torch.float32, device=x.device)
+            stack[l0:l0 + nl].copy_(o.view(nl, B, o.shape[1], th, tw))
+        return stack
 
     def get_first_stage_encoding(self, encoder_posterior):
         """ddpm.py:537-544: the VQ interface returns the latent tensor itself."""
@@ -625,11 +703,22 @@ class LatentDiffusion(nn.Module):
         shape = (self.channels, self.image_size, self.image_size)
         return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
 
-    def decode_first_stage(self, z, **kw):
+    def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False, split=None, tile_batch=None, out_u8=False, **kw):
+        """ddpm.py:708-766 (predict_cids / force_not_quantize are accepted and ignored, as before). split / the attribute
+        `split_input_params` with `patch_distributed_vq` true: the patch-distributed path over crops of ks / stride LATENT pixels
+        (_tiled_first_stage; see encode_first_stage). out_u8: return predict_step's uint8 image [B,H,W,C] (images_for_saving's conversion)
+        instead of the fp32 one; on the tiled path it comes out of the blend kernel's registers, no fp32 image is written."""
         if self.first_stage_model is None:
             raise NotImplementedError("decode_first_stage: this LatentDiffusion was built without a first stage; pass first_stage_config "
                                       "(built as stedm_amd.vq.VQModelInterface) or a first_stage module")
-        return self.first_stage_model.decode(z / self.scale_factor)
+        params = self._split_params(split)
+        if params is not None:
+            return self._tiled_first_stage(1. / self.scale_factor * z, params, False, tile_batch, out_u8=out_u8)
+        dec = self.first_stage_model.decode(z / self.scale_factor)
+        if out_u8:
+            dec = dec.float().contiguous()
+            return ops.image_to_uint8(dec) if dec.is_cuda else image_to_uint8_cpu(dec)
+        return dec
 
 
 class S_ZSS_DM(LatentDiffusion):
@@ -901,6 +990,6 @@ def images_for_saving(decoded: torch.Tensor, segmentation_nhwc: Optional[torch.T
     """The array work of predict_step after decode_first_stage (modules/ldm_diffusion.py:93-99): decoded [B,3,H,W] fp32 -> uint8
     [B,H,W,3] (clip to [-1,1], scale, truncate), segmentation [B,H,W,ncls] -> uint8 class map. Returned on the device; PNG
     encoding stays with the caller."""
-    img = ops.image_to_uint8(decoded.float().contiguous())
+    img = None if decoded is None else ops.image_to_uint8(decoded.float().contiguous())       # None: the caller has the uint8 image already
     seg = None if segmentation_nhwc is None else ops.argmax_u8(segmentation_nhwc.float().contiguous())
     return img, seg

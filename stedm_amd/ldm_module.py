@@ -131,7 +131,9 @@ class LDM_Diffusion(_Base):
         selects PLMS (stedm_amd/plms.py), DDIM's schedule with n + 1 model evaluations for n iterations. "ddpm" runs the reference's
         ancestral chain (stedm_amd/ancestral.py: model.num_timesteps unguided steps, ddim_steps ignored; cfg_scale must then be 1).
         The optional mapping `dpm_solver` (with sampler "dpm_solver") holds DPM-Solver options (latent_diffusion.DPM_OPTIONS, e.g.
-        {order: 3} or {method: singlestep, order: 3}); configs without it run exactly as before."""
+        {order: 3} or {method: singlestep, order: 3}); configs without it run exactly as before. The optional mapping `first_stage_split`
+        (the reference's `split_input_params` keys: ks, stride, vqf, patch_distributed_vq, clip_*_weight, tie_braker, clip_*_tie_weight; ks
+        and stride in latent pixels) decodes the latents over overlapping crops (LatentDiffusion.decode_first_stage(split=...))."""
         cfg = self._cfg
         ldm_batch = self.prepare_batch(batch)
         sname = cfg.style_sampling["name"] if isinstance(cfg.style_sampling, dict) else cfg.style_sampling.name
@@ -139,8 +141,13 @@ class LDM_Diffusion(_Base):
         extra = {} if dpm is None else {"dpm_solver": dict(dpm.items() if hasattr(dpm, "items") else vars(dpm).items())}
         lat = predict_latents(self._model, ldm_batch, ddim_steps=cfg.ddim_steps, eta=cfg.eta, cfg_scale=cfg.cfg_scale, style_sampling=sname,
                               sampler=getattr(cfg, "sampler", None) or "ddim", **extra)
-        dec = self._model.decode_first_stage(lat)
-        img, seg = images_for_saving(dec, ldm_batch["segmentation"])
+        split = getattr(cfg, "first_stage_split", None)
+        if split is None:
+            dec = self._model.decode_first_stage(lat)
+            img, seg = images_for_saving(dec, ldm_batch["segmentation"])
+        else:       # patch-distributed decode: the uint8 image comes straight out of the blend
+            img = self._model.decode_first_stage(lat, split=dict(split.items() if hasattr(split, "items") else vars(split).items()), out_u8=True)
+            _, seg = images_for_saving(None, ldm_batch["segmentation"])
         img, seg = img.cpu().numpy(), seg.cpu().numpy()
         if self.predict_dir is not None and len(batch) > 4:
             from PIL import Image

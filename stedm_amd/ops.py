@@ -1553,6 +1553,49 @@ def argmax_u8(seg: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------- patch-distributed first stage
+def unfold_tiles(x: torch.Tensor, ks: Tuple[int, int], stride: Tuple[int, int], l0: int = 0, nl: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """crops l0 .. l0+nl-1 (l = ly*Lx + lx, nn.Unfold's order; nl None: all that follow l0) of x [B,C,H,W] fp32 -> [nl,B,C,kh,kw]; see
+    stedm_unfold_tiles."""
+    _chk(x, name="x")
+    B, Cc, H, W = x.shape
+    (kh, kw), (sy, sx) = (int(ks[0]), int(ks[1])), (int(stride[0]), int(stride[1]))
+    if not (0 < kh <= H and 0 < kw <= W and sy > 0 and sx > 0):
+        raise ValueError(f"unfold_tiles: crop {kh} x {kw}, stride {sy} x {sx} over {H} x {W}")
+    L = ((H - kh) // sy + 1) * ((W - kw) // sx + 1)
+    nl = L - int(l0) if nl is None else int(nl)
+    if l0 < 0 or nl < 1 or l0 + nl > L:
+        raise ValueError(f"unfold_tiles: crops {l0} .. {l0 + nl - 1} outside 0 .. {L - 1}")
+    if out is None:
+        out = torch.empty((nl, B, Cc, kh, kw), dtype=torch.float32, device=x.device)
+    else:
+        _chk(out, name="out")
+        if tuple(out.shape) != (nl, B, Cc, kh, kw):
+            raise ValueError(f"unfold_tiles: out {tuple(out.shape)} != {(nl, B, Cc, kh, kw)}")
+    check(lib().stedm_unfold_tiles(x.data_ptr(), out.data_ptr(), B, Cc, H, W, kh, kw, sy, sx, int(l0), nl, _stream()), "stedm_unfold_tiles")
+    return out
+
+
+def fold_blend(tiles: torch.Tensor, w_tile: torch.Tensor, w_tie: torch.Tensor, stride: Tuple[int, int], grid: Tuple[int, int],
+               want_f32: bool = True, want_u8: bool = False):
+    """tiles [Ly*Lx,B,C,th,tw] fp32, w_tile [th,tw], w_tie [Ly*Lx], stride (sy, sx) and grid (Ly, Lx) in output pixels ->
+    (out [B,C,Ho,Wo] fp32 or None, out_u8 [B,Ho,Wo,C] uint8 or None); see stedm_fold_blend. out_u8 equals image_to_uint8(out) bit for bit."""
+    _chk(tiles, name="tiles"); _chk(w_tile, name="w_tile"); _chk(w_tie, name="w_tie")
+    L, B, Cc, th, tw = tiles.shape
+    (sy, sx), (Ly, Lx) = (int(stride[0]), int(stride[1])), (int(grid[0]), int(grid[1]))
+    if Ly < 1 or Lx < 1 or Ly * Lx != L or tuple(w_tile.shape) != (th, tw) or w_tie.numel() != L:
+        raise ValueError(f"fold_blend: tiles {tuple(tiles.shape)}, grid {Ly} x {Lx}, w_tile {tuple(w_tile.shape)}, w_tie {tuple(w_tie.shape)} disagree")
+    if not (want_f32 or want_u8):
+        raise ValueError("fold_blend: nothing to write (want_f32 or want_u8)")
+    Ho, Wo = (Ly - 1) * sy + th, (Lx - 1) * sx + tw
+    out = torch.empty((B, Cc, Ho, Wo), dtype=torch.float32, device=tiles.device) if want_f32 else None
+    out8 = torch.empty((B, Ho, Wo, Cc), dtype=torch.uint8, device=tiles.device) if want_u8 else None
+    check(lib().stedm_fold_blend(tiles.data_ptr(), w_tile.data_ptr(), w_tie.data_ptr(), _ptr(out), _ptr(out8), B, Cc, th, tw, sy, sx, Ly, Lx,
+                                 _stream()), "stedm_fold_blend")
+    return out, out8
+
+
 # ------------------------------------------------------------------------------------------- graphs
 class Graph:
     """hipGraph captured on the current torch stream (all buffers must be allocated beforehand)."""

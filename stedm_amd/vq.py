@@ -195,6 +195,7 @@ class VQModelInterface(nn.Module):
         if monitor is not None:
             self.monitor = monitor
         self.precision = Precision.parse(precision) if isinstance(precision, str) else precision
+        self.batch_invariant = False                  # True: encode / decode give a sample the same bits in every batch (see _ws)
         self._packed: Dict = {}
         self._pack_key = None
         self._bufs: Dict[Tuple, torch.Tensor] = {}
@@ -264,7 +265,9 @@ class VQModelInterface(nn.Module):
         return ((hi, lo), raw) if want_raw else (hi, lo)
 
     def _ws(self, nel):
-        if nel > (1 << 23):
+        # batch_invariant: no split-K workspace, so no convolution splits its K walk. The split is chosen from the number of tiles in the launch,
+        # i.e. from the batch; without it a sample's result does not depend on which other samples share its call.
+        if nel > (1 << 23) or self.batch_invariant:
             return None
         return self._buf("conv_ws", ((16 if nel <= (1 << 20) else (4 if nel <= (1 << 22) else 2)) * nel,))
 
