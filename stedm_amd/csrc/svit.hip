@@ -1185,7 +1185,8 @@ __global__ void spatial_rescale_kernel(const float* __restrict__ x, const float*
   const long b = i / ((long)Wo * Ho * cout);
   float acc = 0.f;
   for (int ci = 0; ci < cin; ++ci) {
-    // n stages of 2x2 box means == one f x f box mean, but keep the staged summation order of the reference
+    // n stages of 2x2 box means == one f x f box mean: the f * f values are added row-major in one chain and divided once (NOT the staged
+    // order of n halvings: for n >= 2 the two round differently; tests/refs_style.py bounds this loop against the fp64 box mean)
     float s = 0.f;
     const float* p = x + ((b * cin + ci) * H + (long)yo * f) * W + (long)xo * f;
     for (int dy = 0; dy < f; ++dy)

@@ -132,6 +132,9 @@ def test_swin_window_attention_kernel_vs_oracle(dev, H, W, shift):
 
 
 def test_swin_gather_kernels_vs_torch(dev):
+    """one shape per gather kernel in the f16 three-product mode, at 1e-5 / 1e-6. tests/test_gpu_style_kernels.py holds the same kernels against
+    plain references exactly or inside derived bounds: both dtypes, lo present and absent, odd sides, both lane widths of swin_ln, ld16 > dim,
+    hi-only output and the gated form."""
     from stedm_amd import ops
     from stedm_amd.ops import Precision
     prec = Precision.parse("parity")
