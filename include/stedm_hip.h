@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 19
+#define STEDM_ABI_VERSION 20
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -672,6 +672,21 @@ int stedm_ddpm_step(float* x, const float* eps, const float* table, const int32_
  * ws: 1024 doubles. */
 int stedm_l1_loss(const float* pred, const float* target, long n, float grad_scale, float* d_pred, double* ws, float* loss,
                   void* stream);
+/* ---- full diffusion objective (ABI 20): ddpm.py:1015-1048 with get_loss :282-295 ------------ */
+/* pred, target [B][n] fp32 (n = elements per sample), t [B] DEVICE int64 (trusted, as stedm_q_sample trusts it), logvar, lvlb [T] fp32.
+ *   ls_b = mean_i f(target - pred), f = |.| (kind 0, 'l1') or (.)^2 (kind 1, 'l2');   lv_b = logvar[t_b]
+ *   out[4] = { loss = l_simple_weight * loss_gamma + elbo_weight * loss_vlb,  loss_simple = mean_b ls_b,
+ *              loss_gamma = mean_b(ls_b exp(-lv_b) + lv_b),  loss_vlb = mean_b(lvlb[t_b] ls_b) }
+ *   d_pred[b][i] = c_b f'(pred - target) (NULL: skip), c_b = (l_simple_weight exp(-lv_b) + elbo_weight lvlb[t_b]) grad_scale / (B n) formed in
+ *              fp64 and narrowed once; f' = sign (0 at 0) or 2 d
+ *   d_logvar[k] = l_simple_weight grad_scale / B * sum_{b: t_b = k} (1 - ls_b exp(-logvar[k])) (NULL: skip): all T entries are written, those no
+ *              t_b names with 0; the sum runs over b in index order (no atomics: bitwise reproducible with duplicate timesteps)
+ * Sums are fp64 (per (sample, block) partials added in block order), every scalar is narrowed once. Two launches, shape-static: runs under
+ * graph capture. ws: ws_doubles >= B * (stedm_diffusion_loss_blocks(n) + 1) doubles. */
+int stedm_diffusion_loss_blocks(long n);
+int stedm_diffusion_loss(const float* pred, const float* target, const int64_t* t, const float* logvar, const float* lvlb, int B, long n,
+                         int T, int kind, double l_simple_weight, double elbo_weight, double grad_scale, float* d_pred, float* d_logvar,
+                         double* ws, long ws_doubles, float* out, void* stream);
 /* SpatialRescaler.channel_mapper weight gradient (encoders/modules.py:123-130 under autograd, cond_stage_trainable): x NCHW
  * [B][cin][H][W], d_out [B][cout][H>>n][W>>n] (= the c_concat slice of the U-Net's input gradient) -> dw [cout][cin]. ws: B*cin*cout floats. */
 int stedm_spatial_rescale_wgrad(const float* x, const float* d_out, float* ws, float* dw, int B, int cin, int cout, int H, int W,

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 
@@ -150,6 +150,8 @@ SIGNATURES = {
     "stedm_silu": (_I, [_P, _P, _P, C.c_long, _I, _P]),
     "stedm_q_sample": (_I, [_P, _P, _P, _P, _P, _P, _I, C.c_long, _P]),
     "stedm_l1_loss": (_I, [_P, _P, C.c_long, _F, _P, _P, _P, _P]),
+    "stedm_diffusion_loss_blocks": (_I, [C.c_long]),
+    "stedm_diffusion_loss": (_I, [_P, _P, _P, _P, _P, _I, C.c_long, _I, _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, C.c_long, _P, _P]),
     "stedm_spatial_rescale_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "stedm_axpby_f32": (_I, [_P, _P, C.c_long, _F, _F, _P]),
     "stedm_adamw_ema": (_I, [_P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P]),

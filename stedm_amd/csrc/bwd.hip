@@ -912,6 +912,83 @@ __global__ void l1_final_kernel(const double* __restrict__ part, int nb, double 
   }
 }
 
+// The reference's full objective (ddpm.py:1015-1048) on the eps prediction, pred / target [B][n]:
+//   ls_b = mean_i f(target - pred), f = |.| (kind 0) or (.)^2 (kind 1);  lv_b = logvar[t_b]
+//   loss = lsw * mean_b(ls_b exp(-lv_b) + lv_b) + ew * mean_b(lvlb[t_b] ls_b)
+// One pass: d_pred[b][i] = c_b f'(pred - target) with c_b = (lsw exp(-lv_b) + ew lvlb[t_b]) gscale / (B n) formed in fp64 and narrowed once (it does
+// not depend on the sums); f' = sign (0 at 0) or 2 d. blockIdx.y = sample, blockIdx.x strides over its n elements; fp64 partial per (sample, block).
+constexpr int DL_THREADS = 256;
+constexpr int DL_ELEMS = 1024;        // elements per block before the stride loop goes round again
+constexpr int DL_MAX_BLOCKS = 64;     // blocks per sample
+static int dl_blocks(long n) {
+  const long b = (n + DL_ELEMS - 1) / DL_ELEMS;
+  return (int)(b > DL_MAX_BLOCKS ? DL_MAX_BLOCKS : b);
+}
+__global__ void __launch_bounds__(DL_THREADS) diffusion_loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                                            const int64_t* __restrict__ t, const float* __restrict__ logvar,
+                                                                            const float* __restrict__ lvlb, float* __restrict__ dpred, long n, int kind,
+                                                                            double lsw, double ew, double gscale, double* __restrict__ part) {
+  __shared__ double red[DL_THREADS];
+  const int b = blockIdx.y;
+  const long base = (long)b * n;
+  float cb = 0.f;
+  if (dpred) {
+    const int64_t tb = t[b];
+    cb = (float)((lsw * exp(-(double)logvar[tb]) + ew * (double)lvlb[tb]) * gscale / ((double)gridDim.y * (double)n));
+  }
+  double s = 0.0;
+  for (long i = (long)blockIdx.x * DL_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * DL_THREADS) {
+    const double dd = (double)pred[base + i] - (double)target[base + i];       // exact; (float)dd is the fp32 difference
+    const float d = (float)dd;
+    s += kind == 0 ? fabs(dd) : dd * dd;
+    if (dpred) dpred[base + i] = kind == 0 ? (d > 0.f ? cb : (d < 0.f ? -cb : 0.f)) : (2.f * d) * cb;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = DL_THREADS / 2; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = red[0];
+}
+// Finishing launch (one block): ls_b from the partials in block order, the four scalars in fp64 (narrowed once each), and
+//   d_logvar[k] = lsw gscale / B * sum_{b: t_b = k} (1 - ls_b exp(-logvar[k])), b in index order (no atomics: duplicates in t are the normal case);
+// every one of the T entries is written, those no t_b names with 0.
+__global__ void __launch_bounds__(DL_THREADS) diffusion_loss_final_kernel(const double* __restrict__ part, int nbs, const int64_t* __restrict__ t,
+                                                                          const float* __restrict__ logvar, const float* __restrict__ lvlb, int B, int T,
+                                                                          long n, double lsw, double ew, double gscale, double* __restrict__ ls,
+                                                                          float* __restrict__ d_logvar, float* __restrict__ out) {
+  for (int b = threadIdx.x; b < B; b += DL_THREADS) {
+    double s = 0.0;
+    for (int j = 0; j < nbs; ++j) s += part[(long)b * nbs + j];
+    ls[b] = s / (double)n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, g = 0.0, v = 0.0;
+    for (int b = 0; b < B; ++b) {
+      const int64_t tb = t[b];
+      const double lv = (double)logvar[tb];
+      a += ls[b];
+      g += ls[b] * exp(-lv) + lv;
+      v += (double)lvlb[tb] * ls[b];
+    }
+    a /= (double)B; g /= (double)B; v /= (double)B;
+    out[0] = (float)(lsw * g + ew * v);
+    out[1] = (float)a;
+    out[2] = (float)g;
+    out[3] = (float)v;
+  }
+  if (!d_logvar) return;
+  for (int k = threadIdx.x; k < T; k += DL_THREADS) {
+    double acc = 0.0, e = 0.0;
+    bool hit = false;
+    for (int b = 0; b < B; ++b) {
+      if (t[b] != (int64_t)k) continue;
+      if (!hit) { e = exp(-(double)logvar[k]); hit = true; }
+      acc += 1.0 - ls[b] * e;
+    }
+    d_logvar[k] = hit ? (float)(lsw * gscale / (double)B * acc) : 0.f;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ optimizer
 // AdamW (torch.optim.AdamW semantics) + LitEma (ema.py:25-44) over many tensors in one launch. table[t] = {p, g, m, v, ema, n};
 // chunk_tensor[blockIdx.x] / chunk_off[blockIdx.x] map a block to 4096 elements of one tensor.
@@ -1319,6 +1396,23 @@ extern "C" int stedm_l1_loss(const float* pred, const float* target, long n, flo
   const int nb = (int)((n + 256 * 16 - 1) / (256 * 16) < 1024 ? (n + 256 * 16 - 1) / (256 * 16) : 1024);
   l1_partial_kernel<<<nb, 256, 0, as_stream(stream)>>>(pred, target, d_pred, n, grad_scale / (float)n, ws);
   l1_final_kernel<<<1, 64, 0, as_stream(stream)>>>(ws, nb, 1.0 / (double)n, loss);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int stedm_diffusion_loss_blocks(long n) { return n > 0 ? dl_blocks(n) : 0; }
+
+extern "C" int stedm_diffusion_loss(const float* pred, const float* target, const int64_t* t, const float* logvar, const float* lvlb, int B, long n, int T,
+                                    int kind, double l_simple_weight, double elbo_weight, double grad_scale, float* d_pred, float* d_logvar, double* ws,
+                                    long ws_doubles, float* out, void* stream) {
+  STEDM_CHECK_ARG(pred && target && t && logvar && lvlb && ws && out && B > 0 && B <= 65535 && n > 0 && T > 0 && (kind == 0 || kind == 1),
+                  "diffusion_loss: bad args");
+  const int nbs = dl_blocks(n);
+  STEDM_CHECK_ARG(ws_doubles >= (long)B * (nbs + 1), "diffusion_loss: ws needs B * (stedm_diffusion_loss_blocks(n) + 1) doubles");
+  diffusion_loss_partial_kernel<<<dim3(nbs, B), DL_THREADS, 0, as_stream(stream)>>>(pred, target, t, logvar, lvlb, d_pred, n, kind, l_simple_weight,
+                                                                                     elbo_weight, grad_scale, ws);
+  diffusion_loss_final_kernel<<<1, DL_THREADS, 0, as_stream(stream)>>>(ws, nbs, t, logvar, lvlb, B, T, n, l_simple_weight, elbo_weight, grad_scale,
+                                                                        ws + (long)B * nbs, d_logvar, out);
   STEDM_LAUNCH_CHECK();
   return 0;
 }

@@ -26,7 +26,7 @@ from .ancestral import AncestralSampler
 from .ddim import DDIMSampler
 from .dpm_solver import DPMSolverSampler
 from .plms import PLMSSampler
-from .schedule import POSTERIOR_BUFFERS, NoiseSchedule, PosteriorSchedule
+from .schedule import POSTERIOR_BUFFERS, NoiseSchedule, PosteriorSchedule, lvlb_weights
 from .tiling import TilePlan, fold_blend_cpu, image_to_uint8_cpu, unfold_tiles_cpu
 from .unet import UNetModel
 
@@ -121,7 +121,8 @@ class DiffusionWrapper(nn.Module):
 
 
 class _HipTrainingLoss(torch.autograd.Function):
-    """`loss = p_losses(...)` with a grad_fn: forward runs the HIP U-Net forward (tape kept by the trainer) and the L1 loss kernel,
+    """`loss = p_losses(...)` with a grad_fn: forward runs the HIP U-Net forward (tape kept by the trainer) and the loss kernel of the
+    model's objective (a learned logvar's gradient lands in its slot of the trainer's gradient arena),
     backward runs the hand-scheduled HIP backward and ACCUMULATES into every parameter's `.grad` (autograd's contract: several
     `loss.backward()` between two `zero_grad()` sum up — Lightning's accumulate_grad_batches relies on it). c_concat / c_crossattn
     receive their gradients as ordinary autograd inputs, so a conditioning module that runs under autograd upstream (e.g. a
@@ -133,11 +134,12 @@ class _HipTrainingLoss(torch.autograd.Function):
         with torch.no_grad():
             x_noisy = ld.q_sample(x_start, t, noise)
             pred = tr.forward(x_noisy, c_concat.float().contiguous(), t, c_crossattn.float().contiguous())
-            loss = tr._buf("loss", (1,))
             dpred = tr._buf(f"dpred.{tuple(pred.shape)}", tuple(pred.shape))
-            ops.l1_loss(pred, noise.float().contiguous(), dpred, tr._buf("loss.ws", (1024,), torch.float64), loss)
+            obj = ld._objective()
+            loss = tr.loss(pred, noise, t, obj, dpred)
         tr._fwd_token = getattr(tr, "_fwd_token", 0) + 1
         ctx.ld, ctx.token, ctx.dpred, ctx.nx, ctx.cond_input = ld, tr._fwd_token, dpred, x_noisy.shape[1], cond_input
+        ctx.obj = obj
         return loss[0].clone()
 
     @staticmethod
@@ -149,8 +151,10 @@ class _HipTrainingLoss(torch.autograd.Function):
         with torch.no_grad():
             had = tr.internal_grads()
             dx, dctx = tr.backward(ctx.dpred * g)
+            if ctx.obj.learned:
+                tr._logvar_slot(ctx.obj).mul_(g)          # written by the forward's loss kernel for an upstream gradient of 1
             cs = ld.cond_stage_model
-            if tr.extra_params and ctx.cond_input is not None and hasattr(cs, "backward"):
+            if ld._cond_stage_in_optimizer() and ctx.cond_input is not None and hasattr(cs, "backward"):
                 cs.backward(ctx.cond_input, dx[:, ctx.nx:].contiguous())
             tr.publish_grads(1.0, accumulate=had)
             tr._ema_pending = True
@@ -165,9 +169,13 @@ class LatentDiffusion(nn.Module):
                  loss_type="l2", image_size=256, channels=3, conditioning_key=None, parameterization="eps",
                  cond_stage_config=None, first_stage_config=None, cond_stage_trainable=False, first_stage_key="image",
                  cond_stage_key="image", log_every_t=100, scale_factor=1.0, use_graph=False, use_ema=True, scale_by_std=False,
-                 l_simple_weight=1.0, original_elbo_weight=0.0, learn_logvar=False, clip_denoised=True, v_posterior=0., **ignored):
+                 l_simple_weight=1.0, original_elbo_weight=0.0, learn_logvar=False, logvar_init=0., clip_denoised=True, v_posterior=0.,
+                 **ignored):
         super().__init__()
-        assert parameterization == "eps", "the reference configs use eps-prediction"
+        if parameterization != "eps":
+            raise NotImplementedError(f"parameterization {parameterization!r}: every sampler and the training step are built for eps-prediction")
+        if loss_type not in ("l1", "l2"):
+            raise NotImplementedError(f"unknown loss type {loss_type!r} (ddpm.py:282-295 knows 'l1' and 'l2')")
         self.parameterization = parameterization
         self.image_size = image_size
         self.channels = channels
@@ -180,12 +188,11 @@ class LatentDiffusion(nn.Module):
             raise NotImplementedError("v_posterior != 0: no reference config sets it (ddpm.py:69 defaults to 0)")
         self.v_posterior = 0.
         self.loss_type = loss_type
-        if learn_logvar or original_elbo_weight != 0.0 or l_simple_weight != 1.0:
-            raise NotImplementedError("learn_logvar / original_elbo_weight / l_simple_weight: the reference configs keep the defaults "
-                                      "(logvar == 0, plain L1), nothing else is built")
+        self.l_simple_weight = float(l_simple_weight)              # ddpm.py:101-102, 1040-1045
+        self.original_elbo_weight = float(original_elbo_weight)
         self.scale_by_std = scale_by_std
         self.scale_factor = scale_factor
-        self.learn_logvar = False
+        self.learn_logvar = bool(learn_logvar)
         self.use_ema = use_ema          # ddpm.py:58,91-94: LitEma over `model`; the shadows live in the trainer (stedm_amd/train.py)
         self.use_scheduler = False      # ddpm.py:95: scheduler_config is absent from the reference configs
         self.restarted_from_ckpt = False
@@ -201,7 +208,9 @@ class LatentDiffusion(nn.Module):
             # silently dropped (a dropped first stage would make get_input hand all-zero latents to the training step)
             self.first_stage_model = instantiate_first_stage(first_stage_config)
         self.register_schedule(beta_schedule=beta_schedule, timesteps=timesteps, linear_start=linear_start, linear_end=linear_end)
-        self.register_buffer("logvar", torch.zeros(self.num_timesteps))
+        self.register_buffer("logvar", torch.full(fill_value=float(logvar_init), size=(self.num_timesteps,)))      # ddpm.py:115-117
+        if self.learn_logvar:
+            self.logvar = nn.Parameter(self.logvar, requires_grad=True)        # same state-dict key
 
     # ------------------------------------------------------------------------------------------ schedule
     def register_schedule(self, given_betas=None, beta_schedule="linear", timesteps=1000, linear_start=1e-4,
@@ -218,6 +227,9 @@ class LatentDiffusion(nn.Module):
         ps = PosteriorSchedule.make(timesteps, linear_start, linear_end, beta_schedule, v_posterior=getattr(self, "v_posterior", 0.))
         for name in POSTERIOR_BUFFERS:
             self.register_buffer(name, torch.from_numpy(getattr(ps, name).copy()), persistent=False)
+        # the weight of p_losses' variational-bound term (ddpm.py:162-172), non-persistent there too
+        self.register_buffer("lvlb_weights", torch.from_numpy(lvlb_weights(timesteps, linear_start, linear_end, beta_schedule,
+                                                                            v_posterior=getattr(self, "v_posterior", 0.))), persistent=False)
 
     @property
     def device(self):
@@ -269,16 +281,15 @@ class LatentDiffusion(nn.Module):
                             self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
 
     def p_losses(self, x_start, cond, t, noise=None, cond_input=None):
-        """ddpm.py:1015-1048 (loss_type l1 on the HIP loss kernel; logvar == 0, l_simple_weight 1, original_elbo_weight 0, so
-        loss == loss_simple). In training mode with autograd enabled the returned loss carries a grad_fn (`_HipTrainingLoss`):
+        """ddpm.py:1015-1048 on the HIP loss kernels: the whole objective (loss_type l1 / l2, logvar, l_simple_weight,
+        original_elbo_weight) through stedm_diffusion_loss, its plain point (l1, logvar == 0, weights 1 and 0: loss == loss_simple) through
+        stedm_l1_loss. In training mode with autograd enabled the returned loss carries a grad_fn (`_HipTrainingLoss`):
         `loss.backward()` runs the HIP backward, as autograd does for the reference in training_step (ddpm.py:345-358). Otherwise:
         the forward value only."""
         prefix = 'train' if self.training else 'val'
         if self.training and torch.is_grad_enabled():
             if t.is_floating_point():
                 raise TypeError("the training step takes integer timesteps (floating ones are DPM-Solver's inference path); got " + str(t.dtype))
-            if self.loss_type != 'l1':
-                raise NotImplementedError("the training step is built for loss_type 'l1' (conf/diffusion/ldm_based.yaml)")
             noise = torch.randn_like(x_start) if noise is None else noise
             cd = self._as_cond_dict(cond)
             cc, ca = cd["c_concat"], cd["c_crossattn"]
@@ -287,23 +298,60 @@ class LatentDiffusion(nn.Module):
             if cond_input is None:
                 cond_input = self.__dict__.get("_last_cond_input")      # left by get_input: the raw layout the cond stage saw
             tr = self._trainer_or_default()
-            if tr.extra_params and cond_input is None:
+            if self._cond_stage_in_optimizer() and cond_input is None:
                 raise ValueError("the cond stage is in the optimizer (cond_stage_trainable): its gradient needs the raw layout given to the "
                                  "cond stage — call get_input first or pass cond_input")
             loss = _HipTrainingLoss.apply(self._grad_anchor(x_start.device), xc, ctx, self, x_start.float().contiguous(),
                                           t.to(torch.int64).contiguous(), noise, cond_input)
-            return loss, {f"{prefix}/loss_simple": loss.detach(), f"{prefix}/loss": loss.detach()}
+            return loss, self._loss_dict(prefix, loss.detach(), tr.last_loss_terms)
         with torch.no_grad():
             noise = torch.randn_like(x_start) if noise is None else noise
             x_noisy = self.q_sample(x_start, t, noise)
             model_output = self.apply_model(x_noisy, t, cond)
-            if self.loss_type == 'l1':
+            obj = self._objective()
+            if obj.plain:
                 loss = ops.l1_loss(model_output.contiguous(), noise.float().contiguous(), None,
                                    torch.empty((1024,), dtype=torch.float64, device=x_noisy.device),
                                    torch.empty((1,), dtype=torch.float32, device=x_noisy.device))[0]
-            else:
-                loss = ((noise - model_output) ** 2).mean([1, 2, 3]).mean()
-        return loss, {f"{prefix}/loss_simple": loss, f"{prefix}/loss": loss}
+                return loss, self._loss_dict(prefix, loss, None)
+            terms = ops.diffusion_loss(model_output.contiguous(), noise.float().contiguous(), t.to(torch.int64).contiguous(), obj.logvar.detach(),
+                                       obj.lvlb, obj.kind, obj.l_simple_weight, obj.elbo_weight)
+        return terms[0], self._loss_dict(prefix, terms[0], terms)
+
+    def _objective(self):
+        """The objective as the trainer takes it (stedm_amd/train.py: Objective). Whether it is the plain point is decided once per
+        (logvar storage, version): a non-learned logvar that holds a nonzero (logvar_init, a loaded checkpoint) leaves it."""
+        from .train import Objective
+        lv = self.logvar
+        key = (self.loss_type, self.l_simple_weight, self.original_elbo_weight, self.learn_logvar, lv.data_ptr(), lv._version,
+               self.lvlb_weights.data_ptr())
+        hit = self.__dict__.get("_objective_cache")
+        if hit is None or hit[0] != key:
+            plain = (self.loss_type == 'l1' and self.l_simple_weight == 1.0 and self.original_elbo_weight == 0.0 and not self.learn_logvar
+                     and not bool(lv.detach().any()))
+            hit = (key, Objective(self.loss_type, self.l_simple_weight, self.original_elbo_weight, lv, self.lvlb_weights, self.learn_logvar, plain))
+            self.__dict__["_objective_cache"] = hit
+        return hit[1]
+
+    def _loss_dict(self, prefix: str, loss, terms) -> dict:
+        """p_losses' loss_dict (ddpm.py:1020-1046) from the loss kernel's {loss, loss_simple, loss_gamma, loss_vlb} (device values, no
+        host sync); terms None: the plain objective, whose loss is loss_simple."""
+        if terms is None:
+            return {f"{prefix}/loss_simple": loss, f"{prefix}/loss": loss}
+        terms = terms.detach().clone()            # (the trainer's buffer is overwritten by the next step)
+        d = {f"{prefix}/loss_simple": terms[1]}
+        if self.learn_logvar:
+            d[f"{prefix}/loss_gamma"] = terms[2]
+            d["logvar"] = self.logvar.data.mean()
+        d[f"{prefix}/loss_vlb"] = terms[3]
+        d[f"{prefix}/loss"] = terms[0]
+        return d
+
+    def _cond_stage_in_optimizer(self) -> bool:
+        """whether the trainer's extra parameters include the cond stage's (a learned logvar is one too, and needs no cond_input)"""
+        tr = self.__dict__.get("_trainer")
+        lv = self.logvar if self.learn_logvar else None
+        return tr is not None and any(p is not lv for p in tr.extra_params)
 
     def _grad_anchor(self, device) -> torch.Tensor:
         """a scalar that requires grad, so that the bridge node is part of the autograd graph (not a Parameter: it must stay out of
@@ -529,6 +577,10 @@ class LatentDiffusion(nn.Module):
         extra = []
         if self.cond_stage_trainable and self.cond_stage_model is not None and hasattr(self.cond_stage_model, "backward"):
             extra = [p for p in self.cond_stage_model.parameters() if p.requires_grad]
+        if self.learn_logvar:
+            # ddpm.py:1370-1372 / ldm_diffusion.py:228-229: appended after the cond stage's; no EMA shadow (LitEma covers `model` only). Its
+            # gradient is written by the loss kernel into its slot of the arena's tail: it accumulates and all-reduces with that bucket
+            extra.append(self.logvar)
         tr = UNetTrainer(self.model.diffusion_model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                          ema_decay=ema_decay if self.use_ema else None, accumulate_grad_batches=accumulate_grad_batches, extra_params=extra)
         self.__dict__["_trainer"] = tr
@@ -541,23 +593,21 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def p_losses_backward(self, x_start, cond, t, noise=None, cond_input=None):
         """p_losses (ddpm.py:1015-1048) followed by the backward pass autograd runs for the reference in training_step
-        (ddpm.py:345-358): loss_type l1, eps-parameterisation, logvar == 0. Fills `.grad` of the U-Net's parameters and returns
+        (ddpm.py:345-358): eps-parameterisation, the model's objective. Fills `.grad` of the U-Net's parameters (and of a learned logvar) and returns
         (loss, loss_dict, dL/dx_noisy over [x | c_concat], dL/dc_crossattn). With `cond_input` (the raw layout fed to the cond stage) the
         SpatialRescaler's channel-mapper gradient is filled too; the style encoder's backward is not built."""
-        if self.loss_type != 'l1':
-            raise NotImplementedError("the training step is built for loss_type 'l1' (conf/diffusion/ldm_based.yaml)")
         tr = self._trainer_or_default()
         noise = torch.randn_like(x_start) if noise is None else noise
         x_noisy = self.q_sample(x_start, t, noise)
         xc, ctx = self._split_cond(cond)
-        if tr.extra_params and cond_input is None:
+        if self._cond_stage_in_optimizer() and cond_input is None:
             raise ValueError("the cond stage is in the optimizer (cond_stage_trainable): pass cond_input (the raw layout given to the cond stage) so "
                              "that its gradient can be computed")
-        loss, dx, dctx = tr.loss_and_backward(x_noisy, xc, t, ctx, noise)
+        loss, dx, dctx = tr.loss_and_backward(x_noisy, xc, t, ctx, noise, objective=self._objective())
         if cond_input is not None and hasattr(self.cond_stage_model, "backward"):
             # cond_stage_trainable (s_zss_dm.py:46-48): the layout conditioner's channel mapper receives the c_concat slice of dL/dx
             self.cond_stage_model.backward(cond_input, dx[:, x_noisy.shape[1]:].contiguous())
-        return loss, {"train/loss_simple": loss, "train/loss": loss}, dx, dctx
+        return loss, self._loss_dict("train", loss, tr.last_loss_terms), dx, dctx
 
     def _split_cond(self, cond):
         cd = self._as_cond_dict(cond)
@@ -571,16 +621,16 @@ class LatentDiffusion(nn.Module):
         all-reduce when torch.distributed is initialised — what DDP does for train_diff.py:75) and runs AdamW; LitEma's update runs
         after every micro-batch (ddpm.py:369-371). Returns the loss (device tensor). graph=True: the U-Net's part of the step (forward, loss,
         backward, AdamW + EMA) is captured once and replayed as one hipGraph launch (UNetTrainer.train_step_graphed) when the step is
-        shape-static and self-contained — one rank, no accumulation, no trainable cond stage; the eager step runs otherwise."""
-        if self.loss_type != 'l1':
-            raise NotImplementedError("the training step is built for loss_type 'l1' (conf/diffusion/ldm_based.yaml)")
+        shape-static and self-contained — one rank, no accumulation, no trainable cond stage, no learned logvar (any other objective is
+        captured with the step); the eager step runs otherwise."""
         tr = self._trainer_or_default()
+        obj = self._objective()
         if t is None:
             t = torch.randint(0, self.num_timesteps, (x_start.shape[0],), device=x_start.device).long()
         noise = torch.randn_like(x_start) if noise is None else noise
         if cond_input is None:
             cond_input = self.__dict__.get("_last_cond_input")
-        if tr.extra_params and cond_input is None:
+        if self._cond_stage_in_optimizer() and cond_input is None:
             raise ValueError("the cond stage is in the optimizer (cond_stage_trainable): pass cond_input (the raw layout given to the cond stage) so "
                              "that its gradient can be computed")
         x_noisy = self.q_sample(x_start, t, noise)
@@ -592,8 +642,8 @@ class LatentDiffusion(nn.Module):
         if graph and after is None and not tr.extra_params and tr.accumulate_grad_batches == 1 and x_noisy.is_cuda:
             import torch.distributed as dist
             if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1):
-                return tr.train_step_graphed(x_noisy, xc, t, ctx, noise)
-        return tr.train_step(x_noisy, xc, t, ctx, noise, group=group, after_backward=after)
+                return tr.train_step_graphed(x_noisy, xc, t, ctx, noise, objective=obj)
+        return tr.train_step(x_noisy, xc, t, ctx, noise, group=group, after_backward=after, objective=obj)
 
     # ------------------------------------------------------------------------------------------ checkpoints (reference key layout)
     @staticmethod

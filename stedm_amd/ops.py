@@ -1413,6 +1413,46 @@ def l1_loss(pred: torch.Tensor, target: torch.Tensor, d_pred: Optional[torch.Ten
     return loss
 
 
+LOSS_KINDS = {"l1": 0, "l2": 1}
+
+
+def diffusion_loss_blocks(n: int) -> int:
+    """blocks per sample of stedm_diffusion_loss's first launch (256 threads each, striding over the sample's n elements)"""
+    return int(lib().stedm_diffusion_loss_blocks(int(n)))
+
+
+def diffusion_loss_ws_doubles(B: int, n: int) -> int:
+    return int(B) * (diffusion_loss_blocks(n) + 1)
+
+
+def diffusion_loss(pred: torch.Tensor, target: torch.Tensor, t: torch.Tensor, logvar: torch.Tensor, lvlb: torch.Tensor, kind,
+                   l_simple_weight: float = 1.0, elbo_weight: float = 0.0, grad_scale: float = 1.0, d_pred: Optional[torch.Tensor] = None,
+                   d_logvar: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's objective (ddpm.py:1015-1048) on pred / target [B, ...] (include/stedm_hip.h: stedm_diffusion_loss). kind: 'l1' / 'l2'
+    (or 0 / 1). -> out [4] = {loss, loss_simple, loss_gamma, loss_vlb}; d_pred (like pred) and d_logvar [T] are filled when given."""
+    _chk(pred, name="pred"); _chk(target, name="target"); _chk(t, torch.int64, "t"); _chk(logvar, name="logvar"); _chk(lvlb, name="lvlb")
+    B = pred.shape[0]
+    n = pred.numel() // B
+    T = logvar.numel()
+    assert pred.numel() == target.numel() == B * n and t.numel() == B and lvlb.numel() == T
+    need = diffusion_loss_ws_doubles(B, n)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.float64, device=pred.device)
+    if out is None:
+        out = torch.empty((4,), dtype=torch.float32, device=pred.device)
+    assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= need and out.dtype == torch.float32 and out.numel() >= 4
+    if d_pred is not None:
+        _chk(d_pred, name="d_pred")
+        assert d_pred.numel() == pred.numel()
+    if d_logvar is not None:
+        _chk(d_logvar, name="d_logvar")
+        assert d_logvar.numel() == T
+    check(lib().stedm_diffusion_loss(pred.data_ptr(), target.data_ptr(), t.data_ptr(), logvar.data_ptr(), lvlb.data_ptr(), B, n, T,
+                                     LOSS_KINDS.get(kind, kind), float(l_simple_weight), float(elbo_weight), float(grad_scale), _ptr(d_pred),
+                                     _ptr(d_logvar), ws.data_ptr(), ws.numel(), out.data_ptr(), _stream()), "stedm_diffusion_loss")
+    return out
+
+
 def spatial_rescale_wgrad(x: torch.Tensor, d_out: torch.Tensor, dw: torch.Tensor, n_stages: int, accumulate: bool = False) -> torch.Tensor:
     """channel_mapper weight gradient of the SpatialRescaler: x [B,cin,H,W], d_out [B,cout,H>>n,W>>n] -> dw [cout,cin(,1,1)]."""
     _chk(x, name="x"); _chk(d_out, name="d_out"); _chk(dw, name="dw")

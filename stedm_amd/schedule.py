@@ -123,3 +123,23 @@ def ddpm_step_table(sqrt_recip, sqrt_recipm1, coef1, coef2, log_var_clipped) -> 
     sigma[0] = 0.0
     cols = [as32(sqrt_recip), as32(sqrt_recipm1), as32(coef1), as32(coef2), sigma]
     return torch.stack(cols, dim=1).numpy().astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ training objective
+def lvlb_weights(timesteps: int = 1000, linear_start: float = 1e-4, linear_end: float = 2e-2, beta_schedule: str = "linear",
+                 v_posterior: float = 0.0) -> np.ndarray:
+    """`lvlb_weights` of DDPM.register_schedule for eps-parameterisation (ddpm.py:162-172), the weight of the variational-bound term of
+    p_losses (ddpm.py:1042-1045): betas^2 / (2 posterior_variance alphas (1 - alphas_cumprod)), evaluated from the fp32 buffers with the
+    reference's own fp32 torch expression in its order (every product and the quotient round in fp32), then entry 0 — where the posterior
+    variance is 0 — takes entry 1's value. fp32 [T]."""
+    import torch
+    betas64 = make_beta_schedule(timesteps, linear_start, linear_end, beta_schedule)
+    ns = NoiseSchedule.make(timesteps, linear_start, linear_end, beta_schedule)
+    ps = PosteriorSchedule.make(timesteps, linear_start, linear_end, beta_schedule, v_posterior=v_posterior)
+    betas = torch.from_numpy(ns.betas.copy())
+    pv = torch.from_numpy(ps.posterior_variance.copy())
+    alphas = torch.tensor(1. - betas64, dtype=torch.float32)
+    ac = torch.from_numpy(ns.alphas_cumprod.copy())
+    w = betas ** 2 / (2 * pv * alphas * (1 - ac))
+    w[0] = w[1]
+    return w.numpy().astype(np.float32)

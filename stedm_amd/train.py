@@ -19,6 +19,7 @@ Gradients are bitwise reproducible (no atomics)."""
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -33,6 +34,26 @@ from .unet import AttentionBlock, Downsample, ResBlock, UNetModel, Upsample
 
 def _r64(n: int) -> int:
     return (n + 63) // 64 * 64
+
+
+@dataclass(frozen=True, eq=False)
+class Objective:
+    """What p_losses (ddpm.py:1015-1048) computes from the eps prediction:
+        loss = l_simple_weight * mean_b(ls_b / exp(logvar[t_b]) + logvar[t_b]) + elbo_weight * mean_b(lvlb[t_b] * ls_b),
+    ls_b the per-sample mean of |.| (kind 'l1') or (.)^2 ('l2'). logvar / lvlb: fp32 [T] device tensors; learned: logvar is a parameter of
+    the optimizer (one of the trainer's extra_params) and receives its gradient from the loss kernel. plain: the reference configs'
+    point (l1, logvar == 0 and not learned, weights 1 and 0), which stays on stedm_l1_loss."""
+    kind: str = "l1"
+    l_simple_weight: float = 1.0
+    elbo_weight: float = 0.0
+    logvar: Optional[torch.Tensor] = None
+    lvlb: Optional[torch.Tensor] = None
+    learned: bool = False
+    plain: bool = True
+
+    def key(self) -> tuple:
+        return (self.kind, self.l_simple_weight, self.elbo_weight, self.learned, self.plain,
+                None if self.logvar is None else self.logvar.data_ptr(), None if self.lvlb is None else self.lvlb.data_ptr())
 
 
 class UNetTrainer:
@@ -73,6 +94,7 @@ class UNetTrainer:
         self.overlap_fires = 0           # all-reduces started from inside a backward so far
         self.direct_wgrad1 = True    # False: the 1x1 convolutions' weight gradients in the GEMM form
         self.wgrad_oihw = True       # the direct 3x3 kernel writes its slices in the parameter's order (False: [tap][ci][co] partials + transposing reduce)
+        self.last_loss_terms: Optional[torch.Tensor] = None   # {loss, loss_simple, loss_gamma, loss_vlb} of the last stedm_diffusion_loss (None: plain L1)
         self.G: Dict[int, torch.Tensor] = {}
 
     # ------------------------------------------------------------------------------------------------ helpers
@@ -673,13 +695,45 @@ class UNetTrainer:
         return ops.silu(ctx, torch.empty_like(ctx), dy=dSc)
 
     # ------------------------------------------------------------------------------------------------ loss + optimizer
+    def _logvar_slot(self, objective: Objective) -> torch.Tensor:
+        """a learned logvar's gradient: its slot in the arena's tail (it is one of extra_params), where the loss kernel writes it"""
+        if getattr(self, "grad_arena", None) is None:
+            self.m._prepare()
+            self._alloc_grads()
+        i = self._pidx.get(id(objective.logvar))
+        if i is None:
+            raise RuntimeError("a learned logvar must be one of the trainer's extra_params (LatentDiffusion.configure_trainer appends it)")
+        return self._int_views[i]
+
     @torch.no_grad()
-    def loss_and_backward(self, x, c_concat, t, context, target, on_bucket=None, sched=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """L1 loss of ddpm.py:1030-1040 on the eps prediction, then the full backward. -> (loss [1] device tensor, dx, dcontext)"""
+    def loss(self, pred, target, t, objective: Optional[Objective], dpred: Optional[torch.Tensor], grad_scale: float = 1.0) -> torch.Tensor:
+        """The objective's value on the eps prediction (-> [1] device tensor) and, with dpred, its gradient (a learned logvar's goes
+        straight into the gradient arena). The plain objective runs stedm_l1_loss, everything else stedm_diffusion_loss, whose four terms
+        stay in last_loss_terms."""
+        target = target.float().contiguous()
+        if objective is None or objective.plain:
+            loss = self._buf("loss", (1,))
+            ops.l1_loss(pred, target, dpred, self._buf("loss.ws", (1024,), torch.float64), loss, grad_scale)
+            self.last_loss_terms = None
+            return loss
+        B = pred.shape[0]
+        n = pred.numel() // B
+        out = self._buf("loss.terms", (4,))
+        ws = self._buf("loss.ws64", (ops.diffusion_loss_ws_doubles(B, n),), torch.float64)
+        dlv = self._logvar_slot(objective) if (objective.learned and dpred is not None) else None
+        ops.diffusion_loss(pred, target, t.to(torch.int64).contiguous(), objective.logvar.detach(), objective.lvlb, objective.kind,
+                           objective.l_simple_weight, objective.elbo_weight, grad_scale, dpred, dlv, ws, out)
+        self.last_loss_terms = out
+        return out[:1]
+
+    @torch.no_grad()
+    def loss_and_backward(self, x, c_concat, t, context, target, on_bucket=None, sched=None,
+                          objective: Optional[Objective] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The objective of ddpm.py:1015-1048 on the eps prediction (None: the plain L1 of the reference configs), then the full backward.
+        -> (loss [1] device tensor, dx, dcontext)"""
         pred = self.forward(x, c_concat, t, context)
-        loss = self._buf("loss", (1,))
         dpred = self._buf(f"dpred.{tuple(pred.shape)}", tuple(pred.shape))
-        ops.l1_loss(pred, target.float().contiguous(), dpred, self._buf("loss.ws", (1024,), torch.float64), loss)
+        loss = self.loss(pred, target, t, objective, dpred)
         dx, dctx = self.backward(dpred, on_bucket=on_bucket, sched=sched)
         return loss, dx, dctx
 
@@ -696,7 +750,8 @@ class UNetTrainer:
         (the autograd bridge of latent_diffusion.py) still gets on_train_batch_end's EMA from here."""
         import numpy as np
         if getattr(self, "grad_arena", None) is None:
-            self._alloc_grads()
+            self.m._prepare()                # a trainer asked for its optimizer state before its first step (a resumed checkpoint): the
+            self._alloc_grads()              # arena's layout follows the packed embedding-Linear order, as in train_step
         params = list(self._arena_params)
         dev = params[0].device
         ema = [p.detach().clone() if i < self._n_unet_params else None for i, p in enumerate(params)] if self.ema_decay is not None else None
@@ -1008,7 +1063,7 @@ class UNetTrainer:
         return had
 
     @torch.no_grad()
-    def train_step(self, x, c_concat, t, context, target, group=None, after_backward=None) -> torch.Tensor:
+    def train_step(self, x, c_concat, t, context, target, group=None, after_backward=None, objective: Optional[Objective] = None) -> torch.Tensor:
         """One micro-batch: loss + backward; every `accumulate_grad_batches`-th call also all-reduces (data parallel) and steps the
         optimizer on the mean of the accumulated gradients (Lightning divides the loss by the accumulation count); LitEma's update
         runs after every micro-batch. after_backward(dx, dcontext): fills the gradients of `extra_params` (cond stage)."""
@@ -1056,7 +1111,7 @@ class UNetTrainer:
                     self._opt_run(fu, b, decay, gs)
                 self.overlap_opt_fires += 1
 
-            loss, dx, dctx = self.loss_and_backward(x, c_concat, t, context, target, on_bucket=on_run, sched=osched)
+            loss, dx, dctx = self.loss_and_backward(x, c_concat, t, context, target, on_bucket=on_run, sched=osched, objective=objective)
             if after_backward is not None:
                 after_backward(dx, dctx)
             self._grads_ready = True
@@ -1066,7 +1121,7 @@ class UNetTrainer:
                     self._opt_run(fu, b, decay, gs)
             self._after_optimizer(fu)
             return loss
-        loss, dx, dctx = self.loss_and_backward(x, c_concat, t, context, target, on_bucket=on_bucket)
+        loss, dx, dctx = self.loss_and_backward(x, c_concat, t, context, target, on_bucket=on_bucket, objective=objective)
         if after_backward is not None:
             after_backward(dx, dctx)
         if k > 1 and getattr(self, "_acc_arena", None) is None:
@@ -1132,7 +1187,7 @@ class UNetTrainer:
         g["base"], g["lr"] = self.step_count, self.lr
 
     @torch.no_grad()
-    def train_step_graphed(self, x, c_concat, t, context, target) -> torch.Tensor:
+    def train_step_graphed(self, x, c_concat, t, context, target, objective: Optional[Objective] = None) -> torch.Tensor:
         """train_step() of one rank without gradient accumulation as ONE hipGraph launch (ddpm.py:345-371: training_step, optimizer.step,
         on_train_batch_end — shape-static). The first GRAPH_WARMUP calls run eagerly (pack plans and the fused optimizer table are built by
         them), the next call captures the step — forward, L1 loss, backward, AdamW + EMA + re-pack, about 790 launches — and every call from
@@ -1152,6 +1207,8 @@ class UNetTrainer:
             raise RuntimeError("train_step_graphed needs the HIP path (a CUDA/HIP device tensor)")
         args = (x, c_concat, t, context, target)
         key = tuple(None if a is None else (tuple(a.shape), a.dtype) for a in args)
+        if objective is not None and not objective.plain:
+            key = key + (objective.key(),)           # the captured loss launch holds the objective's scalars and table pointers
         g = getattr(self, "_graph", None)
         if g is not None and (g["key"] != key or g["token"] != self.m.freshness_token() or g["host_step"] != self.step_count):
             g = self._graph = None                    # someone else moved the parameters or the counters: the captured plan is stale
@@ -1161,8 +1218,8 @@ class UNetTrainer:
                 if getattr(self, "_graph_key", None) != key:
                     self._graph_key, self._graph_eager = key, 0
                 self._graph_eager += 1
-                return self.train_step(x, c_concat, t, context, target)
-            g = self._capture(args, key)
+                return self.train_step(x, c_concat, t, context, target, objective=objective)
+            g = self._capture(args, key, objective)
         if self.step_count + 1 - g["base"] >= self.GRAPH_WINDOW or g["lr"] != self.lr:
             self._graph_window(g)
         for dst, src in zip(g["inputs"], args):
@@ -1178,7 +1235,7 @@ class UNetTrainer:
         g["token"], g["host_step"] = self.m.freshness_token(), self.step_count
         return g["loss"]
 
-    def _capture(self, args, key):
+    def _capture(self, args, key, objective=None):
         dev = args[0].device
         inputs = [None if a is None else torch.empty_like(a) for a in args]
         for dst, src in zip(inputs, args):
@@ -1195,7 +1252,7 @@ class UNetTrainer:
         try:
             with torch.cuda.graph(graph):
                 ops.step_advance(g["idx"], 1)
-                loss = self.train_step(*inputs)
+                loss = self.train_step(*inputs, objective=objective)
         finally:
             self._cap_sched = None
             self.step_count, self.ema_updates, self.overlap_opt_fires, self.overlap_fires = keep
