@@ -461,7 +461,7 @@ static int conv_dispatch(ConvParams& p, void* stream) {
     if (rc == 0 || !a.src1) return rc;
     // otherwise fall through to the fused fp32-source kernels
   }
-  // fp32-source form (GroupNorm folded into the patch loader): the parity mode's stride-2 convs and the opt-in "fused" path
+  // fp32-source form (GroupNorm folded into the patch loader): the parity mode's stride-2 convs
   const int bkc = (a.npass == 1 && p.Cin % 64 == 0 && (a.c2 == 0 || a.c1 % 64 == 0)) ? 64 : 32;
   if (!conv_geometry(p, BM)) return 1;
   const bool f16 = a.mm_dtype == STEDM_F16;

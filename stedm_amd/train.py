@@ -207,7 +207,7 @@ class UNetTrainer:
             frag = None
         else:
             # packed straight from the OIHW parameter: row n = forward input channel, column ci = forward output channel, taps reversed
-            want_frag = self.m.conv_path == "dma" and bp.npass == 1 and ((ks == 3 and co_f % 16 == 0) or (ks == 1 and co_f % 64 == 0))
+            want_frag = bp.npass == 1 and ((ks == 3 and co_f % 16 == 0) or (ks == 1 and co_f % 64 == 0))
             args = (w, taps, ci_f * taps, True, ci_f, co_f, ks, bp)
             if want_frag:   # the planes are only read when a problem falls to the LDS-operand kernels: packed on first need
                 # the dgrad conv contracts over the forward's OUTPUT channels: the 16x16x32 MFMA kind takes it from 256 of them on
@@ -253,7 +253,7 @@ class UNetTrainer:
         gdst = (lambda: grad) if grad is not None else (lambda: self._param_grad(wparam))
         B, Hs, Ws, Cs = src16[0].shape
         Bo, Ho, Wo, co = dy16[0].shape
-        if ks == 3 and mode == 0 and bp.npass == 1 and self.m.conv_path == "dma" and self.direct_wgrad:
+        if ks == 3 and mode == 0 and bp.npass == 1 and self.direct_wgrad:
             nsplit = ops.wgrad3x3_plan(B, Hs, Ws, Cs, co)
             if nsplit > 0:    # direct kernel: both operands straight from the NHWC planes, transposed in the LDS reads
                 g = gdst()
@@ -271,7 +271,7 @@ class UNetTrainer:
                 ops.wgrad3x3(src16[0], dy16[0], part, bp)
                 ops.wgrad_to_oihw(part, g, Cs, co, False, nsplit)
                 return
-        if ks == 1 and mode == 0 and bp.npass == 1 and self.m.conv_path == "dma" and self.direct_wgrad and self.direct_wgrad1 and src16[0].is_contiguous() and dy16[0].is_contiguous():
+        if ks == 1 and mode == 0 and bp.npass == 1 and self.direct_wgrad and self.direct_wgrad1 and src16[0].is_contiguous() and dy16[0].is_contiguous():
             nsplit = ops.wgrad1x1_plan(B * Hs * Ws, Cs, co)
             if nsplit > 0:    # direct kernel for the 1x1 convolutions: flat [P][C] planes, no transposes through HBM
                 part = self._buf("wg.part1", (nsplit * Cs * co,))
@@ -299,7 +299,7 @@ class UNetTrainer:
             ops.im2col_t16(src16[i], col[i], ks, mode)
             ops.im2col_t16(dy16[i], dyt[i], 1, 0)
         frag = None
-        if self.m.conv_path == "dma" and bp.npass == 1 and P == Ppad and dy_f32 is not None and dy_f32.numel() == P * co:
+        if bp.npass == 1 and P == Ppad and dy_f32 is not None and dy_f32.numel() == P * co:
             # register-streamed kernel (splits K = B*H*W over blocks): dY^T in MFMA-fragment order
             frag = ops.pack_conv_weight_strided(dy_f32, 1, co, False, co, P, 1, bp, want_hi=False, want_frag=True)[2]
         dw = self._buf("dw", (taps, Cs, 1, co))
@@ -387,7 +387,7 @@ class UNetTrainer:
         self._st_holders = []
         # dgrad weight packs: the fragment-order ones recorded by the last backward run again as ONE launch when the parameters kept their
         # storage (ops.PackPlan); everything else is packed when first needed, as before
-        dkey = (self.bprec, m.conv_path, m._m16, tuple(p.data_ptr() for p in m.parameters()))
+        dkey = (self.bprec, m._m16, tuple(p.data_ptr() for p in m.parameters()))
         self._dpacks_step = {}
         if getattr(self, "_dplan", None) is not None and self._dplan_key == dkey:
             self._dplan.run(versions=m.freshness_token())

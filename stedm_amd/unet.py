@@ -6,10 +6,11 @@ and fp32 OIHW parameter shapes — so reference checkpoints load with `load_stat
 `forward` runs entirely in hand-written HIP kernels through the C ABI (stedm_amd/ops.py).
 torch.nn modules below are *parameter containers*; their own forward is never used.
 
-Internal data layout: activations NHWC fp32 in HBM; conv weights pre-packed [cout][tap][cin]
-16-bit (hi/lo planes); GroupNorm is turned into per-(sample, channel) scale/shift by a statistics
-kernel and applied inside the consuming conv's A-tile load together with SiLU; the skip concat is
-never materialised (the conv reads two sources).
+Internal data layout: activations NHWC fp32 in HBM; conv weights pre-packed 16-bit (hi/lo planes
+[cout][tap][cin], or MFMA-fragment order for the register-streamed kernels); GroupNorm statistics
+ride on the producing conv's epilogue, and one normalise / SiLU / convert pass writes the 16-bit
+operand planes the consuming conv reads; the skip concat is never materialised (that pass reads
+two sources).
 """
 from __future__ import annotations
 
@@ -222,10 +223,6 @@ class UNetModel(nn.Module):
         self._bufs: Dict[Tuple, torch.Tensor] = {}
         self._emb_layout: List[Tuple[ResBlock, int]] = []
         self._consts: Dict[str, torch.Tensor] = {}
-        # "dma": GroupNorm statistics kernel + one normalise/activate/convert pass to 16-bit planes, convolution with
-        #        LDS-DMA operands (default). "fused": GroupNorm applied inside the conv's patch loader (v1/v2 kernels).
-        import os as _os
-        self.conv_path = _os.environ.get("STEDM_CONV_PATH", "dma")
         self._m16 = True             # 3x3 convs from 256 input channels on v_mfma_f32_16x16x32 (conv_rs.inc RS_3X3M)
         self._gn_slot = 0
         self._style_cache: Dict[Tuple, torch.Tensor] = {}
@@ -301,7 +298,7 @@ class UNetModel(nn.Module):
             ops.f16_guard_enable()        # fp16 operand planes: the kernels flag an overflow, the sampling loops / check_f16_range() raise
         # Same storage, new values (an optimizer step): the fragment-order packs recorded last time run again as ONE launch into the same
         # tensors (ops.PackPlan); the few other packs below are redone as before. Anything else: pack from scratch and record.
-        ptr_key = (prec, dev, ptrs, self.conv_path, self._m16)
+        ptr_key = (prec, dev, ptrs, self._m16)
         plan = getattr(self, "_plan", None)
         replay = plan is not None and self._plan_key == ptr_key and len(self._packed) > 0
         if not replay:
@@ -332,7 +329,7 @@ class UNetModel(nn.Module):
             k3 = tuple(w4.shape[2:]) == (3, 3) and conv.stride == (1, 1) and conv.in_channels % 16 == 0
             k1 = tuple(w4.shape[2:]) == (1, 1) and conv.in_channels % 64 == 0
             frag16 = None
-            if self.conv_path == "dma" and prec.npass == 1 and (k3 or k1):
+            if prec.npass == 1 and (k3 or k1):
                 # register-streamed weights, packed in the fragment order of the MFMA shape the dispatcher will pick: 16x16x32 for a 3x3 from
                 # 256 input channels on (conv_rs.inc RS_3X3M), 32x32x16 otherwise; a 1x1 (skip_connection, qkv, proj_out) gets both: fused
                 # into an RS_3X3M launch it is read in the 16x16x32 order, on its own in the other
@@ -343,12 +340,12 @@ class UNetModel(nn.Module):
                     frag16 = plan.frag_oihw(w4, True) if in_place else ops.pack_conv_weight_frag16(w4, prec)
                 # the [cout][tap][cin] planes are read only by the LDS-operand kernels: packed on first need
                 hi = ops.LazyPlanes(lambda w=conv.weight: ops.pack_conv_weight(w.float(), prec))
-            elif self.conv_path == "dma" and prec.npass == 1 and conv.stride == (2, 2) and conv.in_channels % 8 == 0:
+            elif prec.npass == 1 and conv.stride == (2, 2) and conv.in_channels % 8 == 0:
                 # Downsample.op: runs as the space-to-depth form below; the plain planes serve odd sizes only
                 hi = ops.LazyPlanes(lambda w=conv.weight: ops.pack_conv_weight(w.float(), prec))
             else:
                 hi, lo = ops.pack_conv_weight(conv.weight.float(), prec)
-                if self.conv_path == "dma" and prec.npass == 3 and self._m16 and conv.in_channels % 32 == 0 and (
+                if prec.npass == 3 and self._m16 and conv.in_channels % 32 == 0 and (
                         (k3 and conv.in_channels >= 128) or (tuple(w4.shape[2:]) == (1, 1) and conv.in_channels >= 64)):
                     # 3-product mode on the register-streamed kernel (conv_rs.inc P3: 3x3, and 1x1 = RS_1X1M): hi + lo fragment streams; the
                     # planes above stay for the problems it does not take
@@ -363,26 +360,26 @@ class UNetModel(nn.Module):
                     pack(m.skip_connection)
             elif isinstance(m, Downsample):
                 pack(m.op)
-                if self.conv_path == "dma" and prec.npass == 1 and m.op.in_channels % 8 == 0:
+                if prec.npass == 1 and m.op.in_channels % 8 == 0:
                     # stride-2 conv as a stride-1 2x2 conv over space-to-depth planes (register-streamed kernel)
                     self._packed[(id(m.op), "s2d")] = _Packed(None, None, self._packed[id(m.op)].bias,
                                                               ops.pack_conv_weight_s2d_frag(m.op.weight.float(), prec))
-                elif self.conv_path == "dma" and prec.npass == 3 and self._m16 and m.op.in_channels % 32 == 0:
+                elif prec.npass == 3 and self._m16 and m.op.in_channels % 32 == 0:
                     # ... in the 3-product modes with hi + lo planes and fragment streams (conv_rs.inc RS_SUBM)
                     self._packed[(id(m.op), "s2d")] = _Packed(None, None, self._packed[id(m.op)].bias, None,
                                                               ops.pack_conv_weight_s2d_frag16_hl(m.op.weight.float(), prec))
             elif isinstance(m, Upsample):
                 pack(m.conv)
-                if self.conv_path == "dma":   # sub-pixel form: 4 parity 2x2 convs with pre-summed taps
-                    frag = ops.pack_conv_weight_up_frag(m.conv.weight.float(), prec) if prec.npass == 1 and m.conv.in_channels % 32 == 0 else None
-                    if frag is not None:     # the planes are read only when a problem falls to the LDS-operand kernel: packed on first need
-                        hi, lo = ops.LazyPlanes(lambda w=m.conv.weight: ops.pack_conv_weight_up(w.float(), prec)), None
-                    else:
-                        hi, lo = ops.pack_conv_weight_up(m.conv.weight.float(), prec)
-                    # 16x16x32 fragment order (RS_SUBM): the 3-product modes (single product: the 32x32x16 RS_SUB form measured faster)
-                    frag16 = (ops.pack_conv_weight_up_frag16_hl(m.conv.weight.float(), prec)
-                              if prec.npass == 3 and self._m16 and m.conv.in_channels % 32 == 0 and m.conv.in_channels >= 128 else None)
-                    self._packed[(id(m.conv), "up")] = _Packed(hi, lo, self._packed[id(m.conv)].bias, frag, frag16)
+                # sub-pixel form: 4 parity 2x2 convs with pre-summed taps
+                frag = ops.pack_conv_weight_up_frag(m.conv.weight.float(), prec) if prec.npass == 1 and m.conv.in_channels % 32 == 0 else None
+                if frag is not None:     # the planes are read only when a problem falls to the LDS-operand kernel: packed on first need
+                    hi, lo = ops.LazyPlanes(lambda w=m.conv.weight: ops.pack_conv_weight_up(w.float(), prec)), None
+                else:
+                    hi, lo = ops.pack_conv_weight_up(m.conv.weight.float(), prec)
+                # 16x16x32 fragment order (RS_SUBM): the 3-product modes (single product: the 32x32x16 RS_SUB form measured faster)
+                frag16 = (ops.pack_conv_weight_up_frag16_hl(m.conv.weight.float(), prec)
+                          if prec.npass == 3 and self._m16 and m.conv.in_channels % 32 == 0 and m.conv.in_channels >= 128 else None)
+                self._packed[(id(m.conv), "up")] = _Packed(hi, lo, self._packed[id(m.conv)].bias, frag, frag16)
             elif isinstance(m, AttentionBlock):
                 pack(m.qkv)
                 pack(m.proj_out)
@@ -421,19 +418,22 @@ class UNetModel(nn.Module):
         self._pack_key = key
 
     # ------------------------------------------------------------------------------------ block runners (NHWC)
-    def _gn(self, tag, norm: nn.GroupNorm, x1, x2=None, x2_bmod=0):
-        B = x1.shape[0]
-        C = x1.shape[-1] + (0 if x2 is None else x2.shape[-1])
-        sc = self._buf(tag + ".sc", (B, C))
-        sh = self._buf(tag + ".sh", (B, C))
-        ops.gn_scale_shift(x1, x2, norm.weight, norm.bias, norm.eps, sc, sh, norm.num_groups, x2_bmod)
-        return sc, sh
-
-    # ---- DMA path helpers: 16-bit operand planes -------------------------------------------------------------
+    # ---- 16-bit operand planes ---------------------------------------------------------------------------------
     def _planes(self, B, H, W, C, kind="a16"):
         hi = self._buf(f"{kind}hi.{B}x{H}x{W}x{C}", (B, H, W, C), torch.int16)
         lo = self._buf(f"{kind}lo.{B}x{H}x{W}x{C}", (B, H, W, C), torch.int16) if self.precision.npass == 3 else None
         return hi, lo
+
+    # Split-K workspace (small grids only) for an output of `nel` fp32 elements. Two rules, tuned separately: keep them apart.
+    def _splitk_ws_res(self, nel: int) -> Optional[torch.Tensor]:
+        """ResBlock convolutions: room for up to 16 partial tiles when the tensor is small, 4 or 2 above that, none above 2^23 elements"""
+        if nel > (1 << 23):
+            return None
+        return self._buf("conv_ws", ((16 if nel <= (1 << 20) else (4 if nel <= (1 << 22) else 2)) * nel,))
+
+    def _splitk_ws(self, nel: int) -> torch.Tensor:
+        """proj_out, Downsample, Upsample: room for up to 16 partial tiles when the tensor is small, 2 otherwise"""
+        return self._buf("conv_ws", ((16 if nel <= (1 << 20) else 2) * nel,))
 
     # Producer-side GroupNorm statistics: tensors written by a conv epilogue carry per-(sample, slab, channel) partial sums
     # (stedm_conv_args.chan_stats); tensors from other producers get them lazily from one stedm_gn_chan_stats pass. One set of
@@ -526,77 +526,69 @@ class UNetModel(nn.Module):
         prec = self.precision
         B, H, W, _ = x1.shape
         co = rb.out_channels
-        dma = self.conv_path == "dma"
         pk = self._packed[id(rb.in_layers[2])]
         # training keeps every block's intermediate (the backward pass reads it); inference shares one buffer per shape
         h = self._buf(tag + ".h" if self._tape is not None else f"h.{B}x{H}x{W}x{co}", (B, H, W, co))
         self._last_h = h
         has_skip = not isinstance(rb.skip_connection, nn.Identity)
         h16_next = gn_next = None
-        if dma:
-            if has_skip:
-                a16, x16 = self._norm16(rb.in_layers[0], 1, x1, x2, x2_bmod, want_raw=True)
-            else:
-                a16 = self._norm16(rb.in_layers[0], 1, x1, x2, x2_bmod)
-            # split-K workspace (small grids only): room for up to 16 partial tiles when the tensor is small, 2 otherwise
-            nel = B * H * W * co
-            ws = self._buf("conv_ws", ((16 if nel <= (1 << 20) else (4 if nel <= (1 << 22) else 2)) * nel,)) if nel <= (1 << 23) else None
-            # out_layers' GroupNorm + SiLU of h rides on this call (inference, single product): where the convolution splits K, the reduce pass
-            # that sums the partial tiles owns whole groups of a sample and writes the normalised planes itself; otherwise the call ends with the
-            # same stedm_gn_apply16c pass as before
-            gn2 = rb.out_layers[0]
-            if (prec.npass == 1 and (self._tape is None or prec.mm_dtype == BF16)) or (prec.npass == 3 and self._tape is None):
-                if self._tape is None:
-                    # NOT the planes _norm16 would hand out: for cin == cout those are the planes this convolution is reading, and an epilogue
-                    # that writes the GroupNorm output would overwrite rows other tiles still gather
-                    h16_next = self._planes(B, H, W, co, "g16")
-                    mr2 = None
-                else:
-                    # training forward in the backward's operand format: the planes and the group statistics are kept, exactly as _norm16 keeps them
-                    self._plane_ctr += 1
-                    h16_next = self._planes(B, H, W, co, f"keep{self._plane_ctr}.a16")
-                    self._saved16[(id(gn2), h.data_ptr())] = h16_next
-                    self._mr_ctr += 1
-                    mr2 = self._buf(f"keep{self._mr_ctr}.mr", (B, gn2.num_groups, 2))
-                    self._saved_mr[(id(gn2), h.data_ptr())] = mr2
-                # (inference: nothing but that GroupNorm reads h — an epilogue that writes the planes itself skips h's fp32 store)
-                # (3-product modes, round 4: the (hi, lo) pair; single-product: the hi plane)
-                gn_next = (gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1, h16_next if prec.npass == 3 else h16_next[0], mr2, self._tape is None)
-            done1 = False
-            # (where a sample spans 2 .. 4 tiles - 32 x 32 pixels at 128 channels - the tiles exchange their channel sums inside the launch
-            #  and the GroupNorm still rides on the epilogue: stedm_conv_args.gn_coop; one word block per call site)
-            coop = self._coop_for(tag, B, H, W, co, prec) if gn_next is not None and self._tape is None else None
-            coop_runs = coop is not None
-            if (gn_next is not None and self._tape is None and prec.npass == 1 and prec.mm_dtype == BF16 and H * W > 256 and B >= 8 and not coop_runs and
-                    not os.environ.get("STEDM_NO_H16ONLY") and ops.gn_apply16c_x16_ok(co, 0, gn2.num_groups)):
-                # Levels whose samples exceed a tile (32 x 32 and up): out_layers' GroupNorm cannot ride on the epilogue and nothing else reads h, so
-                # the convolution stores h as 16-bit values only (+ the channel statistics) and the GroupNorm pass reads 2 B per element.
-                # bf16 mode only: in f16 - the mode that carries the 1e-3 tolerance - the extra rounding in front of five more GroupNorms moved the
-                # forward's rel-L2 from 7.55e-4 to 7.86e-4 for +0.5 % of a step (6.165 -> 6.135 ms); the margin is worth more
-                kw1 = dict(prec=prec, src16=a16, bias=pk.bias, emb=emb_all, emb_offset=emb_off, emb_bstride=emb_bstride, w_frag=pk.frag,
-                           chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16)
-                hraw = self._buf(f"h16raw.{B}x{H}x{W}x{co}", (B, H, W, co), torch.int16)
-                key1 = ("h16only", id(rb), B, H, W)
-                ok1 = self._consts.get(key1)
-                if ok1 is None:
-                    ok1 = bool(ops.conv_igemm(None, pk.hi, pk.lo, None, query_rs=True, out16=(hraw, None), out16_stride=co, cout=co, **kw1))
-                    self._consts[key1] = ok1
-                if ok1:
-                    ops.conv_igemm(None, pk.hi, pk.lo, None, out16=(hraw, None), out16_stride=co, cout=co, **kw1)
-                    ops.gn_apply16c_x16(co, self._cs[h.data_ptr()], None, None, h16_next[0], hraw, prec, gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1)
-                    done1 = True
-            if not done1:
-                ops.conv_igemm(None, pk.hi, pk.lo, h, prec=prec, src16=a16, bias=pk.bias, emb=emb_all, emb_offset=emb_off,
-                               emb_bstride=emb_bstride, w_frag=pk.frag, chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16, gn_next=gn_next,
-                               coop=coop)
+        if has_skip:
+            a16, x16 = self._norm16(rb.in_layers[0], 1, x1, x2, x2_bmod, want_raw=True)
         else:
-            sc, sh = self._gn(tag + ".gn1", rb.in_layers[0], x1, x2, x2_bmod)
-            ops.conv_igemm(x1, pk.hi, pk.lo, h, prec=prec, src2=x2, src2_bmod=x2_bmod, scale=sc, shift=sh, act=1, bias=pk.bias,
-                           emb=emb_all, emb_offset=emb_off, emb_bstride=emb_bstride)
+            a16 = self._norm16(rb.in_layers[0], 1, x1, x2, x2_bmod)
+        ws = self._splitk_ws_res(B * H * W * co)
+        # out_layers' GroupNorm + SiLU of h rides on this call (inference, single product): where the convolution splits K, the reduce pass
+        # that sums the partial tiles owns whole groups of a sample and writes the normalised planes itself; otherwise the call ends with the
+        # same stedm_gn_apply16c pass as before
+        gn2 = rb.out_layers[0]
+        if (prec.npass == 1 and (self._tape is None or prec.mm_dtype == BF16)) or (prec.npass == 3 and self._tape is None):
+            if self._tape is None:
+                # NOT the planes _norm16 would hand out: for cin == cout those are the planes this convolution is reading, and an epilogue
+                # that writes the GroupNorm output would overwrite rows other tiles still gather
+                h16_next = self._planes(B, H, W, co, "g16")
+                mr2 = None
+            else:
+                # training forward in the backward's operand format: the planes and the group statistics are kept, exactly as _norm16 keeps them
+                self._plane_ctr += 1
+                h16_next = self._planes(B, H, W, co, f"keep{self._plane_ctr}.a16")
+                self._saved16[(id(gn2), h.data_ptr())] = h16_next
+                self._mr_ctr += 1
+                mr2 = self._buf(f"keep{self._mr_ctr}.mr", (B, gn2.num_groups, 2))
+                self._saved_mr[(id(gn2), h.data_ptr())] = mr2
+            # (inference: nothing but that GroupNorm reads h — an epilogue that writes the planes itself skips h's fp32 store)
+            # (3-product modes, round 4: the (hi, lo) pair; single-product: the hi plane)
+            gn_next = (gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1, h16_next if prec.npass == 3 else h16_next[0], mr2, self._tape is None)
+        done1 = False
+        # (where a sample spans 2 .. 4 tiles - 32 x 32 pixels at 128 channels - the tiles exchange their channel sums inside the launch
+        #  and the GroupNorm still rides on the epilogue: stedm_conv_args.gn_coop; one word block per call site)
+        coop = self._coop_for(tag, B, H, W, co, prec) if gn_next is not None and self._tape is None else None
+        coop_runs = coop is not None
+        if (gn_next is not None and self._tape is None and prec.npass == 1 and prec.mm_dtype == BF16 and H * W > 256 and B >= 8 and not coop_runs and
+                not os.environ.get("STEDM_NO_H16ONLY") and ops.gn_apply16c_x16_ok(co, 0, gn2.num_groups)):
+            # Levels whose samples exceed a tile (32 x 32 and up): out_layers' GroupNorm cannot ride on the epilogue and nothing else reads h, so
+            # the convolution stores h as 16-bit values only (+ the channel statistics) and the GroupNorm pass reads 2 B per element.
+            # bf16 mode only: in f16 - the mode that carries the 1e-3 tolerance - the extra rounding in front of five more GroupNorms moved the
+            # forward's rel-L2 from 7.55e-4 to 7.86e-4 for +0.5 % of a step (6.165 -> 6.135 ms); the margin is worth more
+            kw1 = dict(prec=prec, src16=a16, bias=pk.bias, emb=emb_all, emb_offset=emb_off, emb_bstride=emb_bstride, w_frag=pk.frag,
+                       chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16)
+            hraw = self._buf(f"h16raw.{B}x{H}x{W}x{co}", (B, H, W, co), torch.int16)
+            key1 = ("h16only", id(rb), B, H, W)
+            ok1 = self._consts.get(key1)
+            if ok1 is None:
+                ok1 = bool(ops.conv_igemm(None, pk.hi, pk.lo, None, query_rs=True, out16=(hraw, None), out16_stride=co, cout=co, **kw1))
+                self._consts[key1] = ok1
+            if ok1:
+                ops.conv_igemm(None, pk.hi, pk.lo, None, out16=(hraw, None), out16_stride=co, cout=co, **kw1)
+                ops.gn_apply16c_x16(co, self._cs[h.data_ptr()], None, None, h16_next[0], hraw, prec, gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1)
+                done1 = True
+        if not done1:
+            ops.conv_igemm(None, pk.hi, pk.lo, h, prec=prec, src16=a16, bias=pk.bias, emb=emb_all, emb_offset=emb_off,
+                           emb_bstride=emb_bstride, w_frag=pk.frag, chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16, gn_next=gn_next,
+                           coop=coop)
         out = self._buf(tag + ".out", (B, H, W, co))
         pk2 = self._packed[id(rb.out_layers[3])]
         o16 = None
-        if dma and want16:     # the consumer (Upsample) reads plain 16-bit planes: the conv epilogue writes them, no conversion pass
+        if want16:     # the consumer (Upsample) reads plain 16-bit planes: the conv epilogue writes them, no conversion pass
             o16 = self._planes(B, H, W, co, "up16")
             self._raw16[out.data_ptr()] = o16
         # next_norm = (GroupNorm32, act) of the layer that reads this block's output alone (the next ResBlock's in_layers without a
@@ -604,7 +596,7 @@ class UNetModel(nn.Module):
         # epilogue / split-K reduce pass where a workgroup owns whole groups of whole samples, by the same trailing pass otherwise - and
         # _norm16 hands them out instead of running its own pass (inference)
         gnn, npl, coop2 = None, None, None
-        if next_norm is not None and dma and self._tape is None and o16 is None and next_cat is None and not os.environ.get("STEDM_NO_NEXT_GN"):
+        if next_norm is not None and self._tape is None and o16 is None and next_cat is None and not os.environ.get("STEDM_NO_NEXT_GN"):
             nn_, nact = next_norm
             npl = self._planes(B, H, W, co)
             gnn = (nn_.weight, nn_.bias, nn_.eps, nn_.num_groups, nact, npl if prec.npass == 3 else npl[0], None, False)
@@ -614,7 +606,7 @@ class UNetModel(nn.Module):
             if gnn is not None:
                 self._pre16[out.data_ptr()] = (id(next_norm[0]), next_norm[1], npl)
             return out
-        if dma and has_skip:
+        if has_skip:
             # conv2 + skip_connection(x) in one kernel when the register-streamed kernel covers the problem (asked once per shape)
             ps = self._packed[id(rb.skip_connection)]
             h16 = h16_next if h16_next is not None else self._norm16(rb.out_layers[0], 1, h)
@@ -661,46 +653,35 @@ class UNetModel(nn.Module):
                 ops.conv_igemm(None, pk2.hi, pk2.lo, out, res=out, gn_next=gnn, **kw)
                 return filed()
             return out
-        if not has_skip:
-            assert x2 is None
-            res = x1
-        else:
-            ps = self._packed[id(rb.skip_connection)]
-            ops.conv_igemm(x1, ps.hi, ps.lo, out, prec=prec, ks=1, src2=x2, src2_bmod=x2_bmod, bias=ps.bias)
-            res = out
-        if dma:
-            h16 = h16_next if h16_next is not None else self._norm16(rb.out_layers[0], 1, h)
-            if next_cat is not None and o16 is None:
-                rawn = self._cat_plane(B, H, W, co, next_cat)
-                kwc = dict(prec=prec, src16=h16, bias=pk2.bias, res=res, w_frag=pk2.frag, chan_stats=self._cs_new(out), ws=ws, w_frag16=pk2.frag16,
-                           out16=(rawn, None), out16_stride=next_cat, cout=co)
-                keyc = ("rescat", id(rb), B, H, W, next_cat)
-                okc = self._consts.get(keyc)
-                if okc is None:
-                    okc = bool(ops.conv_igemm(None, pk2.hi, pk2.lo, None, query_rs=True, **kwc))
-                    self._consts[keyc] = okc
-                if okc:
-                    ops.conv_igemm(None, pk2.hi, pk2.lo, None, **kwc)
-                    self._x16[out.data_ptr()] = (rawn, co)
-                    return out
-            ops.conv_igemm(None, pk2.hi, pk2.lo, out, prec=prec, src16=h16, bias=pk2.bias, res=res, w_frag=pk2.frag,
-                           chan_stats=self._cs_new(out), ws=ws, out16=o16, w_frag16=pk2.frag16, gn_next=gnn, coop=coop2)
-            return filed()
-        else:
-            sc2, sh2 = self._gn(tag + ".gn2", rb.out_layers[0], h)
-            ops.conv_igemm(h, pk2.hi, pk2.lo, out, prec=prec, scale=sc2, shift=sh2, act=1, bias=pk2.bias, res=res)
-        return out
+        # no skip_connection convolution: the residual is the block's input itself
+        assert x2 is None
+        h16 = h16_next if h16_next is not None else self._norm16(rb.out_layers[0], 1, h)
+        if next_cat is not None and o16 is None:
+            rawn = self._cat_plane(B, H, W, co, next_cat)
+            kwc = dict(prec=prec, src16=h16, bias=pk2.bias, res=x1, w_frag=pk2.frag, chan_stats=self._cs_new(out), ws=ws, w_frag16=pk2.frag16,
+                       out16=(rawn, None), out16_stride=next_cat, cout=co)
+            keyc = ("rescat", id(rb), B, H, W, next_cat)
+            okc = self._consts.get(keyc)
+            if okc is None:
+                okc = bool(ops.conv_igemm(None, pk2.hi, pk2.lo, None, query_rs=True, **kwc))
+                self._consts[keyc] = okc
+            if okc:
+                ops.conv_igemm(None, pk2.hi, pk2.lo, None, **kwc)
+                self._x16[out.data_ptr()] = (rawn, co)
+                return out
+        ops.conv_igemm(None, pk2.hi, pk2.lo, out, prec=prec, src16=h16, bias=pk2.bias, res=x1, w_frag=pk2.frag,
+                       chan_stats=self._cs_new(out), ws=ws, out16=o16, w_frag16=pk2.frag16, gn_next=gnn, coop=coop2)
+        return filed()
 
     def _attn(self, tag: str, ab: AttentionBlock, x):
         """AttentionBlock._forward openaimodel.py:340-346 on NHWC (tokens = H*W)."""
         prec = self.precision
         B, H, W, Cc = x.shape
-        dma = self.conv_path == "dma"
         pq = self._packed[id(ab.qkv)]
         pp = self._packed[id(ab.proj_out)]
         out = self._buf(tag + ".out", (B, H, W, Cc))
         ch = Cc // ab.num_heads
-        if dma and prec.npass == 1 and self._tape is None and ch in (16, 32, 64, 128):
+        if prec.npass == 1 and self._tape is None and ch in (16, 32, 64, 128):
             # 64 tokens (64 n tokens: key tiles with an online softmax around the same products): the qkv conv writes its result as a 16-bit plane, the whole attention of a (sample, head) runs on one wave's
             # MFMAs and is written as proj_out's 16-bit operand plane (same operand rounding as everywhere in these modes)
             qkv16 = self._planes(B, H, W, 3 * Cc, "qkv16")
@@ -709,25 +690,81 @@ class UNetModel(nn.Module):
             a16 = self._planes(B, H, W, Cc, "attn16")
             ops.attn_legacy16(qkv16[0].view(B, H * W, 3 * Cc), a16[0], ab.num_heads, prec)
             ops.conv_igemm(None, pp.hi, pp.lo, out, prec=prec, ks=1, src16=a16, bias=pp.bias, res=x, w_frag=pp.frag,
-                           chan_stats=self._cs_new(out), ws=self._buf("conv_ws", ((16 if out.numel() <= (1 << 20) else 2) * out.numel(),)))
+                           chan_stats=self._cs_new(out), ws=self._splitk_ws(out.numel()))
             return out
         qkv = self._buf(tag + ".qkv", (B, H, W, 3 * Cc))
-        if dma:
-            ops.conv_igemm(None, pq.hi, pq.lo, qkv, prec=prec, ks=1, src16=self._norm16(ab.norm, 0, x), bias=pq.bias, w_frag=pq.frag,
-                           w_frag16=pq.frag16 if prec.npass == 3 else None)
-        else:
-            sc, sh = self._gn(tag + ".gn", ab.norm, x)
-            ops.conv_igemm(x, pq.hi, pq.lo, qkv, prec=prec, ks=1, scale=sc, shift=sh, act=0, bias=pq.bias)
+        ops.conv_igemm(None, pq.hi, pq.lo, qkv, prec=prec, ks=1, src16=self._norm16(ab.norm, 0, x), bias=pq.bias, w_frag=pq.frag,
+                       w_frag16=pq.frag16 if prec.npass == 3 else None)
         a = self._buf(tag + ".a", (B, H, W, Cc))
         ops.attn_legacy(qkv.view(B, H * W, 3 * Cc), a.view(B, H * W, Cc), ab.num_heads)
         if self._tape is not None:
             self._tape.append(("attn", ab, x, qkv, a, out))
-        if dma:
-            ops.conv_igemm(None, pp.hi, pp.lo, out, prec=prec, ks=1, src16=self._norm16(None, 0, a), bias=pp.bias, res=x, w_frag=pp.frag,
-                           chan_stats=self._cs_new(out), w_frag16=pp.frag16 if prec.npass == 3 else None)
-        else:
-            ops.conv_igemm(a, pp.hi, pp.lo, out, prec=prec, ks=1, bias=pp.bias, res=x)
+        ops.conv_igemm(None, pp.hi, pp.lo, out, prec=prec, ks=1, src16=self._norm16(None, 0, a), bias=pp.bias, res=x, w_frag=pp.frag,
+                       chan_stats=self._cs_new(out), w_frag16=pp.frag16 if prec.npass == 3 else None)
         return out
+
+    def _down(self, ltag: str, layer: Downsample, h):
+        """Downsample.forward openaimodel.py:165-167: the stride-2 3x3 convolution."""
+        pk = self._packed[id(layer.op)]
+        B, H, W, _ = h.shape
+        out = self._buf(ltag + ".out", (B, H // 2, W // 2, layer.out_channels))
+        if self._tape is not None:
+            self._tape.append(("down", layer, h, out))
+        ps2 = self._packed.get((id(layer.op), "s2d"))
+        if H % 2 == 0 and W % 2 == 0 and not ops.conv3x3_tiles_ok(H // 2, W // 2):
+            # an output grid the tiled kernels cannot tile (latent widths that are not powers of two): im2col + flat GEMM (ops.conv_igemm)
+            return ops.conv_igemm(None, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_DOWN, src16=self._norm16(None, 0, h), bias=pk.bias,
+                                  chan_stats=self._cs_new(out))
+        elif ps2 is not None and H % 2 == 0 and W % 2 == 0 and (H // 2) * (W // 2) >= 16:
+            C = h.shape[-1]
+            planes = self._buf(f"s2d16.{B}x{H}x{W}x{C}", (B, H // 2, W // 2, 4 * C), torch.int16)
+            planes_lo = self._buf(f"s2d16lo.{B}x{H}x{W}x{C}", (B, H // 2, W // 2, 4 * C), torch.int16) if self.precision.npass == 3 else None
+            ws = self._splitk_ws(out.numel())
+            kw2 = dict(prec=self.precision, mode=CONV_S2D, src16=(planes, planes_lo), bias=ps2.bias, w_frag=ps2.frag, w_frag16=ps2.frag16, ws=ws)
+            if self.precision.npass == 3 and not ops.conv_igemm(None, None, None, out, query_rs=True, **kw2):
+                # (a problem the register-streamed 3-product kernel does not take: the fused fp32-source kernel, as before)
+                return ops.conv_igemm(h, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_DOWN, bias=pk.bias)
+            else:
+                ops.space_to_depth16(h, planes, planes_lo, self.precision)
+                return ops.conv_igemm(None, None, None, out, chan_stats=self._cs_new(out), **kw2)
+        else:
+            # fused fp32-source kernel (parity mode / odd sizes)
+            return ops.conv_igemm(h, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_DOWN, bias=pk.bias)
+
+    def _up(self, ltag: str, layer: Upsample, h, nxt, cat_ok, next_skip_c):
+        """Upsample.forward openaimodel.py:124-132: nearest x2 + 3x3 convolution. cat_ok / next_skip_c as in _run_block: as the block's last layer
+        (nxt is None) it may write its output as 16-bit values into the next block's concat plane."""
+        pk = self._packed[id(layer.conv)]
+        B, H, W, _ = h.shape
+        out = self._buf(ltag + ".out", (B, H * 2, W * 2, layer.out_channels))
+        if self._tape is not None:
+            self._tape.append(("up", layer, h, out))
+        pu = self._packed[(id(layer.conv), "up")]
+        src16 = self._raw16.get(h.data_ptr()) or self._norm16(None, 0, h)
+        if not ops.conv3x3_tiles_ok(H, W):
+            # (the sub-pixel form tiles the low-resolution grid) generic shapes: nearest x2 + 3x3 as im2col + flat GEMM from the plain filter
+            return ops.conv_igemm(None, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_UP, src16=src16, bias=pk.bias,
+                                  chan_stats=self._cs_new(out))
+        # statistics slots of the sub-pixel form: (256-pixel run of the low-res grid) x (output parity)
+        # (small grids — a sampling batch of up to 8 — split K over the workspace like the other kinds)
+        ws = self._splitk_ws(out.numel()) if self.precision.npass == 1 else None
+        kwu = dict(prec=self.precision, mode=CONV_UP_SUBPIXEL, src16=src16, bias=pu.bias, w_frag=pu.frag,
+                   chan_stats=self._cs_new(out, 4 * ops.gn_chan_nslab(H * W)), w_frag16=pu.frag16, ws=ws)
+        if cat_ok and nxt is None and ops.gn_apply16c_x16_ok(layer.out_channels, next_skip_c):
+            # the next block's GroupNorm and skip_connection are this tensor's only readers: 16-bit values into its concat's raw plane
+            ncat = layer.out_channels + next_skip_c
+            rawn = self._cat_plane(B, 2 * H, 2 * W, layer.out_channels, ncat)
+            kwc = dict(kwu, out16=(rawn, None), out16_stride=ncat, cout=layer.out_channels)
+            keyc = ("upcat", id(layer), B, H, W, ncat)
+            okc = self._consts.get(keyc)
+            if okc is None:
+                okc = bool(ops.conv_igemm(None, pu.hi, pu.lo, None, query_rs=True, **kwc))
+                self._consts[keyc] = okc
+            if okc:
+                ops.conv_igemm(None, pu.hi, pu.lo, None, **kwc)
+                self._x16[out.data_ptr()] = (rawn, layer.out_channels)
+                return out
+        return ops.conv_igemm(None, pu.hi, pu.lo, out, **kwu)
 
     @staticmethod
     def _first_norm(layer):
@@ -748,7 +785,7 @@ class UNetModel(nn.Module):
         layers = list(blk)
         # (from 8 decoder rows on: at a sampling batch of 1 the 16-bit-only form measured 40.2 against 38.6 ms per DDIM-20 loop - launches
         #  of that size are latency, not bytes)
-        cat_ok = (next_skip_c is not None and self._tape is None and self.conv_path == "dma" and self.precision.npass == 1 and
+        cat_ok = (next_skip_c is not None and self._tape is None and self.precision.npass == 1 and
                   h.shape[0] >= 8 and not os.environ.get("STEDM_NO_CAT16"))
         for li, layer in enumerate(layers, start=li0):
             ltag = f"{tag}.{li}"
@@ -781,69 +818,9 @@ class UNetModel(nn.Module):
                 else:
                     h = layer.run(h, self._packed[id(layer)], self.precision, self._buf)
             elif isinstance(layer, Downsample):
-                pk = self._packed[id(layer.op)]
-                B, H, W, _ = h.shape
-                out = self._buf(ltag + ".out", (B, H // 2, W // 2, layer.out_channels))
-                if self._tape is not None:
-                    self._tape.append(("down", layer, h, out))
-                ps2 = self._packed.get((id(layer.op), "s2d"))
-                if self.conv_path == "dma" and H % 2 == 0 and W % 2 == 0 and not ops.conv3x3_tiles_ok(H // 2, W // 2):
-                    # an output grid the tiled kernels cannot tile (latent widths that are not powers of two): im2col + flat GEMM (ops.conv_igemm)
-                    h = ops.conv_igemm(None, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_DOWN, src16=self._norm16(None, 0, h), bias=pk.bias,
-                                       chan_stats=self._cs_new(out))
-                elif ps2 is not None and H % 2 == 0 and W % 2 == 0 and (H // 2) * (W // 2) >= 16:
-                    C = h.shape[-1]
-                    planes = self._buf(f"s2d16.{B}x{H}x{W}x{C}", (B, H // 2, W // 2, 4 * C), torch.int16)
-                    planes_lo = self._buf(f"s2d16lo.{B}x{H}x{W}x{C}", (B, H // 2, W // 2, 4 * C), torch.int16) if self.precision.npass == 3 else None
-                    ws = self._buf("conv_ws", ((16 if out.numel() <= (1 << 20) else 2) * out.numel(),))
-                    kw2 = dict(prec=self.precision, mode=CONV_S2D, src16=(planes, planes_lo), bias=ps2.bias, w_frag=ps2.frag, w_frag16=ps2.frag16, ws=ws)
-                    if self.precision.npass == 3 and not ops.conv_igemm(None, None, None, out, query_rs=True, **kw2):
-                        # (a problem the register-streamed 3-product kernel does not take: the fused fp32-source kernel, as before)
-                        h = ops.conv_igemm(h, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_DOWN, bias=pk.bias)
-                    else:
-                        ops.space_to_depth16(h, planes, planes_lo, self.precision)
-                        h = ops.conv_igemm(None, None, None, out, chan_stats=self._cs_new(out), **kw2)
-                else:
-                    # fused fp32-source kernel (parity mode / odd sizes)
-                    h = ops.conv_igemm(h, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_DOWN, bias=pk.bias)
+                h = self._down(ltag, layer, h)
             elif isinstance(layer, Upsample):
-                pk = self._packed[id(layer.conv)]
-                B, H, W, _ = h.shape
-                out = self._buf(ltag + ".out", (B, H * 2, W * 2, layer.out_channels))
-                if self._tape is not None:
-                    self._tape.append(("up", layer, h, out))
-                if self.conv_path == "dma":
-                    pu = self._packed[(id(layer.conv), "up")]
-                    src16 = self._raw16.get(h.data_ptr()) or self._norm16(None, 0, h)
-                    if not ops.conv3x3_tiles_ok(H, W):
-                        # (the sub-pixel form tiles the low-resolution grid) generic shapes: nearest x2 + 3x3 as im2col + flat GEMM from the plain filter
-                        h = ops.conv_igemm(None, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_UP, src16=src16, bias=pk.bias,
-                                           chan_stats=self._cs_new(out))
-                        continue
-                    # statistics slots of the sub-pixel form: (256-pixel run of the low-res grid) x (output parity)
-                    # (small grids — a sampling batch of up to 8 — split K over the workspace like the other kinds)
-                    ws = self._buf("conv_ws", ((16 if out.numel() <= (1 << 20) else 2) * out.numel(),)) if self.precision.npass == 1 else None
-                    kwu = dict(prec=self.precision, mode=CONV_UP_SUBPIXEL, src16=src16, bias=pu.bias, w_frag=pu.frag,
-                               chan_stats=self._cs_new(out, 4 * ops.gn_chan_nslab(H * W)), w_frag16=pu.frag16, ws=ws)
-                    done = False
-                    if cat_ok and nxt is None and ops.gn_apply16c_x16_ok(layer.out_channels, next_skip_c):
-                        # the next block's GroupNorm and skip_connection are this tensor's only readers: 16-bit values into its concat's raw plane
-                        ncat = layer.out_channels + next_skip_c
-                        rawn = self._cat_plane(B, 2 * H, 2 * W, layer.out_channels, ncat)
-                        kwc = dict(kwu, out16=(rawn, None), out16_stride=ncat, cout=layer.out_channels)
-                        keyc = ("upcat", id(layer), B, H, W, ncat)
-                        okc = self._consts.get(keyc)
-                        if okc is None:
-                            okc = bool(ops.conv_igemm(None, pu.hi, pu.lo, None, query_rs=True, **kwc))
-                            self._consts[keyc] = okc
-                        if okc:
-                            ops.conv_igemm(None, pu.hi, pu.lo, None, **kwc)
-                            self._x16[out.data_ptr()] = (rawn, layer.out_channels)
-                            h, done = out, True
-                    if not done:
-                        h = ops.conv_igemm(None, pu.hi, pu.lo, out, **kwu)
-                else:
-                    h = ops.conv_igemm(h, pk.hi, pk.lo, out, prec=self.precision, mode=CONV_UP, bias=pk.bias)
+                h = self._up(ltag, layer, h, nxt, cat_ok, next_skip_c)
             else:
                 raise TypeError(f"unexpected layer {type(layer).__name__} in {tag}")
         return h
@@ -952,7 +929,7 @@ class UNetModel(nn.Module):
 
         conv0 = self.input_blocks[0][0]
         h = self._buf("in0.out", (B, H, W, self.model_channels))
-        if self.conv_path == "dma" and H % 2 == 0:
+        if H % 2 == 0:
             cs0 = self._cs_new(h, H // 2)                     # one slot per pair of image rows, from the kernel's epilogue
             if not ops.conv_in(x, c_concat, conv0.weight, conv0.bias, h, chan_stats=cs0):
                 del self._cs[h.data_ptr()]                    # generic path: statistics on first use
@@ -995,7 +972,7 @@ class UNetModel(nn.Module):
         if out is None:
             out = torch.empty((Bd, self.out_channels, H, W), dtype=torch.float32, device=x.device)
         gn = self.out[0]
-        cs = self._chan_stats(h) if self.conv_path == "dma" else None     # left by the last ResBlock's conv epilogue
+        cs = self._chan_stats(h)     # left by the last ResBlock's conv epilogue
         ops.conv_out(h, gn.weight, gn.bias, gn.eps, gn.num_groups, c["out_w_hwio"], self.out[2].bias, out, cs)
         if self._tape is not None:
             self._tape.append(("conv_out", h, out))
