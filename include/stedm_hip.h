@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 20
+#define STEDM_ABI_VERSION 21
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -667,6 +667,29 @@ int stedm_ddpm_step(float* x, const float* eps, const float* table, const int32_
                     const float* mask, long mask_bstride, long mask_cstride, const float* x0, const float* mask_noise,
                     const float* sqrt_ac, const float* sqrt_1mac, int B, int C, int HW, long first_id, unsigned long long seed,
                     unsigned long long mask_seed, void* stream);
+/* The same iteration with the options of the reference's p_sample / p_mean_variance / progressive_denoising (ABI 21; ddpm.py:1050-1166).
+ * Table, mask, strides, sample ids and seeds as stedm_ddpm_step; x is read only, the sample goes to x_out:
+ *   x0 = sr x - srm1 eps;  x0 = clamp(x0, -1, 1) if clip;  x0 = x0 + (e_idx - x0) with a codebook (quantize_denoised, :1071-1072)
+ *   mean = c1 x0 + c2 x;  n = ((z temperature[t]) keep) / (1 - p)   (:1099-1101, each product rounded on its own);  x' = mean + sigma n
+ *   then stedm_ddpm_step's mask blend, unchanged.
+ * t: *step_idx (DEVICE int32), or - exactly one of the two is given - t[b] (DEVICE int64 [B]): one table row per sample, as p_sample
+ * takes it. A t outside [0, T) writes nothing for that sample. temperature: DEVICE fp32 [T] indexed by t (progressive_denoising's
+ * per-timestep list; a captured step serves every t), NULL: 1. noise [B][C][HW], or NULL: z is row first_id + b of stedm_philox_normal
+ * with (seed, stream 0x10000 + t) - stedm_ddpm_step's bits. noise_dropout p in [0, 1): the keep rule of stedm_ddim_step_ex with t in
+ * place of the iteration - element e of sample first_id + b is kept iff u16 >= lrint(p * 65536), u16 = field (e & 7) of
+ * Philox4x32-10(counter {e >> 3, 0x20000 + t, 0x44524F50, 0}, key {seed (low 32 bits), first_id + b}); kept values are scaled by
+ * (float)(1 / (1 - p)) whenever p > 0. The bits are drawn at every t, t = 0 included (sigma is 0 there).
+ * codebook [n_e][C] fp32 (NULL: no quantisation), C in 1..8, any n_e > 0: index and arithmetic are stedm_vq_nearest's on the clamped x0,
+ * bit for bit. It runs as a launch of its own before the update (one thread per latent pixel) and hands the quantised x0 over in x0_out,
+ * which is then required. Outputs, each optional (at least one): x_out [B][C][HW] the sample (NULL: not computed; may be x, in place),
+ * x0_out the predicted x0 after clamp and quantisation, mean_out the posterior mean (before the blend), idx_out int64 [B * HW] the
+ * codebook indices (codebook only). x0_out and mean_out alias no other operand. No allocation and no host read: capturable in a hipGraph.
+ * With temperature NULL, p = 0, no codebook and x_out = x the result equals stedm_ddpm_step bit for bit. */
+int stedm_ddpm_step_ex(const float* x, const float* eps, const float* table, const int32_t* step_idx, const int64_t* t, int T, int clip,
+                       const float* noise, const float* temperature, float noise_dropout, const float* codebook, int n_e,
+                       const float* mask, long mask_bstride, long mask_cstride, const float* x0, const float* mask_noise,
+                       const float* sqrt_ac, const float* sqrt_1mac, float* x_out, float* x0_out, float* mean_out, long long* idx_out,
+                       int B, int C, int HW, long first_id, unsigned long long seed, unsigned long long mask_seed, void* stream);
 
 /* loss = mean|target - pred| (ddpm.py:282-295 'l1' + :1030-1040), d_pred = grad_scale * sign(pred - target) / n (NULL: skip).
  * ws: 1024 doubles. */

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 
@@ -81,6 +81,8 @@ SIGNATURES = {
     "stedm_ddim_mask_blend": (_I, [_P, _P, _P, C.c_long, C.c_long, _P, _P, _P, _P, _P, _I, _I, _I, C.c_long, C.c_ulonglong, _P]),
     "stedm_ddpm_step": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, C.c_long, C.c_long, _P, _P, _P, _P, _I, _I, _I, C.c_long,
                             C.c_ulonglong, C.c_ulonglong, _P]),
+    "stedm_ddpm_step_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _P, _I, _P, C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P, _P,
+                               _I, _I, _I, C.c_long, C.c_ulonglong, C.c_ulonglong, _P]),
     "stedm_gn_apply16c_x16": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _F, _I, _I, _I, _I, _P, _P, _I, _P]),
     "stedm_conv_igemm": (_I, [C.POINTER(ConvArgs), _P]),
     "stedm_conv_fused_skip_ok": (_I, [C.POINTER(ConvArgs)]),

@@ -3,6 +3,7 @@
 
 #include "common.hpp"
 #include "dropmask.hpp"
+#include "ddpm_math.hpp"
 #include "sgemm.hpp"
 
 namespace stedm {
@@ -1475,6 +1476,161 @@ extern "C" int stedm_ddpm_step(float* x, const float* eps, const float* table, c
   else if (masked) STEDM_DDPM_LAUNCH(false, true);
   else STEDM_DDPM_LAUNCH(false, false);
 #undef STEDM_DDPM_LAUNCH
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+// The same iteration with the options of the reference's p_sample / p_mean_variance (ddpm.py:1050-1110; stedm_ddpm_step_ex):
+//   x0   as above; QUANT: read from x0_out, where the pre-pass (ddpm_quantize_x0_launch, vq.hip) left the nearest codebook rows
+//   n    = ((z temperature[t]) keep) / (1 - p)             :1099-1101, each product rounded on its own (ddpm_math.hpp)
+//   x'   = mean + sigma[t] n, then the blend above
+// t = *step_idx, or tv[b] (one table row per sample). The keep bits of a thread's four elements 4 g .. 4 g + 3 are fields 4 (g & 1) + j of
+// one Philox block (counter {g >> 1, 0x20000 + t, "DROP", 0}: ddim_drop_keep's rule with t for the iteration). Optional outputs: x0_out
+// (after clamp and quantisation), mean_out, x_out (NULL: the sample is not written; may be x). Launch and layout: those of
+// ddpm_step_kernel, whose expressions these are, so with every option off the result is the same bits.
+struct DdpmEx {
+  const int64_t* tv;
+  const float* temperature;  // [T] indexed by t; NULL: 1
+  float drop_scale;          // (float)(1 / (1 - p))
+  uint32_t thr16;
+  int drop;                  // p > 0 (thr16 may still be 0: every element kept, and scaled)
+  float* x_out;
+  float* x0_out;
+  float* mean_out;
+};
+
+template <bool VEC, bool MASK, bool QUANT>
+__global__ void __launch_bounds__(256) ddpm_step_ex_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ table,
+                                                           const int32_t* __restrict__ step_idx, int T, int clip, const float* __restrict__ noise,
+                                                           const float* __restrict__ mask, long mbs, long mcs, const float* __restrict__ x0m,
+                                                           const float* __restrict__ mnoise, const float* __restrict__ sa, const float* __restrict__ s1,
+                                                           int C, int HW, unsigned id0, unsigned seed, unsigned mseed, DdpmEx ex) {
+  const int b = blockIdx.y;
+  const int n = C * HW;
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (4 * g >= n) return;
+  const long long tl = ex.tv ? (long long)ex.tv[b] : (long long)*step_idx;
+  if (tl < 0 || tl >= T) return;
+  const int t = (int)tl;
+  const float* row = table + (long)t * 5;
+  const float sr = row[0], srm1 = row[1], c1 = row[2], c2 = row[3], sig = row[4];
+  const float temp = ex.temperature ? ex.temperature[t] : 1.0f;
+  const long base = (long)b * n;
+  auto ld = [&](const float* p, float (&v)[4]) {
+    if (VEC) {
+      const float4 q = *reinterpret_cast<const float4*>(p + base + 4 * g);
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = 4 * g + j < n ? p[base + 4 * g + j] : 0.0f;
+    }
+  };
+  auto st = [&](float* p, const float (&v)[4]) {
+    if (VEC) {
+      *reinterpret_cast<float4*>(p + base + 4 * g) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * g + j < n) p[base + 4 * g + j] = v[j];
+    }
+  };
+  float xv[4], q[4], z[4], mean[4], o[4];
+  ld(x, xv);
+  if (QUANT) {
+    ld(ex.x0_out, q);
+  } else {
+    float ev[4];
+    ld(eps, ev);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = ddpm_predict_x0(xv[j], ev[j], sr, srm1, clip != 0);
+    if (ex.x0_out) st(ex.x0_out, q);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) mean[j] = ddpm_posterior_mean(q[j], xv[j], c1, c2);
+  if (ex.mean_out) st(ex.mean_out, mean);
+  if (!ex.x_out) return;
+  if (noise) ld(noise, z);
+  else philox_normal4((unsigned)g, 0x10000u + (unsigned)t, seed, id0 + (unsigned)b, z);
+  float ks[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+  if (ex.drop) {
+    const U4 r = philox4x32_10(U4{(uint32_t)g >> 1, 0x20000u + (uint32_t)t, DDIM_DROP_WORD, 0u}, seed, id0 + (unsigned)b);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ks[j] = drop_u16(r, 4 * (g & 1) + j) >= ex.thr16 ? ex.drop_scale : 0.0f;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = ddpm_add_noise(mean[j], sig, ddpm_shaped_noise(z[j], temp, ks[j]));
+  if (MASK) {
+    const float ca = sa[t], cn = s1[t];
+    float xk[4], m[4], zb[4];
+    ld(x0m, xk);
+    if (mnoise) ld(mnoise, zb);
+    else philox_normal4((unsigned)g, 0x8000u + (unsigned)t, mseed, id0 + (unsigned)b, zb);
+    if (VEC) {                                          // HW % 4 == 0: the group lies in one channel plane
+      const int c = (4 * g) / HW, p = 4 * g - c * HW;
+      const float4 w = *reinterpret_cast<const float4*>(mask + b * mbs + c * mcs + p);
+      m[0] = w.x; m[1] = w.y; m[2] = w.z; m[3] = w.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = 4 * g + j;
+        const bool in = e < n;
+        const int c = in ? e / HW : 0, p = in ? e - c * HW : 0;
+        m[j] = in ? mask[b * mbs + c * mcs + p] : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = ddpm_blend1(o[j], xk[j], zb[j], m[j], ca, cn);
+  }
+  st(ex.x_out, o);
+}
+
+extern "C" int stedm_ddpm_step_ex(const float* x, const float* eps, const float* table, const int32_t* step_idx, const int64_t* t, int T, int clip,
+                                  const float* noise, const float* temperature, float noise_dropout, const float* codebook, int n_e,
+                                  const float* mask, long mask_bstride, long mask_cstride, const float* x0, const float* mask_noise,
+                                  const float* sqrt_ac, const float* sqrt_1mac, float* x_out, float* x0_out, float* mean_out, long long* idx_out,
+                                  int B, int C, int HW, long first_id, unsigned long long seed, unsigned long long mask_seed, void* stream) {
+  STEDM_CHECK_ARG(x && eps && table, "ddpm_step_ex: null pointer");
+  STEDM_CHECK_ARG((step_idx != nullptr) != (t != nullptr), "ddpm_step_ex: give the device step index or the per-sample t, not both");
+  STEDM_CHECK_ARG(T > 0, "ddpm_step_ex: bad table length %d", T);
+  STEDM_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && HW > 0 && (long)C * HW <= 0x7FFFFFFFL, "ddpm_step_ex: bad shape B=%d C=%d HW=%d", B, C, HW);
+  STEDM_CHECK_ARG(first_id >= 0 && first_id + B <= (1L << 32), "ddpm_step_ex: sample ids %ld + %d outside [0, 2^32]", first_id, B);
+  STEDM_CHECK_ARG(noise_dropout >= 0.0f && noise_dropout < 1.0f, "ddpm_step_ex: noise_dropout %g outside [0, 1)", (double)noise_dropout);
+  STEDM_CHECK_ARG(x_out || x0_out || mean_out || (codebook && idx_out), "ddpm_step_ex: no output");
+  const bool quant = codebook != nullptr;
+  STEDM_CHECK_ARG(quant || !idx_out, "ddpm_step_ex: idx_out without a codebook");
+  STEDM_CHECK_ARG(!quant || (x0_out && x0_out != x && x0_out != eps),
+                  "ddpm_step_ex: with a codebook x0_out is required (the quantised x0 passes through it) and may alias neither x nor eps");
+  const bool masked = mask != nullptr;
+  STEDM_CHECK_ARG(!masked || (x0 && sqrt_ac && sqrt_1mac), "ddpm_step_ex: the mask blend needs x0, sqrt_ac and sqrt_1mac");
+  STEDM_CHECK_ARG(!masked || mask_cstride == 0 || mask_cstride == HW, "ddpm_step_ex: mask channel stride %ld (0 or HW=%d)", mask_cstride, HW);
+  STEDM_CHECK_ARG(!masked || mask_bstride == 0 || mask_bstride == (mask_cstride ? (long)C * HW : (long)HW),
+                  "ddpm_step_ex: mask batch stride %ld (0 or the mask's per-sample size)", mask_bstride);
+  hipStream_t st = as_stream(stream);
+  if (quant) {
+    const int rc = ddpm_quantize_x0_launch(x, eps, table, step_idx, t, T, clip, codebook, n_e, C, B, (long)HW, x0_out, idx_out, st);
+    if (rc) return rc;
+  }
+  const int n = C * HW;
+  const bool aligned = ((uintptr_t)x | (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)mask | (uintptr_t)x0 | (uintptr_t)mask_noise |
+                        (uintptr_t)x_out | (uintptr_t)x0_out | (uintptr_t)mean_out) % 16 == 0;
+  const bool vec = HW % 4 == 0 && aligned;
+  dim3 grid(((n + 3) / 4 + 255) / 256, B);
+  const unsigned id0 = (unsigned)first_id, sd = (unsigned)(seed & 0xFFFFFFFFull), msd = (unsigned)(mask_seed & 0xFFFFFFFFull);
+  const bool drop = noise_dropout > 0.0f;
+  const DdpmEx ex{t, temperature, (float)(1.0 / (1.0 - (double)noise_dropout)), (uint32_t)lrint((double)noise_dropout * 65536.0), drop ? 1 : 0,
+                  x_out, x0_out, mean_out};
+#define STEDM_DDPM_EX_LAUNCH(V, M, Q)                                                                                                    \
+  ddpm_step_ex_kernel<V, M, Q><<<grid, 256, 0, st>>>(x, eps, table, step_idx, T, clip, noise, mask, mask_bstride, mask_cstride, x0,       \
+                                                     mask_noise, sqrt_ac, sqrt_1mac, C, HW, id0, sd, msd, ex)
+#define STEDM_DDPM_EX_VM(Q)                             \
+  if (vec && masked) STEDM_DDPM_EX_LAUNCH(true, true, Q);   \
+  else if (vec) STEDM_DDPM_EX_LAUNCH(true, false, Q);       \
+  else if (masked) STEDM_DDPM_EX_LAUNCH(false, true, Q);    \
+  else STEDM_DDPM_EX_LAUNCH(false, false, Q)
+  if (quant) { STEDM_DDPM_EX_VM(true); }
+  else { STEDM_DDPM_EX_VM(false); }
+#undef STEDM_DDPM_EX_VM
+#undef STEDM_DDPM_EX_LAUNCH
   STEDM_LAUNCH_CHECK();
   return 0;
 }

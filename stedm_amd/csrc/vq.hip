@@ -4,12 +4,15 @@
 //                    the straight-through output z + (e - z)
 //   ddim_quantize_x0 p_sample_ddim's quantize_denoised (ldm/models/diffusion/ddim.py:201-203) inside a DDIM step: pred_x0 snapped to the
 //                    codebook with vq_nearest's arithmetic, x_prev recomputed from it
+//   ddpm_quantize    p_mean_variance's quantize_denoised (ldm/models/diffusion/ddpm.py:1071-1072), the first launch of stedm_ddpm_step_ex with a
+//                    codebook: the predicted x0 of an ancestral step snapped to the codebook, again with vq_nearest's arithmetic
 //   conv1x1_nchw     quant_conv / post_quant_conv (autoencoder.py:42-43): 1x1 convolutions over a handful of channels, NCHW
 //   softmax_rows16   the softmax of AttnBlock (ldm/modules/diffusionmodules/model.py:143-199: single head of width C, logits scaled by
 //                    C^-0.5) written as 16-bit operand planes for the P @ V GEMM
 //   nearest-codebook arithmetic is written WITHOUT fused multiply-adds and in a fixed order (the index is an integer
 //   result and must not depend on contraction choices of the compiler)
 #include "common.hpp"
+#include "ddpm_math.hpp"
 using namespace stedm;
 
 namespace {
@@ -131,6 +134,36 @@ __global__ void __launch_bounds__(256) ddim_quantize_kernel(float* __restrict__ 
   }
 }
 
+// quantize_denoised of p_mean_variance (ddpm.py:1071-1072), the first launch of stedm_ddpm_step_ex with a codebook: per latent pixel, the
+// predicted x0 of row t of the DDPM table (ddpm_predict_x0: the update kernel's expression) -> z + (e - z) of its nearest entry
+// (vq_nearest_index) into x0_out, which the update kernel then reads instead of predicting x0 again. t = *step_idx, or tv[b]; a t outside
+// [0, T) writes nothing (the thread still helps to stage the codebook tiles). One thread per pixel over the whole batch.
+template <int E>
+__global__ void __launch_bounds__(256) ddpm_quantize_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ table,
+                                                            const int32_t* __restrict__ step_idx, const int64_t* __restrict__ tv, int T, int clip,
+                                                            const float* __restrict__ cb, int n_e, long npix, long HW, float* __restrict__ x0_out,
+                                                            long long* __restrict__ idx_out) {
+  __shared__ float scb[VQ_TILE][E + 1];
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  bool live = p < npix;
+  const long b = live ? p / HW : 0, hw = live ? p - b * HW : 0;
+  const long long t = tv ? (long long)tv[b] : (long long)*step_idx;
+  live = live && t >= 0 && t < T;
+  const float* row = table + (live ? t : 0) * 5;
+  const float sr = row[0], srm1 = row[1];
+  float zv[E];
+#pragma unroll
+  for (int c = 0; c < E; ++c) {
+    const long o = (b * E + c) * HW + hw;
+    zv[c] = live ? ddpm_predict_x0(x[o], eps[o], sr, srm1, clip != 0) : 0.f;
+  }
+  const int bi = vq_nearest_index<E>(zv, live, cb, n_e, scb);
+  if (!live) return;
+  if (idx_out) idx_out[p] = bi;
+#pragma unroll
+  for (int c = 0; c < E; ++c) x0_out[(b * E + c) * HW + hw] = vq_straight_through(zv[c], cb[(long)bi * E + c]);
+}
+
 // out[b][co][p] = bias[co] + sum_ci w[co][ci] * x[b][ci][p]; cin, cout <= 16
 __global__ void __launch_bounds__(256) conv1x1_nchw_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                            float* __restrict__ out, int cin, int cout, long HW, long npix) {
@@ -200,6 +233,21 @@ extern "C" int stedm_ddim_quantize_x0(float* pred_x0, const float* eps, const fl
   hipStream_t st = as_stream(stream);
   switch (e_dim) {
 #define CASE(E) case E: ddim_quantize_kernel<E><<<grid, 256, 0, st>>>(pred_x0, eps, noise, coefs, step_idx, codebook, n_e, npix, HW, x_prev, idx); break;
+    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+  }
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+int stedm::ddpm_quantize_x0_launch(const float* x, const float* eps, const float* table, const int32_t* step_idx, const int64_t* t, int T, int clip,
+                                   const float* codebook, int n_e, int e_dim, int B, long HW, float* x0_out, long long* idx_out, hipStream_t st) {
+  STEDM_CHECK_ARG(x && eps && table && (step_idx || t) && codebook && x0_out && n_e > 0 && B > 0 && HW > 0, "ddpm_step_ex: bad quantiser args");
+  STEDM_CHECK_ARG(e_dim >= 1 && e_dim <= VQ_MAXE, "ddpm_step_ex: embedding width %d unsupported (1..%d)", e_dim, VQ_MAXE);
+  const long npix = (long)B * HW;
+  const int grid = (int)((npix + 255) / 256);
+  switch (e_dim) {
+#define CASE(E) case E: ddpm_quantize_kernel<E><<<grid, 256, 0, st>>>(x, eps, table, step_idx, t, T, clip, codebook, n_e, npix, HW, x0_out, idx_out); break;
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
   }

@@ -3,7 +3,9 @@
   DiffusionWrapper   ddpm.py:1398-1424  (hybrid conditioning: cat([x]+c_concat,1), cat(c_crossattn,1))
   LatentDiffusion    ddpm.py:424-…     subset on the hot path: register_schedule :120-172, q_sample :277-280,
                                         apply_model :894-995 (live lines), p_losses :1015-1048 (forward value),
-                                        sample_log :1237-1250, get_learned_conditioning :554-565
+                                        sample_log :1237-1250, get_learned_conditioning :554-565, the DDPM sampling surface
+                                        q_mean_variance / predict_start_from_noise / q_posterior :207-232, p_mean_variance / p_sample /
+                                        progressive_denoising / p_sample_loop / sample :1050-1235 (stedm_amd/ancestral.py)
 Training seam (what `LDM_Diffusion.training_step` drives, modules/ldm_diffusion.py:63-73): `training_step(batch, batch_idx)` ->
 `shared_step` -> `get_input` + `forward(x, c)` (t ~ U{0..T-1}) -> `p_losses`, and the `on_train_batch_start/end` hooks
 (ddpm.py:345-371, 479-494, 868-882). In training mode with autograd enabled `p_losses` returns a loss tensor whose `backward()`
@@ -713,7 +715,8 @@ class LatentDiffusion(nn.Module):
                mask=None, x0=None, shape=None, **kwargs):
         """ddpm.py:1219-1235: the ancestral chain (stedm_amd/ancestral.py, AncestralSampler.sample). Keywords the reference swallows are
         ignored (log_every_t, verbose, ddim_steps, callbacks), except those whose effect it drops, which raise: eta != 0, temperature,
-        noise_dropout, score_corrector, quantize_denoised, and guidance (unconditional_guidance_scale != 1 with unconditional_conditioning).
+        noise_dropout (both are progressive_denoising's), score_corrector, and guidance (unconditional_guidance_scale != 1 with
+        unconditional_conditioning). quantize_denoised snaps every step's predicted x0 to the VQ first stage's codebook.
         Repo keywords: noises, noise_seed, sample_id0, mask_noises, mask_seed (AncestralSampler.p_sample_loop)."""
         return AncestralSampler(self, use_graph=self.use_graph).sample(cond, batch_size=batch_size, return_intermediates=return_intermediates,
                                                                        x_T=x_T, verbose=verbose, timesteps=timesteps,
@@ -728,6 +731,50 @@ class LatentDiffusion(nn.Module):
             cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, callback=callback, timesteps=timesteps,
             quantize_denoised=quantize_denoised, mask=mask, x0=x0, img_callback=img_callback, start_T=start_T, log_every_t=log_every_t,
             **kwargs)
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False, img_callback=None, mask=None,
+                              x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, batch_size=None,
+                              x_T=None, start_T=None, log_every_t=None, **kwargs):
+        """ddpm.py:1112-1166 on the HIP path (AncestralSampler.progressive_denoising; kwargs: its repo keywords) -> (img, the list of the
+        logged steps' predicted x0). The one place where the ancestral chain honours temperature (a number or a per-timestep list) and
+        noise_dropout."""
+        return AncestralSampler(self, use_graph=self.use_graph).progressive_denoising(
+            cond, shape, verbose=verbose, callback=callback, quantize_denoised=quantize_denoised, img_callback=img_callback, mask=mask,
+            x0=x0, temperature=temperature, noise_dropout=noise_dropout, score_corrector=score_corrector,
+            corrector_kwargs=corrector_kwargs, batch_size=batch_size, x_T=x_T, start_T=start_T, log_every_t=log_every_t, **kwargs)
+
+    @torch.no_grad()
+    def p_mean_variance(self, x, c, t, clip_denoised: bool, return_codebook_ids=False, quantize_denoised=False, return_x0=False,
+                        score_corrector=None, corrector_kwargs=None):
+        """ddpm.py:1050-1079 (AncestralSampler.p_mean_variance): t int64 [B], may differ per sample."""
+        return AncestralSampler(self).p_mean_variance(x, c, t, clip_denoised, return_codebook_ids=return_codebook_ids,
+                                                      quantize_denoised=quantize_denoised, return_x0=return_x0,
+                                                      score_corrector=score_corrector, corrector_kwargs=corrector_kwargs)
+
+    @torch.no_grad()
+    def p_sample(self, x, c, t, clip_denoised=False, repeat_noise=False, return_codebook_ids=False, quantize_denoised=False,
+                 return_x0=False, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, _noise=None,
+                 noise_seed=None, sample_id0=0):
+        """ddpm.py:1081-1110 (AncestralSampler.p_sample): one ancestral step at the per-sample timesteps t -> x_prev or (x_prev, x0).
+        Repo keywords: _noise (the step's N(0, 1) draw), else noise_seed / sample_id0 (the in-kernel draw)."""
+        return AncestralSampler(self).p_sample(x, c, t, clip_denoised=clip_denoised, repeat_noise=repeat_noise,
+                                               return_codebook_ids=return_codebook_ids, quantize_denoised=quantize_denoised,
+                                               return_x0=return_x0, temperature=temperature, noise_dropout=noise_dropout,
+                                               score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, _noise=_noise,
+                                               noise_seed=noise_seed, sample_id0=sample_id0)
+
+    def q_posterior(self, x_start, x_t, t):
+        """ddpm.py:225-232 -> (posterior_mean, posterior_variance, posterior_log_variance_clipped)."""
+        return AncestralSampler(self).q_posterior(x_start, x_t, t)
+
+    def predict_start_from_noise(self, x_t, t, noise):
+        """ddpm.py:219-223."""
+        return AncestralSampler(self).predict_start_from_noise(x_t, t, noise)
+
+    def q_mean_variance(self, x_start, t):
+        """ddpm.py:207-217 -> (mean, variance, log_variance)."""
+        return AncestralSampler(self).q_mean_variance(x_start, t)
 
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):

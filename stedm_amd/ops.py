@@ -1103,6 +1103,90 @@ def ddpm_step(x: torch.Tensor, eps: torch.Tensor, table: torch.Tensor, step_idx:
     return x
 
 
+def ddpm_step_ex(x: torch.Tensor, eps: torch.Tensor, table: torch.Tensor, step_idx: Optional[torch.Tensor] = None,
+                 t: Optional[torch.Tensor] = None, clip_denoised: bool = True, noise: Optional[torch.Tensor] = None,
+                 temperature: Optional[torch.Tensor] = None, noise_dropout: float = 0.0, codebook: Optional[torch.Tensor] = None,
+                 seed: int = 0, first_id: int = 0, mask: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None,
+                 mask_noise: Optional[torch.Tensor] = None, mask_seed: int = 0, sqrt_ac: Optional[torch.Tensor] = None,
+                 sqrt_1mac: Optional[torch.Tensor] = None, x_out: Optional[torch.Tensor] = None, x0_out: Optional[torch.Tensor] = None,
+                 mean_out: Optional[torch.Tensor] = None, idx_out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """ddpm_step with the options of the reference's p_sample / p_mean_variance (stedm_ddpm_step_ex): the timestep is step_idx[0] (device
+    int32 [1]) or, exactly one of the two, t (device int64 [B], one table row per sample); x0 is snapped to `codebook` [n_e, C] (the
+    indices and arithmetic of vq_nearest) when given; noise = ((z temperature[t]) keep) / (1 - noise_dropout) with temperature a device
+    fp32 [T] table (None: 1) and the keep bits drawn from (seed, first_id + b, t) - see include/stedm_hip.h. x is read only: the sample
+    goes to x_out (None: not computed; may be x), the predicted x0 after clamp and quantisation to x0_out (required with a codebook),
+    the posterior mean to mean_out, the codebook indices to idx_out (int64, B h w elements). Mask arguments as ddpm_step. Returns x_out."""
+    _chk(x, name="x"); _chk(eps, name="eps"); _chk(table, name="table")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, C, h, w], got {tuple(x.shape)}")
+    B, Cc, H, W = x.shape
+    shp = tuple(x.shape)
+    for v, nm in ((eps, "eps"), (noise, "noise"), (x0, "x0"), (mask_noise, "mask_noise"), (x_out, "x_out"), (x0_out, "x0_out"),
+                  (mean_out, "mean_out")):
+        if v is not None:
+            _chk(v, name=nm)
+            if tuple(v.shape) != shp:
+                raise ValueError(f"{nm} {tuple(v.shape)} must have x's shape {shp}")
+    if table.dim() != 2 or table.shape[1] != 5:
+        raise ValueError(f"table must be [T, 5], got {tuple(table.shape)}")
+    T = int(table.shape[0])
+    if (step_idx is None) == (t is None):
+        raise ValueError("give step_idx (device int32 [1]) or t (device int64 [B]), not both")
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+        if tuple(step_idx.shape) != (1,):
+            raise ValueError(f"step_idx must be [1], got {tuple(step_idx.shape)}")
+    else:
+        _chk(t, torch.int64, "t")
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"t must be [B] = [{B}], got {tuple(t.shape)}")
+    if temperature is not None:
+        _chk(temperature, name="temperature")
+        if temperature.dim() != 1 or temperature.shape[0] < T:
+            raise ValueError(f"temperature must hold a value for every row of the table ([{T}]), got {tuple(temperature.shape)}")
+    if not 0.0 <= float(noise_dropout) < 1.0:
+        raise ValueError(f"noise_dropout {noise_dropout} outside [0, 1)")
+    if codebook is not None:
+        _chk(codebook, name="codebook")
+        if codebook.dim() != 2 or codebook.shape[1] != Cc or codebook.shape[0] < 1:
+            raise ValueError(f"codebook {tuple(codebook.shape)} must be [n_e, {Cc}]")
+        if x0_out is None:
+            raise ValueError("with a codebook x0_out is required (the quantised x0 passes through it)")
+    elif idx_out is not None:
+        raise ValueError("idx_out without a codebook")
+    if idx_out is not None:
+        _chk(idx_out, torch.int64, "idx_out")
+        if idx_out.numel() != B * H * W:
+            raise ValueError(f"idx_out must hold {B * H * W} indices, got {idx_out.numel()}")
+    if x_out is None and x0_out is None and mean_out is None and idx_out is None:
+        raise ValueError("no output requested")
+    for v, nm in ((x0_out, "x0_out"), (mean_out, "mean_out")):
+        if v is not None and any(v.data_ptr() == o.data_ptr() for o in (x, eps) if o is not None):
+            raise ValueError(f"{nm} may not alias x or eps")
+    HW = H * W
+    bstride = cstride = 0
+    if mask is not None:
+        _chk(mask, name="mask")
+        if x0 is None or sqrt_ac is None or sqrt_1mac is None:
+            raise ValueError("the mask blend needs x0, sqrt_ac and sqrt_1mac")
+        _chk(sqrt_ac, name="sqrt_ac"); _chk(sqrt_1mac, name="sqrt_1mac")
+        if sqrt_ac.numel() < T or sqrt_1mac.numel() < T:
+            raise ValueError("sqrt_ac / sqrt_1mac must hold a value for every row of the table")
+        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cc) or tuple(mask.shape[2:]) != (H, W):
+            raise ValueError(f"mask {tuple(mask.shape)} must be [B|1, 1|C, h, w] for x {shp}")
+        cstride = HW if mask.shape[1] == Cc else 0
+        bstride = 0 if mask.shape[0] == 1 else mask.shape[1] * HW
+    mk = mask is not None
+    check(lib().stedm_ddpm_step_ex(x.data_ptr(), eps.data_ptr(), table.data_ptr(), _ptr(step_idx), _ptr(t), T, 1 if clip_denoised else 0,
+                                   _ptr(noise), _ptr(temperature), float(noise_dropout), _ptr(codebook),
+                                   0 if codebook is None else int(codebook.shape[0]), _ptr(mask), bstride, cstride,
+                                   _ptr(x0) if mk else None, _ptr(mask_noise) if mk else None, _ptr(sqrt_ac) if mk else None,
+                                   _ptr(sqrt_1mac) if mk else None, _ptr(x_out), _ptr(x0_out), _ptr(mean_out), _ptr(idx_out), B, Cc, HW,
+                                   int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, int(mask_seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
+          "stedm_ddpm_step_ex")
+    return x_out
+
+
 def step_advance(step_idx: torch.Tensor, delta: int = 1) -> None:
     check(lib().stedm_step_advance(step_idx.data_ptr(), delta, _stream()), "stedm_step_advance")
 
