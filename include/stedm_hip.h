@@ -662,7 +662,8 @@ int stedm_ddim_mask_blend(float* img, const float* x0, const float* mask, long m
  * first_id + b of stedm_philox_normal with (seed, stream 0x10000 + t). mask (optional; strides as stedm_ddim_mask_blend): after the
  * step, x = (sqrt_ac[t] x0 + sqrt_1mac[t] z') mask + (1 - mask) x with the given x0 [B][C][HW]; z' = mask_noise, or row first_id + b with
  * (mask_seed, stream 0x8000 + t) - bit for bit the step followed by stedm_ddim_mask_blend at index t (the blend is that kernel's
- * arithmetic). The step rounds each product and sum once. */
+ * arithmetic). The step rounds each product and sum once. This is stedm_ddpm_step_ex with its options off: t NULL, temperature NULL,
+ * p = 0, no codebook, x_out = x, no x0_out / mean_out - one kernel serves both entries. */
 int stedm_ddpm_step(float* x, const float* eps, const float* table, const int32_t* step_idx, int T, int clip, const float* noise,
                     const float* mask, long mask_bstride, long mask_cstride, const float* x0, const float* mask_noise,
                     const float* sqrt_ac, const float* sqrt_1mac, int B, int C, int HW, long first_id, unsigned long long seed,
@@ -684,7 +685,8 @@ int stedm_ddpm_step(float* x, const float* eps, const float* table, const int32_
  * which is then required. Outputs, each optional (at least one): x_out [B][C][HW] the sample (NULL: not computed; may be x, in place),
  * x0_out the predicted x0 after clamp and quantisation, mean_out the posterior mean (before the blend), idx_out int64 [B * HW] the
  * codebook indices (codebook only). x0_out and mean_out alias no other operand. No allocation and no host read: capturable in a hipGraph.
- * With temperature NULL, p = 0, no codebook and x_out = x the result equals stedm_ddpm_step bit for bit. */
+ * With temperature NULL, p = 0, no codebook and x_out = x this is stedm_ddpm_step: the same kernel, so the same bits (the temperature 1 and
+ * the keep scale 1 multiply exactly). */
 int stedm_ddpm_step_ex(const float* x, const float* eps, const float* table, const int32_t* step_idx, const int64_t* t, int T, int clip,
                        const float* noise, const float* temperature, float noise_dropout, const float* codebook, int n_e,
                        const float* mask, long mask_bstride, long mask_cstride, const float* x0, const float* mask_noise,

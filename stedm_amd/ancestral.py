@@ -5,17 +5,16 @@ t = timesteps - 1 ... 0 of the model's schedule, one model evaluation per step, 
 (x_T, then x after every step i with i % log_every_t == 0 or i == timesteps - 1). Every tensor operation of the loop runs in HIP kernels:
   * the model call -> `apply_model(x, t, cond, out=eps, uniform_t=True)` (no guidance: the reference's ancestral path has none);
   * predict_start_from_noise, the clamp (clip_denoised), q_posterior's mean, the posterior noise sigma_t z and, with a mask, the blend
-    with q_sample(x0, t) after the step (ddpm.py:1207-1209) -> one fused kernel (stedm_ddpm_step) from a device table [T][5]
+    with q_sample(x0, t) after the step (ddpm.py:1207-1209) -> one fused kernel (stedm_ddpm_step_ex) from a device table [T][5]
     {sr, srm1, c1, c2, sigma} (schedule.ddpm_step_table); its noise is drawn in the kernel from (noise_seed, global sample id) on stream
     0x10000 + t, the blend's from (mask_seed, global sample id) on stream 0x8000 + t, so a sample does not depend on the shard;
   * with `use_graph=True` the first step runs eagerly (it also packs the weights and allocates every buffer) and one step {t from the
-    device counter, model call into a preallocated eps, stedm_ddpm_step, counter - 1} is captured once in a hipGraph and replayed for the
+    device counter, model call into a preallocated eps, stedm_ddpm_step_ex, counter - 1} is captured once in a hipGraph and replayed for the
     remaining timesteps - 1 steps (the pattern of ddim.StepGraph);
   * quantize_denoised (ddpm.py:1071-1072), and `progressive_denoising` (ddpm.py:1112-1166) with its temperature (a number or a
     per-timestep list), noise_dropout and x0-prediction log, and the single steps `p_sample` / `p_mean_variance` (:1050-1110) at a
-    per-sample t -> stedm_ddpm_step_ex, the same update with those options (the temperature as a device table indexed by t, the keep bits
-    of the dropout drawn in the kernel from (noise_seed, global sample id, t)), eager and graphed alike. A call without options keeps
-    stedm_ddpm_step.
+    per-sample t -> the same kernel's options (the temperature as a device table indexed by t, the keep bits of the dropout drawn in the
+    kernel from (noise_seed, global sample id, t)), eager and graphed alike.
 """
 from __future__ import annotations
 
@@ -24,7 +23,7 @@ import numbers
 import torch
 
 from . import ops
-from .ddim import DDIMSampler
+from .ddim import DDIMSampler, first_stage_codebook
 from .schedule import ddpm_step_table
 
 
@@ -39,7 +38,7 @@ def _slice_cond(cond, batch_size):
 
 
 def step_table(model) -> torch.Tensor:
-    """The device table [T][5] of stedm_ddpm_step from the model's fp32 buffers (built on the CPU: schedule.ddpm_step_table)."""
+    """The device table [T][5] of stedm_ddpm_step_ex from the model's fp32 buffers (built on the CPU: schedule.ddpm_step_table)."""
     tab = ddpm_step_table(*(getattr(model, n).detach().cpu() for n in ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
                                                                        "posterior_mean_coef1", "posterior_mean_coef2",
                                                                        "posterior_log_variance_clipped")))
@@ -47,7 +46,7 @@ def step_table(model) -> torch.Tensor:
 
 
 class _ExOpts:
-    """What stedm_ddpm_step_ex takes beyond stedm_ddpm_step: the temperature table (device fp32 [T] indexed by t, or None for 1), the
+    """The options of stedm_ddpm_step_ex a run sets: the temperature table (device fp32 [T] indexed by t, or None for 1), the
     noise dropout and the codebook of quantize_denoised (or None)."""
 
     def __init__(self, temperature, noise_dropout, codebook):
@@ -122,19 +121,11 @@ class AncestralSampler(object):
         return size, noises, masking
 
     def _codebook(self, shape):
-        """The first stage's codebook [n_e, C] fp32 on the model's device for quantize_denoised, taken as DDIMSampler._codebook takes it:
-        NotImplementedError without a VQ first stage, ValueError when its width is not the latents' channel count - both before any
-        device work."""
+        """first_stage_codebook for quantize_denoised at the latents' shape (B, C, H, W); raises before any device work."""
         size = tuple(shape)
         if len(size) != 4:
             raise ValueError(f"shape must be (B, C, H, W), got {size}")
-        emb = getattr(getattr(getattr(self.model, "first_stage_model", None), "quantize", None), "embedding", None)
-        if emb is None:
-            raise NotImplementedError("quantize_denoised needs a VQ first stage (first_stage_model.quantize.embedding)")
-        w = emb.weight
-        if w.dim() != 2 or int(w.shape[1]) != int(size[1]):
-            raise ValueError(f"quantize_denoised: codebook {tuple(w.shape)} has width {w.shape[-1]}, the latents have {size[1]} channels")
-        return w.detach().to(self.model.device).float().contiguous()
+        return first_stage_codebook(self.model, size[1], "quantize_denoised")
 
     def _temperature_table(self, temperature, T):
         """progressive_denoising's temperature (ddpm.py:1142-1143, 1155) as host floats indexed by t over the whole schedule: a number
@@ -393,8 +384,8 @@ def cached_step_table(model) -> torch.Tensor:
 
 class AncestralStepGraph:
     """The loop's device state: the step table, the step counter (= t), the t buffer, a preallocated eps; `step` = {t from the counter,
-    model call, stedm_ddpm_step (with opts: stedm_ddpm_step_ex, the predicted x0 left in x0_pred), counter - 1}, capturable once in a
-    hipGraph and replayed (the pattern of ddim.StepGraph). opts: _ExOpts (temperature table on the device) or None."""
+    model call, stedm_ddpm_step_ex (with opts: the predicted x0 left in x0_pred), counter - 1}, capturable once in a hipGraph and
+    replayed (the pattern of ddim.StepGraph). opts: _ExOpts (temperature table on the device) or None for the plain step."""
 
     def __init__(self, model, img, cond, table, clip, seed, first_id, masking, opts=None):
         self.m, self.img, self.cond, self.table, self.clip = model, img, cond, table, clip
@@ -421,12 +412,10 @@ class AncestralStepGraph:
             m = self.m
             kw = dict(mask=mk["mask"], x0=mk["x0"], mask_noise=mask_noise, mask_seed=mk["mask_seed"] or 0,
                       sqrt_ac=m.sqrt_alphas_cumprod, sqrt_1mac=m.sqrt_one_minus_alphas_cumprod)
-        if o is None:
-            ops.ddpm_step(self.img, eps, self.table, step_idx, self.clip, noise=noise, seed=self.seed, first_id=self.first_id, **kw)
-        else:
-            ops.ddpm_step_ex(self.img, eps, self.table, step_idx=step_idx, clip_denoised=self.clip, noise=noise,
-                             temperature=o.temperature, noise_dropout=o.noise_dropout, codebook=o.codebook, seed=self.seed,
-                             first_id=self.first_id, x_out=self.img, x0_out=self.x0_pred, **kw)
+        if o is not None:
+            kw.update(temperature=o.temperature, noise_dropout=o.noise_dropout, codebook=o.codebook, x0_out=self.x0_pred)
+        ops.ddpm_step_ex(self.img, eps, self.table, step_idx=step_idx, clip_denoised=self.clip, noise=noise, seed=self.seed,
+                         first_id=self.first_id, x_out=self.img, **kw)
 
     def step(self):
         ops.step_set_t(self.ts_table, self.step_idx, self.t_buf)

@@ -1,6 +1,6 @@
-// Per-element arithmetic of the ancestral DDPM step with options (stedm_ddpm_step_ex, include/stedm_hip.h), shared by its two launches:
-// the quantising pre-pass (vq.hip) and the elementwise update (misc.hip). Every product and sum is rounded on its own (contraction off),
-// the expressions of ddpm_update1 in misc.hip, so that with the options off the result is stedm_ddpm_step's bit for bit.
+// Per-element arithmetic of the ancestral DDPM step (stedm_ddpm_step / stedm_ddpm_step_ex, include/stedm_hip.h), shared by its two
+// launches: the quantising pre-pass (vq.hip) and the elementwise update (sampler.hip). Every product and sum is rounded on its own
+// (contraction off), so with equal inputs torch's CPU arithmetic gives the same bits.
 #pragma once
 
 namespace stedm {

@@ -27,7 +27,7 @@ __device__ __forceinline__ float vq_add_rounded(float a, float b) {
 #pragma clang fp contract(off)
   return a + b;
 }
-// sqrt(a_prev) x0 + dir e with both products rounded, then the sum: the update kernel's form (ddim_base_rounded in misc.hip)
+// sqrt(a_prev) x0 + dir e with both products rounded, then the sum: the update kernel's form (ddim_base_rounded in sampler.hip)
 __device__ __forceinline__ float vq_ddim_base(float sqrt_ap, float x0, float dir_c, float e) {
 #pragma clang fp contract(off)
   return sqrt_ap * x0 + dir_c * e;

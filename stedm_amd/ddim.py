@@ -26,6 +26,19 @@ from . import ops
 from .schedule import DDIMTables, make_ddim_tables
 
 
+def first_stage_codebook(model, C, option):
+    """The first stage's codebook [n_e, C] fp32 on the model's device for the samplers' `option` (quantize_x0 / quantize_denoised):
+    NotImplementedError without a VQ first stage, ValueError when its width is not the latents' channel count C - both before any
+    device work."""
+    emb = getattr(getattr(getattr(model, "first_stage_model", None), "quantize", None), "embedding", None)
+    if emb is None:
+        raise NotImplementedError(f"{option} needs a VQ first stage (first_stage_model.quantize.embedding)")
+    w = emb.weight
+    if w.dim() != 2 or int(w.shape[1]) != int(C):
+        raise ValueError(f"{option}: codebook {tuple(w.shape)} has width {w.shape[-1]}, the latents have {C} channels")
+    return w.detach().to(model.device).float().contiguous()
+
+
 class _StepOpts:
     """What stedm_ddim_step_ex needs beyond stedm_ddim_step: iterations of the run, temperature, noise dropout, the in-kernel draw, the
     seed of the draw and of the keep bits, the first global sample id, the codebook of quantize_x0 (or None)."""
@@ -107,14 +120,7 @@ class DDIMSampler(object):
                                   noise_seed=kwargs.get("noise_seed"), _codebook=codebook, **masking)
 
     def _codebook(self, C):
-        """The first stage's codebook [n_e, C] fp32 on the model's device, for quantize_x0 (raises before any device work)."""
-        emb = getattr(getattr(getattr(self.model, "first_stage_model", None), "quantize", None), "embedding", None)
-        if emb is None:
-            raise NotImplementedError("quantize_x0 needs a VQ first stage (first_stage_model.quantize.embedding)")
-        w = emb.weight
-        if w.dim() != 2 or int(w.shape[1]) != int(C):
-            raise ValueError(f"quantize_x0: codebook {tuple(w.shape)} has width {w.shape[-1]}, the latents have {C} channels")
-        return w.detach().to(self.model.device).float().contiguous()
+        return first_stage_codebook(self.model, C, "quantize_x0")
 
     def _step_opts(self, temperature, noise_dropout, codebook, noise_seed, draw_ok, sample_id0):
         """The options of stedm_ddim_step_ex for this run, or None for stedm_ddim_step (the path and bits of a plain call)."""

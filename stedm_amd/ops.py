@@ -1026,20 +1026,35 @@ def ddim_quantize_x0(pred_x0: torch.Tensor, eps: torch.Tensor, coefs: torch.Tens
                                        int(codebook.shape[0]), Cc, B, H * W, x_prev.data_ptr(), _ptr(idx), _stream()), "stedm_ddim_quantize_x0")
     return x_prev
 
+
+def _mask_strides(shape, mask: torch.Tensor, x0, sqrt_ac, sqrt_1mac, T: int = 0) -> Tuple[int, int]:
+    """The mask blend's operands as ddim_mask_blend, ddpm_step and ddpm_step_ex take them: x0 and the schedule buffers sqrt_ac / sqrt_1mac
+    given (at least T entries each), mask [B|1, 1|C, h, w] against shape = (B, C, h, w) -> the mask's (batch, channel) strides in
+    elements, 0 where it broadcasts."""
+    B, Cc, H, W = shape
+    if x0 is None or sqrt_ac is None or sqrt_1mac is None:
+        raise ValueError("the mask blend needs x0, sqrt_ac and sqrt_1mac")
+    _chk(mask, name="mask"); _chk(sqrt_ac, name="sqrt_ac"); _chk(sqrt_1mac, name="sqrt_1mac")
+    if sqrt_ac.numel() < T or sqrt_1mac.numel() < T:
+        raise ValueError("sqrt_ac / sqrt_1mac must hold a value for every row of the table")
+    if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cc) or tuple(mask.shape[2:]) != (H, W):
+        raise ValueError(f"mask {tuple(mask.shape)} must be [B|1, 1|C, h, w] for {tuple(shape)}")
+    return (0 if mask.shape[0] == 1 else mask.shape[1] * H * W), (H * W if mask.shape[1] == Cc else 0)
+
+
 def ddim_mask_blend(img: torch.Tensor, x0: torch.Tensor, mask: torch.Tensor, t: torch.Tensor, sqrt_ac: torch.Tensor, sqrt_1mac: torch.Tensor,
                     noise: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None, seed: int = 0, first_id: int = 0) -> torch.Tensor:
     """ddim.py:143-146 in place: img = q_sample(x0, t) * mask + (1 - mask) * img (stedm_ddim_mask_blend). img, x0 [B, C, h, w]; mask
     [B|1, 1|C, h, w] (broadcast over batch / channel); t int64 [B]. noise [B, C, h, w], or None: row first_id + b of ops.philox_normal with
     stream 0x8000 + step_idx[0], drawn in the kernel (step_idx: device int32 [1])."""
-    _chk(img, name="img"); _chk(x0, name="x0"); _chk(mask, name="mask"); _chk(t, torch.int64, "t")
-    _chk(sqrt_ac, name="sqrt_ac"); _chk(sqrt_1mac, name="sqrt_1mac")
+    _chk(img, name="img"); _chk(t, torch.int64, "t")
     if img.dim() != 4:
         raise ValueError(f"img must be [B, C, h, w], got {tuple(img.shape)}")
     B, Cc, H, W = img.shape
+    bstride, cstride = _mask_strides(img.shape, mask, x0, sqrt_ac, sqrt_1mac)
+    _chk(x0, name="x0")
     if tuple(x0.shape) != tuple(img.shape):
         raise ValueError(f"x0 {tuple(x0.shape)} must have img's shape {tuple(img.shape)}")
-    if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cc) or tuple(mask.shape[2:]) != (H, W):
-        raise ValueError(f"mask {tuple(mask.shape)} must be [B|1, 1|C, h, w] for img {tuple(img.shape)}")
     if tuple(t.shape) != (B,):
         raise ValueError(f"t must be [B] = [{B}], got {tuple(t.shape)}")
     if noise is not None:
@@ -1050,56 +1065,51 @@ def ddim_mask_blend(img: torch.Tensor, x0: torch.Tensor, mask: torch.Tensor, t: 
         raise ValueError("the in-kernel noise draw needs step_idx (device int32)")
     if step_idx is not None:
         _chk(step_idx, torch.int32, "step_idx")
-    HW = H * W
-    cstride = HW if mask.shape[1] == Cc else 0
-    bstride = 0 if mask.shape[0] == 1 else mask.shape[1] * HW
     check(lib().stedm_ddim_mask_blend(img.data_ptr(), x0.data_ptr(), mask.data_ptr(), bstride, cstride, _ptr(noise), t.data_ptr(),
-                                      sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(), _ptr(step_idx), B, Cc, HW, int(first_id),
+                                      sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(), _ptr(step_idx), B, Cc, H * W, int(first_id),
                                       int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "stedm_ddim_mask_blend")
     return img
+
+
+def _ddpm_step_args(x, eps, table, step_idx, same_shape, mask, x0, sqrt_ac, sqrt_1mac):
+    """The checks ddpm_step and ddpm_step_ex share: x [B, C, h, w], eps and every given tensor of same_shape ((tensor, name) pairs) of x's
+    shape, table [T, 5], step_idx (when given) int32 [1], the mask operands (_mask_strides) -> T and the mask's strides."""
+    _chk(x, name="x"); _chk(eps, name="eps"); _chk(table, name="table")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, C, h, w], got {tuple(x.shape)}")
+    shp = tuple(x.shape)
+    for v, nm in (((eps, "eps"),) + same_shape):
+        if v is not None:
+            _chk(v, name=nm)
+            if tuple(v.shape) != shp:
+                raise ValueError(f"{nm} {tuple(v.shape)} must have x's shape {shp}")
+    if table.dim() != 2 or table.shape[1] != 5:
+        raise ValueError(f"table must be [T, 5], got {tuple(table.shape)}")
+    T = int(table.shape[0])
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+        if tuple(step_idx.shape) != (1,):
+            raise ValueError(f"step_idx must be [1], got {tuple(step_idx.shape)}")
+    return (T,) + ((0, 0) if mask is None else _mask_strides(shp, mask, x0, sqrt_ac, sqrt_1mac, T))
 
 
 def ddpm_step(x: torch.Tensor, eps: torch.Tensor, table: torch.Tensor, step_idx: torch.Tensor, clip_denoised: bool = True,
               noise: Optional[torch.Tensor] = None, seed: int = 0, first_id: int = 0, mask: Optional[torch.Tensor] = None,
               x0: Optional[torch.Tensor] = None, mask_noise: Optional[torch.Tensor] = None, mask_seed: int = 0,
               sqrt_ac: Optional[torch.Tensor] = None, sqrt_1mac: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """One ancestral step in place on x [B, C, h, w] (stedm_ddpm_step), t = step_idx[0] (device int32 [1]):
+    """One ancestral step in place on x [B, C, h, w] (stedm_ddpm_step: ddpm_step_ex with its options off and x_out = x), t = step_idx[0]
+    (device int32 [1]):
     x0 = sr x - srm1 eps, clamped to [-1, 1] if clip_denoised; x = c1 x0 + c2 x + sigma z with row t of table [T, 5] {sr, srm1, c1, c2,
     sigma} (schedule.ddpm_step_table). z: noise, or row first_id + b of ops.philox_normal(seed, stream 0x10000 + t), drawn in the kernel.
     mask [B|1, 1|C, h, w] with x0 (and the schedule buffers sqrt_ac / sqrt_1mac): then x = q_sample(x0, t) mask + (1 - mask) x, q_sample's
     noise mask_noise or the draw of ops.ddim_mask_blend at index t with mask_seed."""
-    _chk(x, name="x"); _chk(eps, name="eps"); _chk(table, name="table"); _chk(step_idx, torch.int32, "step_idx")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [B, C, h, w], got {tuple(x.shape)}")
+    T, bstride, cstride = _ddpm_step_args(x, eps, table, step_idx, ((noise, "noise"), (x0, "x0"), (mask_noise, "mask_noise")), mask, x0,
+                                          sqrt_ac, sqrt_1mac)
     B, Cc, H, W = x.shape
-    shp = tuple(x.shape)
-    for t, nm in ((eps, "eps"), (noise, "noise"), (x0, "x0"), (mask_noise, "mask_noise")):
-        if t is not None:
-            _chk(t, name=nm)
-            if tuple(t.shape) != shp:
-                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {shp}")
-    if table.dim() != 2 or table.shape[1] != 5:
-        raise ValueError(f"table must be [T, 5], got {tuple(table.shape)}")
-    if tuple(step_idx.shape) != (1,):
-        raise ValueError(f"step_idx must be [1], got {tuple(step_idx.shape)}")
-    HW = H * W
-    bstride = cstride = 0
-    if mask is not None:
-        _chk(mask, name="mask")
-        if x0 is None or sqrt_ac is None or sqrt_1mac is None:
-            raise ValueError("the mask blend needs x0, sqrt_ac and sqrt_1mac")
-        _chk(sqrt_ac, name="sqrt_ac"); _chk(sqrt_1mac, name="sqrt_1mac")
-        if sqrt_ac.numel() < table.shape[0] or sqrt_1mac.numel() < table.shape[0]:
-            raise ValueError("sqrt_ac / sqrt_1mac must hold a value for every row of the table")
-        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cc) or tuple(mask.shape[2:]) != (H, W):
-            raise ValueError(f"mask {tuple(mask.shape)} must be [B|1, 1|C, h, w] for x {shp}")
-        cstride = HW if mask.shape[1] == Cc else 0
-        bstride = 0 if mask.shape[0] == 1 else mask.shape[1] * HW
-    check(lib().stedm_ddpm_step(x.data_ptr(), eps.data_ptr(), table.data_ptr(), step_idx.data_ptr(), int(table.shape[0]),
-                                1 if clip_denoised else 0, _ptr(noise), _ptr(mask), bstride, cstride, _ptr(x0) if mask is not None else None,
-                                _ptr(mask_noise) if mask is not None else None, _ptr(sqrt_ac) if mask is not None else None,
-                                _ptr(sqrt_1mac) if mask is not None else None, B, Cc, HW, int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                int(mask_seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "stedm_ddpm_step")
+    mp = _ptr if mask is not None else (lambda v: None)         # the blend's operands are passed only with a mask
+    check(lib().stedm_ddpm_step(x.data_ptr(), eps.data_ptr(), table.data_ptr(), step_idx.data_ptr(), T, 1 if clip_denoised else 0,
+                                _ptr(noise), _ptr(mask), bstride, cstride, mp(x0), mp(mask_noise), mp(sqrt_ac), mp(sqrt_1mac), B, Cc, H * W,
+                                int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, int(mask_seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "stedm_ddpm_step")
     return x
 
 
@@ -1116,27 +1126,14 @@ def ddpm_step_ex(x: torch.Tensor, eps: torch.Tensor, table: torch.Tensor, step_i
     fp32 [T] table (None: 1) and the keep bits drawn from (seed, first_id + b, t) - see include/stedm_hip.h. x is read only: the sample
     goes to x_out (None: not computed; may be x), the predicted x0 after clamp and quantisation to x0_out (required with a codebook),
     the posterior mean to mean_out, the codebook indices to idx_out (int64, B h w elements). Mask arguments as ddpm_step. Returns x_out."""
-    _chk(x, name="x"); _chk(eps, name="eps"); _chk(table, name="table")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [B, C, h, w], got {tuple(x.shape)}")
+    T, bstride, cstride = _ddpm_step_args(x, eps, table, step_idx, ((noise, "noise"), (x0, "x0"), (mask_noise, "mask_noise"),
+                                                                    (x_out, "x_out"), (x0_out, "x0_out"), (mean_out, "mean_out")),
+                                          mask, x0, sqrt_ac, sqrt_1mac)
     B, Cc, H, W = x.shape
-    shp = tuple(x.shape)
-    for v, nm in ((eps, "eps"), (noise, "noise"), (x0, "x0"), (mask_noise, "mask_noise"), (x_out, "x_out"), (x0_out, "x0_out"),
-                  (mean_out, "mean_out")):
-        if v is not None:
-            _chk(v, name=nm)
-            if tuple(v.shape) != shp:
-                raise ValueError(f"{nm} {tuple(v.shape)} must have x's shape {shp}")
-    if table.dim() != 2 or table.shape[1] != 5:
-        raise ValueError(f"table must be [T, 5], got {tuple(table.shape)}")
-    T = int(table.shape[0])
+    mp = _ptr if mask is not None else (lambda v: None)         # the blend's operands are passed only with a mask
     if (step_idx is None) == (t is None):
         raise ValueError("give step_idx (device int32 [1]) or t (device int64 [B]), not both")
-    if step_idx is not None:
-        _chk(step_idx, torch.int32, "step_idx")
-        if tuple(step_idx.shape) != (1,):
-            raise ValueError(f"step_idx must be [1], got {tuple(step_idx.shape)}")
-    else:
+    if t is not None:
         _chk(t, torch.int64, "t")
         if tuple(t.shape) != (B,):
             raise ValueError(f"t must be [B] = [{B}], got {tuple(t.shape)}")
@@ -1163,27 +1160,12 @@ def ddpm_step_ex(x: torch.Tensor, eps: torch.Tensor, table: torch.Tensor, step_i
     for v, nm in ((x0_out, "x0_out"), (mean_out, "mean_out")):
         if v is not None and any(v.data_ptr() == o.data_ptr() for o in (x, eps) if o is not None):
             raise ValueError(f"{nm} may not alias x or eps")
-    HW = H * W
-    bstride = cstride = 0
-    if mask is not None:
-        _chk(mask, name="mask")
-        if x0 is None or sqrt_ac is None or sqrt_1mac is None:
-            raise ValueError("the mask blend needs x0, sqrt_ac and sqrt_1mac")
-        _chk(sqrt_ac, name="sqrt_ac"); _chk(sqrt_1mac, name="sqrt_1mac")
-        if sqrt_ac.numel() < T or sqrt_1mac.numel() < T:
-            raise ValueError("sqrt_ac / sqrt_1mac must hold a value for every row of the table")
-        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, Cc) or tuple(mask.shape[2:]) != (H, W):
-            raise ValueError(f"mask {tuple(mask.shape)} must be [B|1, 1|C, h, w] for x {shp}")
-        cstride = HW if mask.shape[1] == Cc else 0
-        bstride = 0 if mask.shape[0] == 1 else mask.shape[1] * HW
-    mk = mask is not None
     check(lib().stedm_ddpm_step_ex(x.data_ptr(), eps.data_ptr(), table.data_ptr(), _ptr(step_idx), _ptr(t), T, 1 if clip_denoised else 0,
                                    _ptr(noise), _ptr(temperature), float(noise_dropout), _ptr(codebook),
-                                   0 if codebook is None else int(codebook.shape[0]), _ptr(mask), bstride, cstride,
-                                   _ptr(x0) if mk else None, _ptr(mask_noise) if mk else None, _ptr(sqrt_ac) if mk else None,
-                                   _ptr(sqrt_1mac) if mk else None, _ptr(x_out), _ptr(x0_out), _ptr(mean_out), _ptr(idx_out), B, Cc, HW,
-                                   int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, int(mask_seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
-          "stedm_ddpm_step_ex")
+                                   0 if codebook is None else int(codebook.shape[0]), _ptr(mask), bstride, cstride, mp(x0),
+                                   mp(mask_noise), mp(sqrt_ac), mp(sqrt_1mac), _ptr(x_out), _ptr(x0_out), _ptr(mean_out), _ptr(idx_out),
+                                   B, Cc, H * W, int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, int(mask_seed) & 0xFFFFFFFFFFFFFFFF,
+                                   _stream()), "stedm_ddpm_step_ex")
     return x_out
 
 

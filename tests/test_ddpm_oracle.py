@@ -204,19 +204,20 @@ class _CpuToy:
 
 @pytest.fixture
 def cpu_kernels(monkeypatch):
-    """stedm_ddpm_step on the CPU: ddpm_update_ref at row step_idx[0] with the given noises. Returns the list of t of every update."""
+    """The plain step on the CPU - ops.ddpm_step_ex as the loop calls it, in place (x_out = x) and with no option set: ddpm_update_ref at
+    row step_idx[0] with the given noises. Returns the list of t of every update."""
     from stedm_amd import ops
     seen = []
 
-    def step(x, eps, table, step_idx, clip_denoised=True, noise=None, seed=0, first_id=0, mask=None, x0=None, mask_noise=None,
-             mask_seed=0, sqrt_ac=None, sqrt_1mac=None):
+    def step(x, eps, table, step_idx=None, clip_denoised=True, noise=None, seed=0, first_id=0, mask=None, x0=None, mask_noise=None,
+             mask_seed=0, sqrt_ac=None, sqrt_1mac=None, x_out=None):
         t = int(step_idx[0])
         seen.append(t)
-        assert noise is not None and (mask is None or mask_noise is not None)
+        assert x_out is x and noise is not None and (mask is None or mask_noise is not None)
         kw = {} if mask is None else dict(mask=mask, x0=x0, zb=mask_noise, ca=sqrt_ac[t], cn=sqrt_1mac[t])
         return ddpm_update_ref(x, eps, table[t], clip_denoised, noise, **kw)
 
-    monkeypatch.setattr(ops, "ddpm_step", step)
+    monkeypatch.setattr(ops, "ddpm_step_ex", step)
     return seen
 
 

@@ -2,7 +2,9 @@
   * stedm_ddpm_step against ddpm_update_ref bit for bit: a shape off the float4 grid (HW % 4 != 0), B = 1, [16, 3, 128, 128]; clamp on
     and off; t = 0 and t > 0; noise given, and the in-kernel draw equal to ops.philox_normal at stream 0x10000 + t; the fused mask blend
     equal to the step followed by ops.ddim_mask_blend bit for bit, with a broadcast mask (that kernel's compiled arithmetic fuses one
-    product of each sum into an FMA, so the blended elements agree with torch's unfused expression to an ulp);
+    product of each sum into an FMA, so the blended elements agree with torch's unfused expression to an ulp); an operand off the
+    16-byte grid at HW % 4 == 0 (the scalar form chosen by the alignment test) gives the aligned call's bits in stedm_ddpm_step,
+    stedm_ddpm_step_ex and stedm_ddim_mask_blend; the three wrappers refuse the same bad mask operands;
   * the sampler with F20's closed-form eps model on the device and F20's recorded noise against F20 (the reference's own chain);
   * the TINY U-Net, timesteps = 50, against ref_ddpm_sample over the oracle U-Net with the kernel's noise: parity, f16 and bf16;
     graphed equal to eager bit for bit;
@@ -92,6 +94,74 @@ def test_ddpm_step_kernel_matches_torch_bitwise(dev, shape):
         ops.ddpm_step(x.to(dev), e.to(dev), tab_d[:, :4].contiguous(), step)
     with pytest.raises(ValueError):
         ops.ddpm_step(x.to(dev), e.to(dev), tab_d, step, mask=masks[0].to(dev))
+
+
+def _off16(src, dev):
+    """src on the device as a contiguous view one float into a larger buffer: 4 bytes past a 16-byte boundary"""
+    buf = torch.empty(src.numel() + 1, device=dev)
+    v = buf[1:].view(src.shape)
+    v.copy_(src)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+def test_misaligned_operand_takes_the_scalar_form_with_the_same_bits(dev):
+    """HW % 4 == 0 with one operand off the 16-byte grid: the entries' alignment test, not the shape, selects the scalar form."""
+    from oracle import ddim as od
+    from stedm_amd import ops
+    shape = (2, 4, 8, 8)
+    tab = _table()
+    tab_d = tab.to(dev)
+    s = od.Schedule()
+    sa, s1 = s.sqrt_alphas_cumprod.to(dev), s.sqrt_one_minus_alphas_cumprod.to(dev)
+    x, e, z = prng.normal(93, "a.x", shape) * 1.5, prng.normal(93, "a.e", shape), prng.normal(93, "a.z", shape)
+    zb, x0 = prng.normal(93, "a.zb", shape), prng.normal(93, "a.x0", shape)
+    m = prng.uniform(93, "a.m", (1, 1, 8, 8), lo=0., hi=1.).to(dev)
+    on = lambda v: v.to(dev)
+    for t in (0, 537):
+        step = torch.tensor([t], dtype=torch.int32, device=dev)
+        want = ddpm_update_ref(x.clone(), e, tab[t], True, z)
+        mk = dict(mask=m, x0=on(x0), mask_noise=on(zb), sqrt_ac=sa, sqrt_1mac=s1)
+        want_m = ops.ddpm_step(on(x), on(e), tab_d, step, True, noise=on(z), **mk)
+        for which in ("x", "eps"):
+            xd = lambda: _off16(x, dev) if which == "x" else on(x)
+            ed = _off16(e, dev) if which == "eps" else on(e)
+            assert torch.equal(ops.ddpm_step(xd(), ed, tab_d, step, True, noise=on(z)).cpu(), want), (t, which)
+            assert torch.equal(ops.ddpm_step(xd(), ed, tab_d, step, True, noise=on(z), **mk), want_m), (t, which)
+        out = _off16(torch.zeros(shape), dev)
+        ops.ddpm_step_ex(on(x), on(e), tab_d, step_idx=step, noise=on(z), x_out=out, **mk)
+        assert torch.equal(out, want_m), t
+        tb = torch.full((2,), t, dtype=torch.int64, device=dev)
+        blend = lambda img: ops.ddim_mask_blend(img, on(x0), m, tb, sa, s1, noise=on(zb))
+        assert torch.equal(blend(_off16(x, dev)), blend(on(x))), t
+
+
+def test_mask_operand_checks_are_the_same_in_the_three_wrappers(dev):
+    from oracle import ddim as od
+    from stedm_amd import ops
+    shape = (2, 4, 8, 8)
+    tab = _table().to(dev)
+    s = od.Schedule()
+    sa, s1 = s.sqrt_alphas_cumprod.to(dev), s.sqrt_one_minus_alphas_cumprod.to(dev)
+    x, e, x0 = (torch.zeros(shape, device=dev) for _ in range(3))
+    step = torch.zeros(1, dtype=torch.int32, device=dev)
+    tb = torch.zeros(2, dtype=torch.int64, device=dev)
+    good = dict(mask=torch.ones((1, 1, 8, 8), device=dev), x0=x0, sqrt_ac=sa, sqrt_1mac=s1)
+    calls = {"ddpm_step": lambda **kw: ops.ddpm_step(x, e, tab, step, **kw),
+             "ddpm_step_ex": lambda **kw: ops.ddpm_step_ex(x, e, tab, step_idx=step, x_out=x, **kw),
+             "ddim_mask_blend": lambda **kw: ops.ddim_mask_blend(x, kw["x0"], kw["mask"], tb, kw["sqrt_ac"], kw["sqrt_1mac"], step_idx=step)}
+    bad = {"mask rank": dict(mask=torch.ones((1, 8, 8), device=dev)), "mask batch": dict(mask=torch.ones((3, 1, 8, 8), device=dev)),
+           "mask plane": dict(mask=torch.ones((1, 1, 8, 4), device=dev)), "no x0": dict(x0=None), "no sqrt_ac": dict(sqrt_ac=None),
+           "no sqrt_1mac": dict(sqrt_1mac=None)}
+    for call in calls.values():
+        call(**good)
+        for kw in bad.values():
+            with pytest.raises(ValueError):
+                call(**{**good, **kw})
+    for name in ("ddpm_step", "ddpm_step_ex"):                    # the blend has no step table: its t indexes the buffers directly
+        for kw in (dict(sqrt_ac=sa[:999].contiguous()), dict(sqrt_1mac=s1[:999].contiguous())):
+            with pytest.raises(ValueError):
+                calls[name](**{**good, **kw})
 
 
 # ------------------------------------------------------------------------------------------------ F20 through the HIP sampler
