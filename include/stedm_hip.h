@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 21
+#define STEDM_ABI_VERSION 22
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -375,6 +375,20 @@ int stedm_ddim_step_ex(const float* x, const float* e_c, const float* e_u, const
                        int n_iters, float cfg_scale, float rescale_phi, int draw, float temperature, float noise_dropout, long first_id,
                        unsigned long long seed, float* x_prev, float* pred_x0, float* eps_out, float* noise_out, int B, int C, int H, int W,
                        void* stream);
+/* The DDIM update with one guidance scale per sample (ABI 22). scales: DEVICE fp32 [B], read by the kernel when it runs - never a launch
+ * argument - so a captured launch replays with whatever the array then holds. Row b with scales[b] != 1 (and e_u given):
+ *   e_w = e_u + s_b (e_c - e_u);  ratio_w = std_{C,H}(e_c) / std_{C,H}(e_w) per column w (two-pass, unbiased, fp32);
+ *   e = (e_w ratio) phi + (1 - phi) e_c                                                     (ddim.py:179-184)
+ * Row b with scales[b] == 1 (or e_u NULL): e = e_c, the reference's unguided branch (ddim.py:170-171); e_u is not read for that row.
+ * x0, the direction term and the noise term are stedm_ddim_step's expressions (both products of sqrt(a_prev) x0 + dir e rounded, the noise
+ * added as fma(sigma, z, .)). z: noise [B][C][H][W] (given), or with draw != 0 element e of row first_id + b of stedm_philox_normal with
+ * (seed, stream 1 + iteration), iteration = n_iters - 1 - *step_idx, as stedm_ddim_step_ex draws it (needs step_idx and n_iters > 0);
+ * neither: no noise term. No temperature, dropout, eps_out or noise_out. pred_x0 may be NULL; x_prev may alias x.
+ * One workgroup = (sample, chunk of 16 columns): the columns of a sample are independent, so a sample spans ceil(W / 16) workgroups; any
+ * W (no W <= 256 limit), any H, C H >= 2 with e_u. A row's result depends on that row's operands and scale alone. */
+int stedm_ddim_step_rows(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
+                         const int32_t* step_idx, int n_iters, const float* scales, float rescale_phi, int draw, long first_id,
+                         unsigned long long seed, float* x_prev, float* pred_x0, int B, int C, int H, int W, void* stream);
 /* *step_idx += delta (device-side loop counter for graph replay). */
 int stedm_step_advance(int32_t* step_idx, int delta, void* stream);
 /* t_buf[0..B) = ts_table[*step_idx] : ts = torch.full((b,), step) of ddim.py:141, device-side so that one

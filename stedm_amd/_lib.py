@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 
@@ -98,6 +98,7 @@ SIGNATURES = {
     "stedm_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I, _P]),
     "stedm_ddim_step_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, _I, _F, _F, C.c_long, C.c_ulonglong, _P, _P, _P, _P, _I, _I, _I, _I,
                                _P]),
+    "stedm_ddim_step_rows": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _F, _I, C.c_long, C.c_ulonglong, _P, _P, _I, _I, _I, _I, _P]),
     "stedm_step_advance": (_I, [_P, _I, _P]),
     "stedm_step_set_t": (_I, [_P, _P, _P, _I, _P]),
     "stedm_step_set_t_f32": (_I, [_P, _P, _P, _I, _P]),

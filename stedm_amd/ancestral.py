@@ -23,7 +23,7 @@ import numbers
 import torch
 
 from . import ops
-from .ddim import DDIMSampler, first_stage_codebook
+from .ddim import DDIMSampler, first_stage_codebook, refuse_guidance_rows
 from .schedule import ddpm_step_table
 
 
@@ -84,6 +84,7 @@ class AncestralSampler(object):
         ancestral chain has no guidance; temperature and noise_dropout are progressive_denoising's). quantize_denoised needs a VQ first
         stage (p_sample_loop)."""
         scale = kwargs.get("unconditional_guidance_scale", 1.)
+        refuse_guidance_rows(scale, "the ancestral sampler")
         if kwargs.get("unconditional_conditioning") is not None and scale != 1.:
             raise NotImplementedError("ancestral sampling has no classifier-free guidance in the reference (sample() drops "
                                       "unconditional_guidance_scale / unconditional_conditioning); use a DDIM / PLMS / DPM-Solver sampler")

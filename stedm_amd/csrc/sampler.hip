@@ -276,6 +276,238 @@ extern "C" int stedm_ddim_step_ex(const float* x, const float* e_c, const float*
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// DDIM update with one guidance scale per sample (stedm_ddim_step_rows). The rescale statistic of ddim.py:182-183 is a std over (C,H) for
+// every column w on its own, so a sample's columns are independent: one workgroup = (sample b, chunk of ROWS_CHUNK columns), a sample
+// spans ceil(W / ROWS_CHUNK) workgroups and nothing is exchanged between them. thread = (col = tid % 16, part = tid / 16); part strides
+// the C H rows, so a wave reads four rows' 64-byte segments per load and a thread's sums run over r = part, part + 16, ...; the 16 parts
+// of a column meet in LDS. scales[b] is read here, from device memory: a captured launch replays with whatever the array then holds.
+// scales[b] == 1 (or e_u NULL): the reference's unguided branch (ddim.py:170-171), e = e_c; e_u is not read and no statistic is computed.
+//   R > 0   a thread's R = ceil(C H / 16) elements of every operand are held in registers (one round of independent loads);
+//   R == 0  the looped form for C H > 16 * 24: three passes over e_c / e_u.
+// x_prev may alias x: a thread reads its elements of x before it writes them, and no other thread touches them.
+// ------------------------------------------------------------------------------------------------
+constexpr int ROWS_CHUNK = 16;                   // columns per workgroup: 16 fp32 = the 64-byte segment a quarter-wave reads from one row
+constexpr int ROWS_PARTS = 256 / ROWS_CHUNK;     // row strides per workgroup
+
+struct DdimRows {
+  const float* scales;       // DEVICE [B]
+  uint32_t seed, id0;
+  int n_iters;
+  int nchunk;                // ceil(W / ROWS_CHUNK)
+};
+
+// The fusions are spelled out and contraction is off in everything below: left to the compiler, the pairing of products and sums into
+// FMAs differed between the instantiations, and a row's bits must not depend on the variant that computes it.
+__device__ __forceinline__ float ddim_rows_ew(float ec, float eu, float s) {          // e_u + s (e_c - e_u)
+#pragma clang fp contract(off)
+  return __builtin_fmaf(s, ec - eu, eu);
+}
+
+__device__ __forceinline__ float ddim_rows_guided(float ec, float eu, float s, float ratio, float phi) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(ddim_rows_ew(ec, eu, s) * ratio, phi, (1.0f - phi) * ec);
+}
+
+// x_prev / pred_x0 of one element from its (guided) eps: ddim_step_kernel's expressions
+template <bool DRAW>
+__device__ __forceinline__ void ddim_rows_finish(float xv, float e, float nzv, bool noisy, float sq1m, float sqrt_at, float sqrt_ap, float dir_c,
+                                                 float sigma, uint32_t el, uint32_t stream, uint32_t seed, uint32_t sid, long o,
+                                                 float* x_prev, float* pred_x0) {
+#pragma clang fp contract(off)
+  const float x0 = __builtin_fmaf(-sq1m, e, xv) / sqrt_at;
+  float xp = ddim_base_rounded(sqrt_ap, x0, dir_c, e);
+  if constexpr (DRAW) xp = __builtin_fmaf(sigma, philox_normal1(el, stream, seed, sid), xp);
+  else if (noisy) xp = __builtin_fmaf(sigma, nzv, xp);
+  x_prev[o] = xp;
+  if (pred_x0) pred_x0[o] = x0;
+}
+
+template <int R, bool DRAW>
+__global__ void __launch_bounds__(256) ddim_step_rows_kernel(const float* x, const float* __restrict__ e_c, const float* __restrict__ e_u,
+                                                             const float* __restrict__ noise, const float* __restrict__ coefs,
+                                                             const int32_t* __restrict__ step_idx, float phi, float* x_prev,
+                                                             float* __restrict__ pred_x0, int C, int H, int W, DdimRows rw) {
+#pragma clang fp contract(off)
+  __shared__ float red[2][256];
+  __shared__ float ratio_s[ROWS_CHUNK];
+  const int b = blockIdx.x / rw.nchunk, chunk = blockIdx.x - b * rw.nchunk;
+  const int col = threadIdx.x % ROWS_CHUNK, part = threadIdx.x / ROWS_CHUNK;
+  const int w = chunk * ROWS_CHUNK + col;
+  const bool in_w = w < W;
+  const int idx = step_idx ? *step_idx : 0;
+  const float a_t = coefs[idx * 4 + 0], a_prev = coefs[idx * 4 + 1], sigma = coefs[idx * 4 + 2], sq1m = coefs[idx * 4 + 3];
+  const int CH = C * H;
+  const long base = (long)b * CH * W;
+  const float s = rw.scales[b];
+  const bool guided = e_u != nullptr && s != 1.0f;      // uniform over the workgroup
+  const bool noisy = !DRAW && noise != nullptr;
+  const uint32_t stream = 1u + (uint32_t)(rw.n_iters - 1 - idx), sid = rw.id0 + (uint32_t)b;
+  const float sqrt_at = sqrtf(a_t);
+  const float dir_c = sqrtf(1.0f - a_prev - sigma * sigma);
+  const float sqrt_ap = sqrtf(a_prev);
+
+  if constexpr (R > 0) {
+    float ec[R], eu[R], xv[R], nz[R];
+    bool ok[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) ok[j] = in_w && part + j * ROWS_PARTS < CH;
+#pragma unroll
+    for (int j = 0; j < R; ++j) ec[j] = ok[j] ? e_c[base + (long)(part + j * ROWS_PARTS) * W + w] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < R; ++j) xv[j] = ok[j] ? x[base + (long)(part + j * ROWS_PARTS) * W + w] : 0.0f;
+    if (guided) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) eu[j] = ok[j] ? e_u[base + (long)(part + j * ROWS_PARTS) * W + w] : 0.0f;
+    }
+    if (noisy) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) nz[j] = ok[j] ? noise[base + (long)(part + j * ROWS_PARTS) * W + w] : 0.0f;
+    }
+    float ratio = 1.0f;
+    if (guided) {
+      // means over (c,h) of column w, then centred sums of squares -> unbiased std (torch.std default, ddim.py:183)
+      float sc = 0.f, sw = 0.f;
+#pragma unroll
+      for (int j = 0; j < R; ++j)
+        if (ok[j]) {
+          sc += ec[j];
+          sw += ddim_rows_ew(ec[j], eu[j], s);
+        }
+      red[0][threadIdx.x] = sc;
+      red[1][threadIdx.x] = sw;
+      __syncthreads();
+      float mc = 0.f, mw = 0.f;
+#pragma unroll
+      for (int p = 0; p < ROWS_PARTS; ++p) {
+        mc += red[0][p * ROWS_CHUNK + col];
+        mw += red[1][p * ROWS_CHUNK + col];
+      }
+      mc /= (float)CH;
+      mw /= (float)CH;
+      __syncthreads();
+      float qc = 0.f, qw = 0.f;
+#pragma unroll
+      for (int j = 0; j < R; ++j)
+        if (ok[j]) {
+          const float dc = ec[j] - mc, dw = ddim_rows_ew(ec[j], eu[j], s) - mw;
+          qc = __builtin_fmaf(dc, dc, qc);
+          qw = __builtin_fmaf(dw, dw, qw);
+        }
+      red[0][threadIdx.x] = qc;
+      red[1][threadIdx.x] = qw;
+      __syncthreads();
+      if (threadIdx.x < ROWS_CHUNK) {
+        float vc = 0.f, vw = 0.f;
+#pragma unroll
+        for (int p = 0; p < ROWS_PARTS; ++p) {
+          vc += red[0][p * ROWS_CHUNK + threadIdx.x];
+          vw += red[1][p * ROWS_CHUNK + threadIdx.x];
+        }
+        ratio_s[threadIdx.x] = sqrtf(vc / (float)(CH - 1)) / sqrtf(vw / (float)(CH - 1));
+      }
+      __syncthreads();
+      ratio = ratio_s[col];
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+      if (ok[j]) {
+        const int r = part + j * ROWS_PARTS;
+        const float e = guided ? ddim_rows_guided(ec[j], eu[j], s, ratio, phi) : ec[j];
+        ddim_rows_finish<DRAW>(xv[j], e, noisy ? nz[j] : 0.0f, noisy, sq1m, sqrt_at, sqrt_ap, dir_c, sigma, (uint32_t)(r * W + w), stream,
+                               rw.seed, sid, base + (long)r * W + w, x_prev, pred_x0);
+      }
+  } else {
+    float ratio = 1.0f;
+    if (guided) {
+      float sc = 0.f, sw = 0.f;
+      if (in_w)
+        for (int r = part; r < CH; r += ROWS_PARTS) {
+          const float ec = e_c[base + (long)r * W + w], eu = e_u[base + (long)r * W + w];
+          sc += ec;
+          sw += ddim_rows_ew(ec, eu, s);
+        }
+      red[0][threadIdx.x] = sc;
+      red[1][threadIdx.x] = sw;
+      __syncthreads();
+      float mc = 0.f, mw = 0.f;
+      for (int p = 0; p < ROWS_PARTS; ++p) {
+        mc += red[0][p * ROWS_CHUNK + col];
+        mw += red[1][p * ROWS_CHUNK + col];
+      }
+      mc /= (float)CH;
+      mw /= (float)CH;
+      __syncthreads();
+      float qc = 0.f, qw = 0.f;
+      if (in_w)
+        for (int r = part; r < CH; r += ROWS_PARTS) {
+          const float ec = e_c[base + (long)r * W + w], eu = e_u[base + (long)r * W + w];
+          const float dc = ec - mc, dw = ddim_rows_ew(ec, eu, s) - mw;
+          qc = __builtin_fmaf(dc, dc, qc);
+          qw = __builtin_fmaf(dw, dw, qw);
+        }
+      red[0][threadIdx.x] = qc;
+      red[1][threadIdx.x] = qw;
+      __syncthreads();
+      if (threadIdx.x < ROWS_CHUNK) {
+        float vc = 0.f, vw = 0.f;
+        for (int p = 0; p < ROWS_PARTS; ++p) {
+          vc += red[0][p * ROWS_CHUNK + threadIdx.x];
+          vw += red[1][p * ROWS_CHUNK + threadIdx.x];
+        }
+        ratio_s[threadIdx.x] = sqrtf(vc / (float)(CH - 1)) / sqrtf(vw / (float)(CH - 1));
+      }
+      __syncthreads();
+      ratio = ratio_s[col];
+    }
+    if (in_w)
+      for (int r = part; r < CH; r += ROWS_PARTS) {
+        const long o = base + (long)r * W + w;
+        const float ec = e_c[o];
+        const float e = guided ? ddim_rows_guided(ec, e_u[o], s, ratio, phi) : ec;
+        ddim_rows_finish<DRAW>(x[o], e, noisy ? noise[o] : 0.0f, noisy, sq1m, sqrt_at, sqrt_ap, dir_c, sigma, (uint32_t)(r * W + w), stream,
+                               rw.seed, sid, o, x_prev, pred_x0);
+      }
+  }
+}
+
+template <bool DRAW>
+static void launch_ddim_step_rows(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
+                                  const int32_t* step_idx, float phi, float* x_prev, float* pred_x0, int B, int C, int H, int W,
+                                  const DdimRows& rw, hipStream_t st) {
+  const int per = (C * H + ROWS_PARTS - 1) / ROWS_PARTS;      // a thread's elements
+  const unsigned grid = (unsigned)((long)B * rw.nchunk);
+#define DDIM_ROWS(RR) ddim_step_rows_kernel<RR, DRAW><<<grid, 256, 0, st>>>(x, e_c, e_u, noise, coefs, step_idx, phi, x_prev, pred_x0, C, H, W, rw)
+  if (per <= 2) DDIM_ROWS(2);            // 8 x 8 x 4 and smaller
+  else if (per <= 4) DDIM_ROWS(4);       // 16 x 16 x 4
+  else if (per <= 8) DDIM_ROWS(8);       // 32 x 32 x 4 (the bench's latents)
+  else if (per <= 16) DDIM_ROWS(16);     // 64 x 64 x 4
+  else if (per <= 24) DDIM_ROWS(24);     // 128 x 128 x 3 (the reference's native latents)
+  else DDIM_ROWS(0);
+#undef DDIM_ROWS
+}
+
+extern "C" int stedm_ddim_step_rows(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
+                                    const int32_t* step_idx, int n_iters, const float* scales, float rescale_phi, int draw, long first_id,
+                                    unsigned long long seed, float* x_prev, float* pred_x0, int B, int C, int H, int W, void* stream) {
+  STEDM_CHECK_ARG(x && e_c && coefs && scales && x_prev, "ddim_step_rows: null pointer");
+  STEDM_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "ddim_step_rows: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+  STEDM_CHECK_ARG((long)C * H * W <= 0x7FFFFFFFL, "ddim_step_rows: a sample of %d x %d x %d elements exceeds 2^31 - 1", C, H, W);
+  STEDM_CHECK_ARG(!e_u || C * H > 1, "ddim_step_rows: std over (C,H) needs C*H > 1");
+  STEDM_CHECK_ARG(!(draw && noise), "ddim_step_rows: a given noise tensor and the in-kernel draw exclude each other");
+  STEDM_CHECK_ARG(!(draw && !step_idx), "ddim_step_rows: the in-kernel draw needs the device step index");
+  STEDM_CHECK_ARG(!(draw && n_iters <= 0), "ddim_step_rows: the in-kernel draw needs n_iters > 0 (got %d)", n_iters);
+  STEDM_CHECK_ARG(first_id >= 0 && first_id + B <= (1L << 32), "ddim_step_rows: sample ids %ld + %d outside [0, 2^32]", first_id, B);
+  const int nchunk = (W + ROWS_CHUNK - 1) / ROWS_CHUNK;
+  STEDM_CHECK_ARG((long)B * nchunk <= 0x7FFFFFFFL, "ddim_step_rows: %d samples of %d column chunks exceed one launch", B, nchunk);
+  const DdimRows rw{scales, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)first_id, n_iters, nchunk};
+  hipStream_t st = as_stream(stream);
+  if (draw) launch_ddim_step_rows<true>(x, e_c, e_u, noise, coefs, step_idx, rescale_phi, x_prev, pred_x0, B, C, H, W, rw, st);
+  else launch_ddim_step_rows<false>(x, e_c, e_u, noise, coefs, step_idx, rescale_phi, x_prev, pred_x0, B, C, H, W, rw, st);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
 __global__ void step_advance_kernel(int32_t* p, int d) { *p += d; }
 extern "C" int stedm_step_advance(int32_t* step_idx, int delta, void* stream) {
   STEDM_CHECK_ARG(step_idx, "step_advance: null pointer");

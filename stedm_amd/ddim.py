@@ -13,7 +13,9 @@ operation of the loop body runs in HIP kernels:
   * with `use_graph=True` the whole step (timestep fill, U-Net, update, counter decrement) is captured
     once in a hipGraph and replayed per step, per-step scalars coming from a device table;
   * temperature / noise_dropout (ddim.py:206-208) and the step noise drawn from (noise_seed, sample id) -> stedm_ddim_step_ex, the same
-    kernel with compile-time options; quantize_x0 (ddim.py:201-203) -> one more kernel after it (stedm_ddim_quantize_x0).
+    kernel with compile-time options; quantize_x0 (ddim.py:201-203) -> one more kernel after it (stedm_ddim_quantize_x0);
+  * one guidance scale per sample (a sequence or 1-D tensor as unconditional_guidance_scale) -> stedm_ddim_step_rows, which reads the
+    scales from a device array, so a captured step serves any scales (StepGraph.set_scales).
 """
 from __future__ import annotations
 
@@ -37,6 +39,40 @@ def first_stage_codebook(model, C, option):
     if w.dim() != 2 or int(w.shape[1]) != int(C):
         raise ValueError(f"{option}: codebook {tuple(w.shape)} has width {w.shape[-1]}, the latents have {C} channels")
     return w.detach().to(model.device).float().contiguous()
+
+
+def guidance_rows(scale, batch_size):
+    """unconditional_guidance_scale as the samplers take it -> None for one scale (a Python / numpy number or a 0-d tensor: today's path),
+    else the per-sample scales as a list of `batch_size` finite floats (a sequence or a 1-D tensor). ValueError on a wrong length, a
+    non-finite value or more than one dimension. Host work only."""
+    if isinstance(scale, torch.Tensor):
+        if scale.dim() == 0:
+            return None
+        vals = scale.detach().cpu().double().numpy()
+    elif isinstance(scale, np.ndarray):
+        if scale.ndim == 0:
+            return None
+        vals = scale.astype(np.float64)
+    elif isinstance(scale, (list, tuple)):
+        try:
+            vals = np.asarray(scale, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"unconditional_guidance_scale {scale!r}: per-sample scales must be a flat sequence of numbers") from e
+    else:
+        return None
+    if vals.ndim != 1 or vals.shape[0] != int(batch_size):
+        raise ValueError(f"unconditional_guidance_scale of shape {tuple(vals.shape)}: per-sample scales must be 1-D of length batch_size = "
+                         f"{int(batch_size)}")
+    if not np.isfinite(vals).all():
+        raise ValueError(f"unconditional_guidance_scale holds a non-finite value: {vals.tolist()}")
+    return [float(v) for v in vals]
+
+
+def refuse_guidance_rows(scale, who):
+    """The samplers without per-sample guidance scales: NotImplementedError for anything guidance_rows would read as rows."""
+    if (isinstance(scale, (torch.Tensor, np.ndarray)) and scale.ndim > 0) or isinstance(scale, (list, tuple)):
+        raise NotImplementedError(f"{who} takes one unconditional_guidance_scale for the batch; per-sample scales are DDIMSampler's "
+                                  "(stedm_ddim_step_rows)")
 
 
 class _StepOpts:
@@ -100,11 +136,20 @@ class DDIMSampler(object):
         With eta == 0 the noise term is zero, so temperature and noise_dropout change nothing. `noise_seed` (repo-specific, the ancestral
         sampler's name): the step noise of eta > 0 is drawn in the kernel as row sample_id0 + b of ops.philox_normal(noise_seed, stream
         1 + iteration) - what predict_latents_sharded fed as `noises` - and the loop can be graphed; without it the step noise comes from
-        torch.randn per step (or `noises`) and the dropout bits from a seed drawn once per call from torch's CPU generator."""
+        torch.randn per step (or `noises`) and the dropout bits from a seed drawn once per call from torch's CPU generator.
+
+        unconditional_guidance_scale may be a sequence or a 1-D tensor of batch_size finite scales, one per sample (repo-specific; a
+        number or 0-d tensor is the reference's one scale and runs exactly as before). Sample b then equals a run of the whole batch at
+        scale[b] (stedm_ddim_step_rows). Without unconditional_conditioning, or with every scale 1, the run is unguided: one forward per
+        step, as in the reference. Otherwise every step runs the CFG pass on all rows: a row at scale 1 inside a mixed batch is legal and
+        takes the unguided update, but still pays its share of the unconditional decoder rows (there is no ragged forward). eta > 0,
+        noises / noise_seed and mask / x0 compose; quantize_x0 and, with eta != 0, temperature != 1 or noise_dropout != 0 are refused
+        (NotImplementedError)."""
         if score_corrector is not None:
             raise NotImplementedError("score_corrector: unused by the reference drivers (ldm_diffusion.py:82,90), not implemented")
         if not 0.0 <= float(noise_dropout) < 1.0:
             raise ValueError(f"noise_dropout {noise_dropout} outside [0, 1)")
+        self._check_rows(guidance_rows(unconditional_guidance_scale, batch_size), quantize_x0, eta, temperature, noise_dropout)
         codebook = self._codebook(shape[0]) if quantize_x0 else None
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
@@ -121,6 +166,16 @@ class DDIMSampler(object):
 
     def _codebook(self, C):
         return first_stage_codebook(self.model, C, "quantize_x0")
+
+    @staticmethod
+    def _check_rows(rows, quantize_x0, eta, temperature, noise_dropout):
+        """What per-sample guidance scales do not combine with (stedm_ddim_step_rows has none of stedm_ddim_step_ex's options)."""
+        if rows is None:
+            return
+        if quantize_x0:
+            raise NotImplementedError("per-sample guidance scales: quantize_x0 is not implemented (stedm_ddim_step_rows has no eps output)")
+        if float(eta) != 0.0 and (float(temperature) != 1.0 or float(noise_dropout) != 0.0):
+            raise NotImplementedError("per-sample guidance scales with eta != 0: temperature and noise_dropout are not implemented")
 
     def _step_opts(self, temperature, noise_dropout, codebook, noise_seed, draw_ok, sample_id0):
         """The options of stedm_ddim_step_ex for this run, or None for stedm_ddim_step (the path and bits of a plain call)."""
@@ -174,13 +229,19 @@ class DDIMSampler(object):
         quantize_denoised / temperature / noise_dropout / noise_seed: see `sample`."""
         device = self.model.device
         b = shape[0]
+        rows = guidance_rows(unconditional_guidance_scale, b)
+        self._check_rows(rows, quantize_denoised, self._eta, temperature, noise_dropout)
+        if rows is not None and (unconditional_conditioning is None or all(v == 1.0 for v in rows)):
+            rows, unconditional_guidance_scale = None, 1.0          # unguided: one forward per step (ddim.py:170-171)
+        # the device array stedm_ddim_step_rows reads, made once
+        scales = None if rows is None else torch.tensor(rows, dtype=torch.float32, device=device)
         if quantize_denoised and _codebook is None:
             _codebook = self._codebook(shape[1])
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().clone()
         timesteps = self.ddim_timesteps
         total_steps = timesteps.shape[0]
         intermediates = {'x_inter': [img.clone()], 'pred_x0': [img.clone()]}
-        cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
+        cfg = rows is not None or not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         need_inter = lambda index: index % log_every_t == 0 or index == total_steps - 1
 
         blend = None if mask is None else (mask, x0, mask_seed, int(sample_id0))
@@ -189,7 +250,7 @@ class DDIMSampler(object):
 
         if self.use_graph and callback is None and img_callback is None and hasattr(self.model, "apply_model_cfg") \
                 and mask_noises is None and (self._eta == 0.0 or (opts is not None and opts.draw)):
-            out = self._sample_graph(img, cond, unconditional_conditioning, unconditional_guidance_scale, cfg,
+            out = self._sample_graph(img, cond, unconditional_conditioning, rows if rows is not None else unconditional_guidance_scale, cfg,
                                      total_steps, log_every_t, intermediates, blend, opts)
             ops.f16_guard_check("the DDIM sampling loop")       # fp16 modes: raise rather than return samples computed through an inf
             return out
@@ -208,7 +269,7 @@ class DDIMSampler(object):
                 nz = torch.randn(shape, device=device)     # ddim.py:206 (when sigma == 0 the draw cannot change x)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning, _noise=nz, _out=(img, pred_x0),
-                                              _uniform_t=True, _opts=opts)
+                                              _uniform_t=True, _opts=opts, _scales=scales)
             if callback:
                 callback(i)
             if img_callback:
@@ -223,11 +284,21 @@ class DDIMSampler(object):
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, rescale_phi=0.7,
-                      _noise: Optional[torch.Tensor] = None, _out=None, _uniform_t: bool = False, _opts=None):
+                      _noise: Optional[torch.Tensor] = None, _out=None, _uniform_t: bool = False, _opts=None, _scales=None):
         """ddim.py:164-210. Returns (x_prev, pred_x0). The step noise is `_noise` (None: no noise term); temperature, noise_dropout
-        (keep bits from a seed drawn per call) and quantize_denoised as in `sample`. _opts: the loop's options (they take precedence)."""
+        (keep bits from a seed drawn per call) and quantize_denoised as in `sample`. _opts: the loop's options (they take precedence).
+        unconditional_guidance_scale: a number, or one scale per sample (a sequence or 1-D tensor of x.shape[0] values) - see `sample`.
+        _scales: the loop's device tensor of per-sample scales, already checked (it takes precedence)."""
         if use_original_steps or score_corrector is not None or repeat_noise:
             raise NotImplementedError("use_original_steps / score_corrector / repeat_noise not implemented")
+        scales = _scales
+        rows = None if _scales is not None else guidance_rows(unconditional_guidance_scale, x.shape[0])
+        if rows is not None:
+            self._check_rows(rows, quantize_denoised, self._eta if _noise is not None else 0.0, temperature, noise_dropout)
+            if unconditional_conditioning is None or all(v == 1.0 for v in rows):
+                unconditional_guidance_scale = 1.0
+            else:
+                scales = torch.tensor(rows, dtype=torch.float32, device=x.device)
         if _opts is None and (quantize_denoised or temperature != 1. or noise_dropout != 0.):
             if not 0.0 <= float(noise_dropout) < 1.0:
                 raise ValueError(f"noise_dropout {noise_dropout} outside [0, 1)")
@@ -236,7 +307,7 @@ class DDIMSampler(object):
         e_u = None
         ours = hasattr(self.model, "apply_model_cfg")
         kw = {"uniform_t": True} if (ours and _uniform_t) else {}
-        if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
+        if scales is None and (unconditional_conditioning is None or unconditional_guidance_scale == 1.):
             e_c = self.model.apply_model(x, t, c, **kw)
         elif ours:
             e_c, e_u = self.model.apply_model_cfg(x, t, c, unconditional_conditioning, **kw)
@@ -246,11 +317,18 @@ class DDIMSampler(object):
         x_prev, pred_x0 = _out if _out is not None else (torch.empty_like(x), torch.empty_like(x))
         step = self._idx_all[index:index + 1]   # device-resident loop index (no H2D copy per step)
         self._update(x, e_c.contiguous(), None if e_u is None else e_u.contiguous(), x_prev, pred_x0, step,
-                     float(unconditional_guidance_scale), float(rescale_phi), _noise, _opts)
+                     scales if scales is not None else float(unconditional_guidance_scale), float(rescale_phi), _noise, _opts)
         return x_prev, pred_x0
 
     def _update(self, x, e_c, e_u, x_prev, pred_x0, step, scale, phi, noise=None, opts=None, noise_buf=None):
-        """ddim.py:179-210 after the model call: stedm_ddim_step, or with options stedm_ddim_step_ex (+ stedm_ddim_quantize_x0)."""
+        """ddim.py:179-210 after the model call: stedm_ddim_step, or with options stedm_ddim_step_ex (+ stedm_ddim_quantize_x0); with
+        `scale` a device tensor [B] (per-sample scales) stedm_ddim_step_rows."""
+        if isinstance(scale, torch.Tensor):
+            draw = opts is not None and opts.draw and self._eta != 0.0
+            ops.ddim_step_rows(x, e_c, e_u, self._coefs, x_prev, scale, pred_x0=pred_x0, noise=noise if self._eta != 0.0 else None,
+                               draw=draw, step_idx=step, n_iters=opts.n_iters if draw else 0, rescale_phi=phi,
+                               seed=opts.seed if draw else 0, first_id=opts.first_id if draw else 0)
+            return
         if opts is None:
             ops.ddim_step(x, e_c, e_u, self._coefs, x_prev, pred_x0=pred_x0, noise=noise, step_idx=step, cfg_scale=scale, rescale_phi=phi)
             return
@@ -295,17 +373,24 @@ class StepGraph:
     """One denoising step = {t fill from the device table, [masked sampling: blend of q_sample(x0, t) into `img`, noise drawn in the
     kernel from the device index], U-Net (shared-encoder CFG pass), fused DDIM/CFG update in place on `img` [with opts: stedm_ddim_step_ex,
     its noise drawn in the kernel from the device index, then stedm_ddim_quantize_x0 for quantize_x0], device index decrement},
-    capturable once in a hipGraph and replayed for every step. blend: None or (mask, x0, seed, first sample id)."""
+    capturable once in a hipGraph and replayed for every step. blend: None or (mask, x0, seed, first sample id). scale: one number, or
+    per-sample scales (a float32 tensor [B], a sequence): the update is then stedm_ddim_step_rows reading `scales`, a device tensor this
+    object owns - set_scales() overwrites it in place, and the captured graph replays with the new values, no recapture."""
 
     def __init__(self, sampler: DDIMSampler, img: torch.Tensor, cond, uncond, scale: float, rescale_phi: float = 0.7, blend=None, opts=None):
         self.s = sampler
         self.img = img
         self.blend = blend
         self.opts = opts            # _StepOpts of stedm_ddim_step_ex (in-kernel noise, temperature, dropout, quantize_x0) or None
-        self.cond, self.uncond, self.scale, self.phi = cond, uncond, float(scale), float(rescale_phi)
         dev = img.device
         b = img.shape[0]
-        self.cfg = uncond is not None and scale != 1.0
+        rows = guidance_rows(scale, b)
+        self.scales = None if rows is None else torch.tensor(rows, dtype=torch.float32, device=dev)
+        if rows is not None and opts is not None and (opts.codebook is not None or opts.temperature != 1.0 or opts.noise_dropout != 0.0):
+            raise NotImplementedError("per-sample guidance scales: quantize_x0, temperature and noise_dropout are not implemented")
+        self.cond, self.uncond, self.phi = cond, uncond, float(rescale_phi)
+        self.scale = None if rows is not None else float(scale)
+        self.cfg = uncond is not None and (rows is not None or scale != 1.0)
         self.step = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.t_buf = torch.empty((b,), dtype=torch.int64, device=dev)
         self.pred_x0 = torch.empty_like(img)
@@ -317,6 +402,17 @@ class StepGraph:
     def reset(self, index: int):
         self.step.fill_(int(index))
 
+    def set_scales(self, values):
+        """New per-sample guidance scales for a StepGraph built with per-sample scales: an in-place copy into the device tensor the
+        captured update reads (no recapture). Every row keeps running through the CFG pass, a row set to 1 included."""
+        if self.scales is None:
+            raise ValueError("set_scales: this StepGraph was built with one scale for the batch (it is a launch argument of the captured "
+                             "stedm_ddim_step); build it with per-sample scales")
+        rows = guidance_rows(values, self.img.shape[0])
+        if rows is None:
+            raise ValueError(f"set_scales takes one scale per sample (a sequence or 1-D tensor), got {values!r}")
+        self.scales.copy_(torch.tensor(rows, dtype=torch.float32), non_blocking=False)
+
     def step_eager(self):
         s, m = self.s, self.s.model
         ops.step_set_t(s._ts_table, self.step, self.t_buf)
@@ -327,7 +423,8 @@ class StepGraph:
             e_c, e_u = m.apply_model_cfg(self.img, self.t_buf, self.cond, self.uncond, out=self.eps, uniform_t=True)
         else:
             e_c, e_u = m.apply_model(self.img, self.t_buf, self.cond, out=self.eps, uniform_t=True), None
-        s._update(self.img, e_c, e_u, self.img, self.pred_x0, self.step, self.scale, self.phi, opts=self.opts, noise_buf=self.noise_buf)
+        s._update(self.img, e_c, e_u, self.img, self.pred_x0, self.step, self.scales if self.scales is not None else self.scale, self.phi,
+                  opts=self.opts, noise_buf=self.noise_buf)
         ops.step_advance(self.step, -1)
 
     def stream_ctx(self):

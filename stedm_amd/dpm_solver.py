@@ -25,6 +25,7 @@ from typing import List
 import torch
 
 from . import ops
+from .ddim import refuse_guidance_rows
 
 MODEL_TYPES = {"eps": "noise"}      # sampler.py:7-10 ('v' is not a parameterization of the STEDM configs)
 
@@ -400,7 +401,9 @@ class DPMSolverSampler(object):
         reference sampler's DPM-Solver++(2M)) the run takes the 2M path above (dpm_tables, stedm_dpm_step); any other setting runs the
         general plan (dpm_plan, stedm_dpm_update, stedm_dpm_threshold), one model evaluation (NFE) per row, callbacks per NFE.
         method 'adaptive' raises NotImplementedError; an order outside 1..3, an unknown method / skip_type / solver_type, or multistep
-        S < order raise ValueError, before any device work."""
+        S < order raise ValueError, before any device work. One unconditional_guidance_scale for the batch: per-sample scales (a sequence
+        or 1-D tensor) raise NotImplementedError - DDIMSampler has them."""
+        refuse_guidance_rows(unconditional_guidance_scale, "DPMSolverSampler")
         general = not (order == 2 and method == "multistep" and skip_type == "time_uniform" and predict_x0 is True
                        and solver_type == "dpm_solver" and lower_order_final is True and not denoise_to_zero and not thresholding
                        and t_start is None and t_end is None)

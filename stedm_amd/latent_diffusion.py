@@ -25,7 +25,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import StedmHipError
 from .ancestral import AncestralSampler
-from .ddim import DDIMSampler
+from .ddim import DDIMSampler, guidance_rows
 from .dpm_solver import DPMSolverSampler
 from .plms import PLMSSampler
 from .schedule import POSTERIOR_BUFFERS, NoiseSchedule, PosteriorSchedule, lvlb_weights
@@ -941,9 +941,20 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
 
     dpm_solver (sampler="dpm_solver" only, ValueError otherwise): a dict of DPMSolverSampler.sample's solver options (DPM_OPTIONS:
     order, method, skip_type, predict_x0, solver_type, lower_order_final, denoise_to_zero, thresholding, max_val, t_start, t_end);
-    None or {} keeps DPM-Solver++(2M)."""
+    None or {} keeps DPM-Solver++(2M).
+
+    cfg_scale may be a sequence or 1-D tensor with one guidance scale per sample of the batch (sampler="ddim" only; NotImplementedError
+    otherwise): sample b is then guided at cfg_scale[b] in one batched run (DDIMSampler.sample, stedm_ddim_step_rows). A wrong length
+    raises ValueError before any device work; every scale 1 is the unguided run."""
     if sampler not in ALL_SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}; choose from {ALL_SAMPLERS}")
+    rows = None
+    if isinstance(cfg_scale, (list, tuple)) or (isinstance(cfg_scale, (torch.Tensor, np.ndarray)) and cfg_scale.ndim > 0):
+        rows = guidance_rows(cfg_scale, len(ldm_batch["image"]))
+    if rows is not None:
+        if sampler != "ddim":
+            raise NotImplementedError(f"sampler={sampler!r} takes one cfg_scale for the batch; per-sample scales are sampler='ddim' (DDIMSampler)")
+        cfg_scale = 1.0 if all(v == 1.0 for v in rows) else rows
     if dpm_solver is not None:
         if sampler != "dpm_solver":
             raise ValueError(f"dpm_solver options are for sampler='dpm_solver', got sampler={sampler!r}")
@@ -976,7 +987,7 @@ def predict_latents(model: S_ZSS_DM, ldm_batch: dict, ddim_steps: int, eta: floa
         kw.update(dpm_solver or {})
     elif eta != 0.0 and noise_seed is not None:
         kw.update(noise_seed=int(noise_seed), sample_id0=int(sample_id0))
-    if cfg_scale == 1 or style_sampling == "none":
+    if (not isinstance(cfg_scale, list) and cfg_scale == 1) or style_sampling == "none":
         out, _ = model.sample_log(c_0, batch_size=len(z), ddim=True, ddim_steps=ddim_steps, eta=eta, log_every_t=1000, **kw)
     else:
         if dedup_uncond:
@@ -1031,7 +1042,9 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
 
     sampler="dpm_solver" (through **kw): DPM-Solver draws nothing after x_T, so the per-sample x_T alone makes the shards invariant.
     sampler="plms" likewise, its masked blend keyed by the global sample id as DDIM's. sampler="ddpm": every step's noise is drawn in
-    the kernel from (seed, global sample id), so the ancestral chain is shard-invariant too."""
+    the kernel from (seed, global sample id), so the ancestral chain is shard-invariant too.
+
+    cfg_scale: one number, or per-sample scales (predict_latents) given for the global batch (rows lo:hi are taken) or for the shard."""
     import torch.distributed as dist
     from . import parallel as par
     if rank is None or world is None:
@@ -1042,6 +1055,11 @@ def predict_latents_sharded(model: S_ZSS_DM, shard_batch: dict, global_batch: in
     n = len(shard_batch["image"])
     if n != hi - lo:
         raise ValueError(f"rank {rank} of {world}: the shard holds {n} samples, shard_range({global_batch}) gives {hi - lo}")
+    if (isinstance(cfg_scale, (torch.Tensor, np.ndarray)) and cfg_scale.ndim == 1) or isinstance(cfg_scale, (list, tuple)):
+        if len(cfg_scale) == int(global_batch) and len(cfg_scale) != n:
+            cfg_scale = cfg_scale[lo:hi]
+        elif len(cfg_scale) != n:
+            raise ValueError(f"cfg_scale holds {len(cfg_scale)} scales: expected {int(global_batch)} (the global batch) or {n} (this shard)")
     shape = (model.channels, model.image_size, model.image_size)
     dev = model.device
     on_gpu = torch.device(dev).type == "cuda"

@@ -1,7 +1,8 @@
 """In-tree counterpart of the reference's Lightning wrapper `modules/ldm_diffusion.py::LDM_Diffusion` (:14-234) for the HIP path.
 
 Same constructor argument (the Hydra config), same members the drivers call — `prepare_batch` (:51-60), `training_step(batch,
-batch_idx)` (:63-73), `predict_step` (:76-107), `on_train_batch_start/end` (:110-115), `configure_optimizers` (:224-234) — with one
+batch_idx)` (:63-73), `predict_step` (:76-107), `on_train_batch_start/end` (:110-115), `on_train_epoch_end` (:118-221; its eight
+monitoring images come from two batched DDIM runs, `sample_test_images`), `configure_optimizers` (:224-234) — with one
 declared difference: `automatic_optimization = False`. The training step runs the fused HIP path (`S_ZSS_DM.training_step_hip`:
 forward + L1 + hand-scheduled backward, gradient accumulation, bucketed all-reduce over the ranks, fused AdamW + EMA), so Lightning's
 own backward / DDP reducer / optimizer loop have nothing to do; `train_diff.py` can construct this class in place of the reference's
@@ -120,6 +121,108 @@ class LDM_Diffusion(_Base):
             self._loss_sum, self._loss_n = None, 0
         return v
 
+    # ------------------------------------------------------------------------------------------ epoch end
+    @torch.no_grad()
+    def sample_test_images(self, test_folder: Optional[str] = None, ddim_steps: int = 128, seed: Optional[int] = None):
+        """The monitoring images of ldm_diffusion.py:127-221 -> {"Sample Images": [4 uint8 [H,W,3] arrays], "Sample Images CFG": [4 arrays]
+        (absent when no guided run is made)}.
+
+        Files read as the reference reads them, from `test_folder` (default cfg.location.data_dir + "/" + cfg.data.test_folder):
+        test_c.png (grey, > 0 -> class 1, one-hot over 2 classes) and, under the style sampling's name, the four test styles:
+        "nearby" {i}_img.png; "mp" {i}_img_{k}.png for k < num_patches; "dummy" no files, the constant stack zeros / 127.5 - 1 (at the
+        condition image's size; the reference hard-codes 512). Pixels / 127.5 - 1, first three channels.
+
+        The reference renders each image in a run of its own: eight batch-1 DDIM-128 runs. Here they are two graphed runs at eta 0
+        through predict_latents (conditionings from get_input(..., predict_only=True): the reference's VQ encodes of a zero image are
+        unused; the unconditional style is encoded once):
+          * B = 4 unguided, test styles 0 - 3;
+          * B = 4 guided, rows [style 0, style 0, style 1, style 1] at guidance scales [3, 5, 3, 5] against the shared unconditional
+            conditioning, one scale per sample (stedm_ddim_step_rows) - only when style_drop_rate > 0 and the sampling is not "dummy"
+            (:193).
+        Each batch is decoded once and converted by images_for_saving's uint8 rule.
+
+        Declared differences: the reference draws eight independent torch.randn x_T; here x_T are the per-sample Philox streams of
+        (seed, sample ids 0 - 3 unguided, 4 - 7 guided), seed defaulting to one draw from torch's CPU generator. The module's train / eval
+        flags are restored afterwards (the reference leaves eval() set)."""
+        from PIL import Image
+        from . import parallel as par
+        cfg, m = self._cfg, self._model
+        if test_folder is None:
+            test_folder = cfg.location.data_dir + "/" + cfg.data.test_folder
+        scfg = cfg.style_sampling
+        sname = scfg["name"] if isinstance(scfg, dict) else scfg.name
+        dev = m.device
+        test_img = (np.array(Image.open(os.path.join(test_folder, "test_c.png")).convert("L")) > 0).astype(np.uint8)
+        seg = torch.nn.functional.one_hot(torch.from_numpy(test_img).to(torch.long), num_classes=2).unsqueeze(0).to(torch.float32)
+        H, W = test_img.shape
+        sdir = os.path.join(test_folder, sname)
+        load = lambda name: torch.from_numpy(np.array(Image.open(os.path.join(sdir, name)))[:, :, :3]).to(torch.float32)[None, None] / 127.5 - 1
+        if sname == "nearby":
+            styles = [load(f"{i}_img.png") for i in range(4)]
+        elif sname == "mp":
+            num = scfg["num_patches"] if isinstance(scfg, dict) else scfg.num_patches
+            styles = [torch.cat([load(f"{i}_img_{k}.png") for k in range(num)], dim=1) for i in range(4)]
+        elif sname == "dummy":
+            styles = [torch.zeros((1, 1, H, W, 3), dtype=torch.float32) / 127.5 - 1] * 4
+        else:
+            raise ValueError(f"sample_test_images: no test styles are defined for style_sampling {sname!r} (nearby, mp, dummy)")
+        guided = float(getattr(cfg, "style_drop_rate", 0.0)) > 0.0 and sname != "dummy"
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+
+        def batch_of(rows):
+            return {"image": torch.zeros((len(rows), H, W, 3), dtype=torch.float32, device=dev),
+                    "segmentation": seg.expand(len(rows), -1, -1, -1).contiguous().to(dev),
+                    "style_imgs": torch.cat([styles[i] for i in rows], dim=0).to(dev)}
+
+        shape = (m.channels, m.image_size, m.image_size)
+        x_T = (lambda first: par.per_sample_normal_device(seed, first, 4, shape, 0, dev)) if torch.device(dev).type == "cuda" else \
+              (lambda first: par.per_sample_normal(seed, list(range(first, first + 4)), shape, stream=0).to(dev))
+        flags = [(mod, mod.training) for mod in self.modules()]
+        graph = m.use_graph
+        out = {}
+        try:
+            m.eval()
+            m.use_graph = True
+            runs = [("Sample Images", [0, 1, 2, 3], 1.0, 0)]
+            if guided:
+                runs.append(("Sample Images CFG", [0, 0, 1, 1], [3.0, 5.0, 3.0, 5.0], 4))
+            for title, rows, scale, first in runs:
+                lat = predict_latents(m, batch_of(rows), ddim_steps=ddim_steps, eta=0.0, cfg_scale=scale, style_sampling=sname, x_T=x_T(first))
+                img, _ = images_for_saving(m.decode_first_stage(lat))
+                out[title] = list(img.cpu().numpy())
+        finally:
+            m.use_graph = graph
+            for mod, was in flags:
+                mod.training = was
+        return out
+
+    def on_train_epoch_end(self):
+        """ldm_diffusion.py:118-221: logs "Train Loss" (when the base class offers `log`: under Lightning), records the wandb id (when a
+        logger exists), renders the monitoring images when cfg.data has `test_folder` (sample_test_images) and hands them to
+        logger.log_image with the reference's titles and captions. The images stay in `last_test_images` ({} without test_folder), so a
+        plain loop without Lightning or a logger gets them too."""
+        loss = self.train_loss()
+        if callable(getattr(self, "log", None)):
+            self.log("Train Loss", loss)
+        try:
+            logger = getattr(self, "logger", None)
+        except RuntimeError:          # a LightningModule that no Trainer holds
+            logger = None
+        if logger is not None and self._wandb_id == "":
+            self._wandb_id = logger.version
+            if hasattr(self, "hparams"):
+                self.hparams["wandb_id"] = self._wandb_id
+        self.last_test_images = {}
+        data = getattr(self._cfg, "data", None)
+        if data is not None and (("test_folder" in data) if isinstance(data, dict) else hasattr(data, "test_folder")):
+            self.last_test_images = self.sample_test_images()
+            if logger is not None:
+                captions = ["Test 0", "Test 1", "Test 2", "Test 3"]
+                for title in ("Sample Images CFG", "Sample Images"):          # the reference's order (:213, :221)
+                    if title in self.last_test_images:
+                        logger.log_image(title, images=self.last_test_images[title], caption=captions)
+
     # ------------------------------------------------------------------------------------------ prediction
     @torch.no_grad()
     def predict_step(self, batch, batch_idx):
@@ -139,7 +242,10 @@ class LDM_Diffusion(_Base):
         sname = cfg.style_sampling["name"] if isinstance(cfg.style_sampling, dict) else cfg.style_sampling.name
         dpm = getattr(cfg, "dpm_solver", None)
         extra = {} if dpm is None else {"dpm_solver": dict(dpm.items() if hasattr(dpm, "items") else vars(dpm).items())}
-        lat = predict_latents(self._model, ldm_batch, ddim_steps=cfg.ddim_steps, eta=cfg.eta, cfg_scale=cfg.cfg_scale, style_sampling=sname,
+        scale = cfg.cfg_scale           # a number, or a list-valued key: one guidance scale per sample of the batch (predict_latents)
+        if not isinstance(scale, (int, float, torch.Tensor, np.ndarray)) and hasattr(scale, "__len__"):
+            scale = [float(v) for v in scale]
+        lat = predict_latents(self._model, ldm_batch, ddim_steps=cfg.ddim_steps, eta=cfg.eta, cfg_scale=scale, style_sampling=sname,
                               sampler=getattr(cfg, "sampler", None) or "ddim", **extra)
         split = getattr(cfg, "first_stage_split", None)
         if split is None:

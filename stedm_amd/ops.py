@@ -1001,6 +1001,40 @@ def ddim_step_ex(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor]
     return x_prev
 
 
+def ddim_step_rows(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], coefs: torch.Tensor, x_prev: torch.Tensor,
+                   scales: torch.Tensor, pred_x0: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, draw: bool = False,
+                   step_idx: Optional[torch.Tensor] = None, n_iters: int = 0, rescale_phi: float = 0.7, seed: int = 0,
+                   first_id: int = 0) -> torch.Tensor:
+    """ddim_step with one guidance scale per sample (stedm_ddim_step_rows). scales: device fp32 [B], read by the kernel when it runs, so
+    a captured launch replays with what the tensor then holds. Row b with scales[b] == 1 takes the unguided branch (e = e_c) and does
+    not read e_u. z: `noise`, or with draw=True row first_id + b of ops.philox_normal(seed, stream 1 + n_iters - 1 - step_idx[0]) drawn in
+    the kernel; neither: no noise term. Any W and H (a sample spans ceil(W / 16) workgroups); x_prev may be x."""
+    _chk(x, name="x")
+    _chk(e_c, name="e_c")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, C, H, W], got {tuple(x.shape)}")
+    B, Cc, H, W = x.shape
+    for t, nm in ((e_c, "e_c"), (e_u, "e_u"), (noise, "noise"), (x_prev, "x_prev"), (pred_x0, "pred_x0")):
+        if t is not None:
+            _chk(t, name=nm)
+            if tuple(t.shape) != tuple(x.shape):
+                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {tuple(x.shape)}")
+    _chk(scales, name="scales")
+    if tuple(scales.shape) != (B,):
+        raise ValueError(f"scales {tuple(scales.shape)} must be [{B}]")
+    if draw and noise is not None:
+        raise ValueError("a given noise tensor and the in-kernel draw exclude each other")
+    if draw and (step_idx is None or int(n_iters) <= 0):
+        raise ValueError("the in-kernel draw needs step_idx (device int32) and n_iters > 0")
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+    check(lib().stedm_ddim_step_rows(x.data_ptr(), e_c.data_ptr(), _ptr(e_u), _ptr(noise), coefs.data_ptr(), _ptr(step_idx), int(n_iters),
+                                     scales.data_ptr(), float(rescale_phi), 1 if draw else 0, int(first_id),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, x_prev.data_ptr(), _ptr(pred_x0), B, Cc, H, W, _stream()),
+          "stedm_ddim_step_rows")
+    return x_prev
+
+
 def ddim_quantize_x0(pred_x0: torch.Tensor, eps: torch.Tensor, coefs: torch.Tensor, codebook: torch.Tensor, x_prev: torch.Tensor,
                      noise: Optional[torch.Tensor] = None, step_idx: Optional[torch.Tensor] = None,
                      idx: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .ddim import DDIMSampler
+from .ddim import DDIMSampler, refuse_guidance_rows
 
 
 class PLMSSampler(object):
@@ -55,7 +55,9 @@ class PLMSSampler(object):
         """plms.py:58-112 -> (x, intermediates). eta != 0 raises ValueError (as the reference); quantize_x0, score_corrector,
         noise_dropout and temperature != 1 raise NotImplementedError, as do per-step `noises` (PLMS draws nothing after x_T) — all before
         any device work. mask / x0 and the keywords mask_noises / mask_seed / sample_id0: as DDIMSampler.sample. callback(i) and
-        img_callback(pred_x0, i) run after iteration i (eager loop)."""
+        img_callback(pred_x0, i) run after iteration i (eager loop). One unconditional_guidance_scale for the batch: per-sample scales
+        (a sequence or 1-D tensor) raise NotImplementedError - DDIMSampler has them."""
+        refuse_guidance_rows(unconditional_guidance_scale, "PLMSSampler")
         if eta != 0:
             raise ValueError('ddim_eta must be 0 for PLMS')
         if quantize_x0 or score_corrector is not None or noise_dropout > 0. or temperature != 1. or kwargs.get("noises") is not None:
@@ -85,6 +87,7 @@ class PLMSSampler(object):
     def plms_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, mask=None, x0=None, mask_noises=None, mask_seed=None, sample_id0=0):
         """plms.py:114-170 (ddim_use_original_steps=False, timesteps=None). x_inter logs the unblended img as the reference does."""
+        refuse_guidance_rows(unconditional_guidance_scale, "PLMSSampler")
         device = self.model.device
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().clone()
         total_steps = self.ddim_timesteps.shape[0]
