@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 22
+#define STEDM_ABI_VERSION 23
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -281,6 +281,19 @@ typedef struct stedm_conv_args {
   void* gn_coop;
   const uint32_t* gn_coop_epoch;
   uint32_t* gn_coop_tmo;
+  /* Optional (ABI 23): a K window. The convolution reads channels [k_chan0, k_chan0 + c1) of 16-bit planes whose pixel rows hold
+   * src16_cstride elements (0: c1), and the matching chunks of a fragment pack that was made for w_cin input channels (0: c1): its result is
+   * the partial sum of that channel range of the wider convolution, so two launches over [0, s) and [s, C) add up to the full one without
+   * repacking anything. All three are multiples of 32, k_chan0 + c1 <= min(src16_cstride, w_cin). The dispatcher's choices (MFMA kind, K
+   * split, block order) follow the window width c1. Plain 3x3 stride-1 single-product problems of the register-streamed kernel only
+   * (w_frag / w_frag16, no fused skip phase): everything else fails, and stedm_conv_rs_ok answers 0. */
+  int32_t src16_cstride;
+  int32_t k_chan0;
+  int32_t w_cin;
+  /* Optional (ABI 23): the residual row of output sample b is read from sample b % res_bmod of `res` (0: sample b) - a partial sum that
+   * several output samples share, e.g. the skip half of a decoder concat convolution under classifier-free guidance, where samples b and
+   * b + B read the same encoder tensor. Same operation order per element. Same forms as the K window. */
+  int32_t res_bmod;
 } stedm_conv_args;
 /* Replaces: GN->SiLU->conv3x3(+bias)(+emb)(+skip) of ResBlock._forward openaimodel.py:268-288,
  * Downsample/Upsample convs (:122-132,:156-173), 1x1 skip_connection (:254), and the 1x1

@@ -14,6 +14,7 @@ constexpr int BN = 128;
 struct ConvParams {
   stedm_conv_args a;
   int M, Hout, Wout, HWout, Cin, taps;
+  int cstride, w_cin;       // elements per pixel row of src16_* and input channels of the fragment pack (= Cin unless a K window is set: stedm_conv_args.src16_cstride / w_cin)
   int whole, nsamp, trows;  // tile geometry
   int wsplit;               // 1: image rows are WIDER than the tile (Wout % tile == 0): a tile is a run of one row, PW = tile + 2 (conv_rs only)
   int PRs, PW, NP;          // patch rows per sample, patch cols, patch positions

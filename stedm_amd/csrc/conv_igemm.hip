@@ -423,6 +423,23 @@ static int conv_setup(ConvParams& p) {
   STEDM_CHECK_ARG(a.B > 0 && a.Hin > 0 && a.Win > 0 && a.cout > 0, "conv_igemm: bad sizes");
   STEDM_CHECK_ARG(a.mm_dtype == STEDM_F16 || a.mm_dtype == STEDM_BF16, "conv_igemm: bad mm_dtype %d", a.mm_dtype);
   p.Cin = a.c1 + a.c2;
+  p.cstride = a.src16_cstride ? a.src16_cstride : p.Cin;
+  p.w_cin = a.w_cin ? a.w_cin : p.Cin;
+  // K window and res_bmod (ABI 23): the plain 3x3 stride-1 single-product problems of the register-streamed kernel. The fused-skip form, the
+  // 1x1 and sub-pixel / space-to-depth kinds, the 3-product modes, the LDS-operand kernels and the fp32-source kernels know neither
+  {
+    const bool kwin = a.src16_cstride || a.k_chan0 || a.w_cin;
+    const bool plain3 = a.src16_hi && !a.src1 && a.c2 == 0 && a.ks == 3 && a.mode == STEDM_CONV_S1 && a.npass == 1 && !a.src16b_hi && (a.w_frag || a.w_frag16) &&
+                        !a.ln_gamma && !a.qkv_q;
+    STEDM_CHECK_ARG(!kwin || (plain3 && a.k_chan0 >= 0 && a.k_chan0 % 32 == 0 && p.cstride % 32 == 0 && p.w_cin % 32 == 0 && a.c1 % 32 == 0 &&
+                              a.k_chan0 + a.c1 <= p.cstride && a.k_chan0 + a.c1 <= p.w_cin),
+                    "conv_igemm: a K window (src16_cstride=%d k_chan0=%d w_cin=%d) needs a plain 3x3 stride-1 single-product problem on src16 planes with "
+                    "w_frag / w_frag16 and no fused skip phase; multiples of 32 with k_chan0 + c1 inside both the plane row and the pack",
+                    a.src16_cstride, a.k_chan0, a.w_cin);
+    STEDM_CHECK_ARG(a.res_bmod == 0 || (a.res_bmod > 0 && a.res && plain3),
+                    "conv_igemm: res_bmod=%d needs res and a plain 3x3 stride-1 single-product problem on src16 planes with w_frag / w_frag16 and no fused skip phase",
+                    a.res_bmod);
+  }
   p.taps = (a.mode == STEDM_CONV_UP_SUBPIXEL || a.mode == STEDM_CONV_S2D) ? 4 : a.ks * a.ks;
   if (a.mode == STEDM_CONV_UP_SUBPIXEL || a.mode == STEDM_CONV_S2D) {
     p.Hout = a.Hin; p.Wout = a.Win;     // tiles are cut on the LOW-RES grid; each tile is computed for the 4 output parities

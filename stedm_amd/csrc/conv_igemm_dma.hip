@@ -18,7 +18,7 @@ int stedm::conv_launch_dma(ConvParams& p, hipStream_t st, bool dry) {
     set_error("conv_igemm(dma): fused skip operand too large (cb=%d)", a.cb);
     return 1;
   }
-  if ((long)a.B * a.Hin * a.Win * p.Cin >= (1L << 31)) {
+  if ((long)a.B * a.Hin * a.Win * (p.cstride > p.Cin ? p.cstride : p.Cin) >= (1L << 31)) {
     set_error("conv_igemm(dma): activation tensor too large for 32-bit element offsets");
     return 1;
   }
@@ -29,6 +29,10 @@ int stedm::conv_launch_dma(ConvParams& p, hipStream_t st, bool dry) {
   if (dry) return rc < 0 ? 1 : 0;
   if (rc < 0 && a.ln_gamma) { set_error("conv_igemm(dma): the register-streamed kernel does not run this LayerNorm-epilogue problem (see stedm_conv_rs_ok)"); return 1; }
   if (rc < 0 && a.qkv_q) { set_error("conv_igemm(dma): the register-streamed kernel does not run this qkv-epilogue problem (see stedm_conv_rs_ok)"); return 1; }
+  if (rc < 0 && (a.src16_cstride || a.k_chan0 || a.w_cin || a.res_bmod || a.out16_stride)) {
+    set_error("conv_igemm(dma): the register-streamed kernel does not run this problem, and no other kernel knows a K window, res_bmod or out16_stride (see stedm_conv_rs_ok)");
+    return 1;
+  }
   if (rc < 0 && a.src16b_hi) { set_error("conv_igemm(dma): no kernel runs this fused skip problem (see stedm_conv_fused_skip_ok)"); return 1; }
   if (rc < 0) { set_error("conv_igemm(dma): no tile configuration fits (Hin=%d Win=%d mode=%d Cin=%d)", a.Hin, a.Win, a.mode, p.Cin); return 1; }
   return rc;

@@ -495,6 +495,10 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
   if STEDM_DBG(p.dbg, 256) { tile_n = 0; tile_m = 0; }
   const int m0 = tile_m * BMT, n0 = tile_n * BN;
   const int nchunks_all = p.Cin / BKC;
+  // K window (stedm_conv_args.k_chan0 / w_cin, the plain 3x3 kinds): the host moved src16_hi and the fragment stream to the window's first
+  // chunk, so only two things differ from the plain form: the pixel rows are p.cstride elements apart and an N-tile of the pack holds
+  // nchunks_w chunks. The chunk walk itself (and the K split's share of it) runs over the window's p.Cin channels as ever.
+  const int nchunks_w = p.w_cin / BKC;
   const int nsteps = split ? nchunks_all / p.ksplit : nchunks_all;   // chunks of this block
   const int cbeg = kz * nsteps;                               // its first chunk
   const int nsteps2_all = FUSE ? a.cb / 64 : 0;      // chunks of the fused 1x1 phase
@@ -593,7 +597,7 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
         const int pos = (aw + 2 * k) * PPI + lpos;
         const int logical = M16 ? lphys : lphys ^ ((pos / RPB) % CPP);
         const int pix = patch_pixel(pos);
-        asrc[k] = (pix >= 0 ? a_hi + (long)pix * p.Cin : zero16) + logical * 8;
+        asrc[k] = (pix >= 0 ? a_hi + (long)pix * p.cstride : zero16) + logical * 8;
         if (P3 && pix < 0) zmask |= 1u << k;
         if (!STEDM_DBG(p.dbg, 2)) {
 #pragma unroll
@@ -720,7 +724,7 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
         tapd[t] = G1 ? 0u : (SUBM ? (unsigned)((t >> 1) * p.PW + (t & 1)) * 32u : (unsigned)((t / 3) * p.PW + (t % 3)) * 32u);
       // weight fragment stream: sub-step g = chunk * 9 + tap at wq + g * 8192, this wave's 4 column fragments at + wn * 4096
       const unsigned char* wq = reinterpret_cast<const unsigned char*>(a.w_frag16) +
-                                (((((size_t)parity * p.tiles_n + tile_n) * nchunks_all + cbeg) * NS) * 8 + wn * 4) * 1024;
+                                (((((size_t)parity * p.tiles_n + tile_n) * nchunks_w + cbeg) * NS) * 8 + wn * 4) * 1024;
       f32x4 acc[8][4];
 #pragma unroll
       for (int i = 0; i < 8; ++i)
@@ -774,7 +778,7 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
       }
     // weight fragment stream: sub-step g = chunk*NS + s lives at wq + g*4096 B (+1024 for the second fragment)
     const unsigned char* wq = reinterpret_cast<const unsigned char*>(a.w_frag) +
-                              ((((size_t)parity * p.tiles_n + tile_n) * nchunks_all + cbeg) * NS * 4 + wn * 2) * 1024;
+                              ((((size_t)parity * p.tiles_n + tile_n) * nchunks_w + cbeg) * NS * 4 + wn * 2) * 1024;
 
     f32x16 acc[WM][2];
     if constexpr (NPERS) {
@@ -1179,7 +1183,9 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
         for (int u = 0; u < 4; ++u) ev[u] = ep[u];
       }
       const bool has_emb = a.emb != nullptr;
-      const float* __restrict__ resp = a.res;
+      // (res_bmod: the sample of this `sub` reads the residual rows of sample b % res_bmod - one block-uniform pointer shift)
+      const int rb_ = a.res_bmod ? __builtin_amdgcn_readfirstlane(sMb[rfirst]) : 0;
+      const float* __restrict__ resp = a.res_bmod ? a.res - (long)(rb_ - rb_ % a.res_bmod) * p.HWout * a.cout : a.res;
       float* __restrict__ outp = a.out;
       typedef T V4T16 __attribute__((ext_vector_type(4)));
       T* __restrict__ o16p = only16 ? reinterpret_cast<T*>(a.out16_hi) : nullptr;
@@ -1237,8 +1243,9 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
           for (int u = 0; u < nv; ++u) v[u] += ep[u];
         }
         if (a.res) {
-          if (vec_ok) { const float4 r4 = *reinterpret_cast<const float4*>(a.res + o); v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w; }
-          else for (int u = 0; u < nv; ++u) v[u] += a.res[o + u];
+          const long ro = a.res_bmod ? o - (long)(sMb[row] - sMb[row] % a.res_bmod) * p.HWout * a.cout : o;     // (the rows of sample b % res_bmod)
+          if (vec_ok) { const float4 r4 = *reinterpret_cast<const float4*>(a.res + ro); v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w; }
+          else for (int u = 0; u < nv; ++u) v[u] += a.res[ro + u];
         }
         if (a.act_out == 2) {   // exact GELU (nn.GELU default), as the LDS kernels' epilogue
 #pragma unroll
@@ -1455,7 +1462,7 @@ static __global__ void __launch_bounds__(256) conv_splitk_reduce_kernel(const st
       for (int z = 1; z < KSMAX; ++z)
         if (KSMAX == 2 || z < ksplit) { v.x += pz[z].x; v.y += pz[z].y; v.z += pz[z].z; v.w += pz[z].w; }
       v.x += add.x; v.y += add.y; v.z += add.z; v.w += add.w;
-      if (a.res) { const float4 r4 = *reinterpret_cast<const float4*>(a.res + o); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
+      if (a.res) { const float4 r4 = *reinterpret_cast<const float4*>(a.res + (a.res_bmod ? o - (long)(b - b % a.res_bmod) * HW * C : o)); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
       if (GN || a.out) *reinterpret_cast<float4*>(a.out + o) = v;      // (16-bit-only form: no fp32 tensor; the GN form always has one: host)
       if (a.out16_hi) {      // 16-bit side output (operand planes of the consumer), single-product modes; out16_stride: into a wider plane
         const long o16 = a.out16_stride ? ((long)b * HW + pix) * a.out16_stride + n : o;
@@ -1596,6 +1603,9 @@ static int conv_rs_try(ConvParams& p, const ConvParams& q, hipStream_t st, bool 
   // write them - there is no fp32 tensor for the dispatcher's extra pass; a strided out16 plane belongs to the generic row loop / reduce pass
   if (!q.a.out && q.a.chan_stats && !stats) return -1;
   if (q.a.out16_stride && (KIND == RS_1X1N || P3)) return -1;
+  // a K window / res_bmod: the plain 3x3 kinds alone (conv_setup has checked the arguments; this keeps every other instantiation out)
+  const bool kwin = q.a.src16_cstride || q.a.k_chan0 || q.a.w_cin;
+  if ((kwin || q.a.res_bmod) && !((KIND == RS_3X3 || KIND == RS_3X3M) && !FUSE && !P3)) return -1;
   if (dry) return 0;
   p = q;
   p.mg_hw = flat ? 0u : magic(p.HWout); p.mg_w = magic(p.Wout); p.mg_pw = magic(p.PW); p.mg_prpw = magic(p.PRs * p.PW);
@@ -1646,6 +1656,13 @@ static int conv_rs_try(ConvParams& p, const ConvParams& q, hipStream_t st, bool 
   }
   ConvParams kp = p;
   if (!stats) kp.a.chan_stats = nullptr;
+  if (q.a.k_chan0) {
+    // the window's first chunk: a channel is 2 bytes of a pixel row and 9 taps x 256 bytes of an N-tile's fragment stream in both
+    // fragment orders (16 channels x 9 x 4 KiB, 32 channels x 9 x 8 KiB)
+    kp.a.src16_hi = reinterpret_cast<const unsigned char*>(q.a.src16_hi) + (size_t)q.a.k_chan0 * 2;
+    if (q.a.w_frag) kp.a.w_frag = reinterpret_cast<const unsigned char*>(q.a.w_frag) + (size_t)q.a.k_chan0 * 9 * 256;
+    if (q.a.w_frag16) kp.a.w_frag16 = reinterpret_cast<const unsigned char*>(q.a.w_frag16) + (size_t)q.a.k_chan0 * 9 * 256;
+  }
   auto k = conv_rs_kernel<T, WM, KIND, FUSE, P3>;
   const size_t lds_launch = lds + (p.gn_coop ? (size_t)4 * 128 * 2 * sizeof(float) : 0);     // + the partner tiles' channel sums
   static size_t lds_set = 0;     // per instantiation: the attribute only ever grows (one driver call per new maximum)

@@ -508,9 +508,12 @@ def conv_igemm(src1: Optional[torch.Tensor], w_hi: torch.Tensor, w_lo: Optional[
                skip: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None, query_fused: bool = False, query_rs: bool = False,
                ws: Optional[torch.Tensor] = None, pad_br: bool = False, w_frag16: Optional[torch.Tensor] = None,
                gn_next: Optional[tuple] = None, qkv_planes: Optional[tuple] = None, ln_after: Optional[tuple] = None, coop: Optional[tuple] = None,
-               out16_stride: int = 0, cout: Optional[int] = None):
+               out16_stride: int = 0, cout: Optional[int] = None, res_bmod: int = 0):
     """src1 [B,Hin,Win,c1] NHWC fp32 (fused path) and/or src16 = (hi, lo) 16-bit NHWC planes [B,Hin,Win,Cin] from
     gn_apply16 (DMA path) -> out [B,Hout,Wout,cout] NHWC fp32 (see stedm_conv_igemm).
+    src16[0] may be a channel-narrowed (and batch-narrowed) view plane[b0:b1, :, :, k0:k1] of a contiguous plane: a K window
+    (stedm_conv_args.src16_cstride / k_chan0 / w_cin) - the convolution sums channels [k0, k1) only, against the matching chunks of the
+    fragment pack of the full filter. res_bmod: output sample b adds the residual rows of sample b % res_bmod (stedm_conv_args.res_bmod).
     qkv_planes = (q, k, vt, T, Tp, heads, qscale): the LSA attention's operand planes as the only output of a flat to_qkv GEMM
     (stedm_conv_args.qkv_*; out and out16 None).
     ln_after = (gamma, beta, eps, res): LayerNorm over the output row (cout <= 128) + optional fp32 residual in the epilogue
@@ -521,6 +524,8 @@ def conv_igemm(src1: Optional[torch.Tensor], w_hi: torch.Tensor, w_lo: Optional[
         if not conv3x3_tiles_ok(Ho_, Wo_):
             if query_fused or query_rs:
                 return False
+            if not src16[0].is_contiguous() or res_bmod:
+                raise _lib.StedmHipError("conv_igemm: a K window / res_bmod belongs to the tiled register-streamed kernel; this output grid takes the im2col form")
             return _conv3x3_generic(src16, w_hi, w_lo, out, prec=prec, mode=mode, scale=scale, shift=shift, act=act, bias=bias, emb=emb,
                                     emb_offset=emb_offset, emb_bstride=emb_bstride, res=res, act_out=act_out, out16=out16, chan_stats=chan_stats,
                                     skip=skip, ws=ws, gn_next=gn_next)
@@ -606,10 +611,34 @@ def conv_igemm(src1: Optional[torch.Tensor], w_hi: torch.Tensor, w_lo: Optional[
     else:
         B, Hin, Win, c1 = src16[0].shape
         c2 = 0
+    kwin = False
     if src16 is not None:
-        assert src16[0].dtype == torch.int16 and src16[0].is_contiguous() and tuple(src16[0].shape) == (B, Hin, Win, c1 + c2)
-        a.src16_hi = src16[0].data_ptr()
+        s16 = src16[0]
+        assert s16.dtype == torch.int16 and tuple(s16.shape) == (B, Hin, Win, c1 + c2)
+        a.src16_hi = s16.data_ptr()
         a.src16_lo = _ptr(src16[1]) if prec.npass == 3 else None
+        if not s16.is_contiguous():
+            # a K window: channels [k0, k0 + c1) of a plane whose pixel rows hold cs elements (both from the view's strides / storage offset)
+            cs = s16.stride(2)
+            base = s16._base if s16._base is not None else s16
+            k0 = (s16.storage_offset() - base.storage_offset()) % cs
+            assert src1 is None and tuple(s16.stride()) == (Hin * Win * cs, Win * cs, cs, 1) and k0 + c1 <= cs, \
+                "src16[0] must be contiguous or a view plane[b0:b1, :, :, k0:k1] of a contiguous plane"
+            assert cs % 32 == 0 and k0 % 32 == 0 and c1 % 32 == 0, "a K window is cut on 32-channel boundaries"
+            kwin = True
+            a.src16_hi = s16.data_ptr() - 2 * k0          # channel 0 of the view's first pixel row: the kernel walks from k_chan0
+            if a.src16_lo is not None:
+                assert tuple(src16[1].stride()) == tuple(s16.stride()) and src16[1].storage_offset() == s16.storage_offset()
+                a.src16_lo = src16[1].data_ptr() - 2 * k0
+            a.src16_cstride, a.k_chan0 = cs, k0
+            # input channels of the pack: [.., N-tiles, chunks, taps, fragments, 64, 8] with chunks of 16 (w_frag) or 32 (w_frag16) channels
+            wplanes = w_hi._val[0] if isinstance(w_hi, LazyPlanes) and w_hi._val is not None else (None if isinstance(w_hi, LazyPlanes) else w_hi)
+            a.w_cin = (w_frag.shape[-5] * 16 if w_frag is not None and prec.npass == 1 else
+                       w_frag16.shape[-5] * 32 if w_frag16 is not None else wplanes.shape[-1] if wplanes is not None else cs)
+            assert w_frag is None or w_frag16 is None or w_frag.shape[-5] * 16 == w_frag16.shape[-5] * 32
+    a.res_bmod = int(res_bmod)
+    if res_bmod:
+        assert res is not None and res.is_contiguous() and res.dtype == torch.float32 and B % res_bmod == 0 and res.shape[0] >= res_bmod
     a.c1, a.c2, a.src2_bmod = c1, c2, src2_bmod
     a.B, a.Hin, a.Win = B, Hin, Win
     a.mode, a.ks = mode, ks
@@ -635,7 +664,7 @@ def conv_igemm(src1: Optional[torch.Tensor], w_hi: torch.Tensor, w_lo: Optional[
         assert w_hi is None and (w_frag is not None or w_frag16 is not None) and src1 is None, \
             "the space-to-depth form runs on the register-streamed kernel only"
     else:
-        assert w_hi.shape == (a.cout, ks * ks, a.c1 + a.c2), (w_hi.shape, a.cout, ks, a.c1, a.c2)
+        assert w_hi.shape == (a.cout, ks * ks, a.w_cin if kwin else a.c1 + a.c2), (w_hi.shape, a.cout, ks, a.c1, a.c2)
     if query_fused:     # capability query only: would this (fused) problem run as one kernel?
         return bool(lib().stedm_conv_fused_skip_ok(C.byref(a)))
     if query_rs:        # capability query only: would the register-streamed kernel run this problem?

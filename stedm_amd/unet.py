@@ -233,6 +233,9 @@ class UNetModel(nn.Module):
         self._mr_ctr = 0
         self._plane_ctr = 0
         self._tape: Optional[list] = None     # training forward (stedm_amd/train.py): one record per layer for the backward pass
+        # forward_cfg: the skip half of a decoder concat convolution once per CFG pair (_shared_skip). None: the rule of
+        # _shared_skip_rule decides per site; True / False: every admissible site / none
+        self.cfg_shared_skip: Optional[bool] = None
 
     # ------------------------------------------------------------------------------------ engine plumbing
     def convert_to_fp16(self):  # openaimodel.py:745-751 — a no-op in the reference too (openaimodel.py:25-29)
@@ -582,9 +585,9 @@ class UNetModel(nn.Module):
                 ops.gn_apply16c_x16(co, self._cs[h.data_ptr()], None, None, h16_next[0], hraw, prec, gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1)
                 done1 = True
         if not done1:
-            ops.conv_igemm(None, pk.hi, pk.lo, h, prec=prec, src16=a16, bias=pk.bias, emb=emb_all, emb_offset=emb_off,
-                           emb_bstride=emb_bstride, w_frag=pk.frag, chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16, gn_next=gn_next,
-                           coop=coop)
+            kw1 = dict(prec=prec, bias=pk.bias, emb=emb_all, emb_offset=emb_off, emb_bstride=emb_bstride, w_frag=pk.frag,
+                       chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16, gn_next=gn_next, coop=coop)
+            self._in_conv(tag, rb, pk, a16, x1.shape[-1], x2_bmod if x2 is not None else 0, h, kw1)
         out = self._buf(tag + ".out", (B, H, W, co))
         pk2 = self._packed[id(rb.out_layers[3])]
         o16 = None
@@ -672,6 +675,69 @@ class UNetModel(nn.Module):
         ops.conv_igemm(None, pk2.hi, pk2.lo, out, prec=prec, src16=h16, bias=pk2.bias, res=x1, w_frag=pk2.frag,
                        chan_stats=self._cs_new(out), ws=ws, out16=o16, w_frag16=pk2.frag16, gn_next=gnn, coop=coop2)
         return filed()
+
+    def _in_conv(self, tag: str, rb: ResBlock, pk, a16, c1: int, x2_bmod: int, h, kw) -> None:
+        """in_layers' convolution of a ResBlock over the normalised planes a16 of [x1 | x2] (c1 = channels of x1). Under forward_cfg the
+        decoder runs at batch 2B = [cond | uncond] while x2, the encoder's skip tensor, is read modulo B: every skip channel whose
+        GroupNorm group holds skip channels only carries the same bits in samples b and b + B, and the convolution is linear in its input
+        channels. Where _shared_skip admits the site, that K range is summed once, over batch B, into an fp32 partial P, and the 2B launch
+        walks the remaining channels and adds P[b % B] as its residual - two launches on the same stream, nothing repacked."""
+        plan = self._shared_skip(rb, pk, a16, c1, x2_bmod, h, kw)
+        if plan is None:
+            ops.conv_igemm(None, pk.hi, pk.lo, h, src16=a16, **kw)
+            return
+        seam, P = plan
+        Bs = P.shape[0]
+        ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:Bs, :, :, seam:], None), w_frag=pk.frag, w_frag16=pk.frag16, ws=kw["ws"])
+        ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P, res_bmod=Bs, **kw)
+
+    def _shared_skip(self, rb: ResBlock, pk, a16, c1: int, x2_bmod: int, h, kw):
+        """(seam, P) when the in_layers convolution of `rb` runs as shared launch + 2B launch (_in_conv), else None. Inference, one CFG pair
+        (decoder batch = 2 x2_bmod), single product, both launches admitted by stedm_conv_rs_ok; then cfg_shared_skip or the rule."""
+        Bd, H, W, co = h.shape
+        if (self.cfg_shared_skip is False or self._tape is not None or self.precision.npass != 1 or x2_bmod <= 0 or Bd != 2 * x2_bmod or
+                a16[0].shape[0] != Bd or not a16[0].is_contiguous()):
+            return None
+        key = ("sskip", id(rb), Bd, H, W, self.cfg_shared_skip)
+        hit = self._consts.get(key)
+        if hit is None:
+            norm = rb.in_layers[0]
+            C = a16[0].shape[-1]
+            cpg = C // norm.num_groups
+            # first 32-channel boundary from which every GroupNorm group holds skip channels only; one chunk further when that makes the
+            # shared chunk count even (the K split of a small grid halves it: 15 chunks would not split, 14 do)
+            seam = -(-(-(-c1 // cpg) * cpg) // 32) * 32
+            if (C - seam) // 32 > 1 and ((C - seam) // 32) % 2:
+                seam += 32
+            hit = 0
+            if 32 <= seam <= C - 32 and (pk.frag is not None or pk.frag16 is not None):
+                P = self._buf(f"sskip.P.{x2_bmod}x{H}x{W}x{co}", (x2_bmod, H, W, co))
+                ok = bool(ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:x2_bmod, :, :, seam:], None), w_frag=pk.frag,
+                                         w_frag16=pk.frag16, ws=kw["ws"], query_rs=True))
+                ok = ok and bool(ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P, res_bmod=x2_bmod, query_rs=True, **kw))
+                if ok and (self.cfg_shared_skip or self._shared_skip_rule(Bd, H, W, co, C, seam)):
+                    hit = seam
+            self._consts[key] = hit
+        if not hit:
+            return None
+        return hit, self._buf(f"sskip.P.{x2_bmod}x{H}x{W}x{co}", (x2_bmod, H, W, co))
+
+    @staticmethod
+    def _shared_skip_rule(Bd: int, H: int, W: int, co: int, C: int, seam: int) -> bool:
+        """Does the pair beat the single launch at this site? From the per-site measurement (tools/shared_skip_sites.py):
+        the saving is the shared channels' MFMA work at half the batch, the cost a second launch's per-tile fixed cost (tables, first patch,
+        epilogue), the partial's store and its read. Measured at decoder batch 128: 14 shared chunks of 32 channels win where the shared
+        launch fills the chip without a K split (16^2: +27 us of 337) and break even where it needs one (8^2: -2 us of 181: the reduce pass
+        eats the gain); 32 chunks win either way (+28 .. +34 us of 235); 2 .. 4 chunks lose 10 .. 15 us everywhere. A decoder batch whose
+        own launch does not fill the chip (K-split grids, priced by their fixed cost) was not measured and stays on the single launch."""
+        cus = ops.device_cus()
+
+        def fills(b):      # conv_rs_pick's own test: 256-row x 128-channel tiles against 3/4 of the chip
+            tiles_m = -(-b * H * W // 256) if H * W >= 256 else -(-b // (256 // (H * W)))
+            return tiles_m * -(-co // 128) * 4 >= cus * 3
+        if not fills(Bd):
+            return False
+        return (C - seam) // 32 >= (14 if fills(Bd // 2) else 32)
 
     def _attn(self, tag: str, ab: AttentionBlock, x):
         """AttentionBlock._forward openaimodel.py:340-346 on NHWC (tokens = H*W)."""
