@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 23
+#define STEDM_ABI_VERSION 24
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -294,6 +294,16 @@ typedef struct stedm_conv_args {
    * several output samples share, e.g. the skip half of a decoder concat convolution under classifier-free guidance, where samples b and
    * b + B read the same encoder tensor. Same operation order per element. Same forms as the K window. */
   int32_t res_bmod;
+  /* Optional (ABI 24): a second residual. The residual of an element becomes t = res[o'] + res2[o'] (both addressed through res_bmod), then
+   * v += t: with res / res2 the two K-share partials of a two-way split this gives the bits of a route that first reduces them to one
+   * tensor. Needs res. Honoured where res_bmod is (the plain 3x3 stride-1 single-product kinds of the register-streamed kernel and the
+   * split-K finish pass); everything else fails, and stedm_conv_rs_ok answers 0. */
+  const float* res2;
+  /* Optional (ABI 24), stedm_conv_finish only: the partials in `ws` were written at batch ws_bmod, and output sample b sums the partial rows
+   * of sample b % ws_bmod (0: sample b). Bias, the embedding row emb + b * emb_bstride, the residual, chan_stats, out16 and the riding
+   * GroupNorm stay per output sample; same operation order per element (p0 + p1 (+ ...), + (bias + emb), + residual). stedm_conv_igemm
+   * refuses a non-zero value. */
+  int32_t ws_bmod;
 } stedm_conv_args;
 /* Replaces: GN->SiLU->conv3x3(+bias)(+emb)(+skip) of ResBlock._forward openaimodel.py:268-288,
  * Downsample/Upsample convs (:122-132,:156-173), 1x1 skip_connection (:254), and the 1x1
@@ -312,6 +322,19 @@ int stedm_im2col_rows16(const void* src16, void* dst16, int B, int Hs, int Ws, i
 /* 1 when the register-streamed kernel (w_frag) takes this problem: w_hi / w_lo are then never read, so the caller may skip packing
  * them and pass any non-NULL w_hi. Same decision path as stedm_conv_igemm; nothing is launched. */
 int stedm_conv_rs_ok(const stedm_conv_args* args);
+/* The two halves of a split-K call, launched separately (ABI 24): a convolution evaluated once for several output samples that share its
+ * input and differ only in what the finish pass adds (the style block's in_layers convolution under classifier-free guidance: samples b
+ * and b + B). Plain 3x3 stride-1 single-product problems of the register-streamed kernel (the forms that take res_bmod).
+ * stedm_conv_partials: the convolution of `args` at batch args->B leaves its K-share partials in args->ws as [*nshare][B][Hout][Wout][cout]
+ * raw fp32 sums and launches no reduce; bias, emb, res, out, out16, chan_stats and gn_* of `args` are not used. *nshare is the share count
+ * the dispatcher chose with that workspace (2 .. 16), or 1 when it did not split: the launch then wrote the raw tile sums (no bias, no
+ * embedding) as the one partial. ws_floats must hold the partials. With dry != 0 nothing is launched: 0 when the call would run.
+ * stedm_conv_finish: the reduce pass on its own. args->B is the OUTPUT batch, a multiple of args->ws_bmod (the partials' batch; 0: B);
+ * out [B][Hin][Win][cout] = sum of the nshare (1 .. 16) partials + (bias + emb row) + residual (res / res2 / res_bmod), with chan_stats,
+ * out16_hi (+ out16_stride) and the riding GroupNorm gn_* as in a split-K stedm_conv_igemm call: the GroupNorm rides in the pass where a
+ * sample has at most 256 pixels, otherwise the call ends with the stedm_gn_apply16c pass. Reads no src / weight field of `args`. */
+int stedm_conv_partials(const stedm_conv_args* args, int32_t* nshare, int dry, void* stream);
+int stedm_conv_finish(const stedm_conv_args* args, int nshare, void* stream);
 
 /* ---- boundary convs (NCHW <-> NHWC) ------------------------------------------------------- */
 /* input_blocks.0: conv3x3(cat([x, c_concat],1)) — DiffusionWrapper hybrid ddpm.py:1414-1417 +

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 
@@ -45,6 +45,7 @@ class ConvArgs(C.Structure):
         ("out16_stride", C.c_int32),
         ("gn_coop", C.c_void_p), ("gn_coop_epoch", C.c_void_p), ("gn_coop_tmo", C.c_void_p),
         ("src16_cstride", C.c_int32), ("k_chan0", C.c_int32), ("w_cin", C.c_int32), ("res_bmod", C.c_int32),
+        ("res2", C.c_void_p), ("ws_bmod", C.c_int32),
     ]
 
 
@@ -88,6 +89,8 @@ SIGNATURES = {
     "stedm_conv_igemm": (_I, [C.POINTER(ConvArgs), _P]),
     "stedm_conv_fused_skip_ok": (_I, [C.POINTER(ConvArgs)]),
     "stedm_conv_rs_ok": (_I, [C.POINTER(ConvArgs)]),
+    "stedm_conv_partials": (_I, [C.POINTER(ConvArgs), C.POINTER(C.c_int32), _I, _P]),
+    "stedm_conv_finish": (_I, [C.POINTER(ConvArgs), _I, _P]),
     "stedm_conv_in": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "stedm_conv_out": (_I, [_P, _I, _P, _I, _P, _P, _F, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "stedm_time_embed": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -26,6 +26,8 @@ struct ConvParams {
   int gn_tile;     // register-streamed kernel: its tiles hold whole samples x whole groups -> the epilogue writes a.gn_out16 (conv_rs_try)
   int gn_coop;     // ... or 2 .. 4: tiles per sample that exchange their channel sums inside the launch (a.gn_coop, conv_rs.inc) and then do the same
   int xcd_m;       // register-streamed kernel: XCD-aware block -> tile order: 0 plain, else gm in {8, 4, 2} = the M-tiles are dealt over gm XCD groups, the N-tiles over 8 / gm (conv_rs_kernel)
+  int partials;    // host only: stedm_conv_partials - the K-share partials (or, without a split, the raw tile sums) stay in a.ws and no reduce pass is launched
+  int nshare;      // host only: ... and how many partial planes that launch left there (conv_rs_try)
   int npers;       // register-streamed 1x1 kind: N-persistent form (one block per M-tile walks all N-tiles; conv_rs_try)
   unsigned* ovf;   // fp16 operand range guard flag (common.hpp) or nullptr; set by the dispatcher for fp16 launches
   int dbg;  // ablation bits (STEDM_CONV_DBG; DIAGNOSTIC BUILDS ONLY, see STEDM_DBG below): 1 no weight DMA, 2 no patch staging, 4 no MFMA, 8 no LDS frag reads
@@ -76,4 +78,8 @@ namespace stedm {
 bool conv_geometry(ConvParams& p, int bm, bool allow_wsplit = false);
 // v3 (LDS-DMA operands from 16-bit activation planes); 0 ok, > 0 error (message set).
 int conv_launch_dma(ConvParams& p, hipStream_t st, bool dry = false);
+// The split-K reduce pass on its own (stedm_conv_finish): sums `nshare` partial planes of a.ws (rows of sample b % a.ws_bmod) into a.out /
+// a.out16_hi with bias, embedding row, residual, statistics and, where a block owns whole groups, the riding GroupNorm. Sets p.stats_done /
+// p.gn_done like a split-K launch. 0 ok, > 0 error (message set).
+int conv_splitk_finish(ConvParams& p, int nshare, hipStream_t st);
 }  // namespace stedm

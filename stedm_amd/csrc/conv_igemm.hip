@@ -348,7 +348,7 @@ extern "C" int stedm_conv_fused_skip_ok(const stedm_conv_args* args) {
 // caller may skip packing them (pass any non-NULL w_hi). Same decision path as stedm_conv_igemm, nothing is launched. (npass = 3: with the
 // hi + lo streams in w_frag16.)
 extern "C" int stedm_conv_rs_ok(const stedm_conv_args* args) {
-  if (!args || !args->src16_hi || (!args->w_frag && !args->w_frag16) || (args->npass != 1 && !args->w_frag16)) return 0;
+  if (!args || !args->src16_hi || (!args->w_frag && !args->w_frag16) || (args->npass != 1 && !args->w_frag16) || args->ws_bmod) return 0;
   ConvParams p;
   memset(&p, 0, sizeof(p));
   p.a = *args;
@@ -356,22 +356,10 @@ extern "C" int stedm_conv_rs_ok(const stedm_conv_args* args) {
   return conv_launch_dma(p, nullptr, /*dry=*/true) == 0 ? 1 : 0;
 }
 
-extern "C" int stedm_conv_igemm(const stedm_conv_args* args, void* stream) {
-  STEDM_CHECK_ARG(args, "conv_igemm: null args");
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.a = *args;
+// What a call still owes after its launch(es): the statistics / the consumer's GroupNorm as passes of their own where no launch wrote them
+static int conv_trailing(ConvParams& p, void* stream) {
   const stedm_conv_args& a = p.a;
-  STEDM_CHECK_ARG(!a.chan_stats || a.out || (a.out16_hi && !a.out16_lo && a.npass == 1), "conv_igemm: chan_stats needs the fp32 output (or, single product, the 16-bit-only form)");
-  STEDM_CHECK_ARG(a.out16_stride == 0 || (a.out16_hi && !a.out16_lo && a.npass == 1 && a.out16_stride >= a.cout && a.out16_stride % 4 == 0 && a.cout % 4 == 0 &&
-                                          !a.ln_gamma && !a.qkv_q && !a.act_out),
-                  "conv_igemm: out16_stride needs out16_hi alone (single product), stride >= cout, both multiples of 4, plain epilogue");
-  STEDM_CHECK_ARG(!a.gn_out16 || (a.out && a.chan_stats && a.gn_gamma && a.gn_beta && a.gn_groups > 0 && a.cout % a.gn_groups == 0 &&
-                                  (a.npass == 1 || a.gn_out16_lo) && a.mode == STEDM_CONV_S1 && (a.gn_act == 0 || a.gn_act == 1)),
-                  "conv_igemm: gn_out16 needs out, chan_stats, gamma / beta, groups dividing cout, stride 1 and a single-product mode (or gn_out16_lo)");
-  STEDM_CHECK_ARG(!a.gn_out16_lo || a.gn_out16, "conv_igemm: gn_out16_lo without gn_out16");
-  int rc = conv_dispatch(p, stream);
-  if (rc != 0) return rc;
+  int rc = 0;
   if (a.chan_stats && !p.stats_done && !a.out) {      // (cannot happen: conv_rs_try declines the 16-bit-only form when its epilogue would not write the statistics)
     set_error("conv_igemm: the 16-bit-only form with chan_stats ran on a kernel without the statistics epilogue");
     return 1;
@@ -389,6 +377,84 @@ extern "C" int stedm_conv_igemm(const stedm_conv_args* args, void* stream) {
                               a.gn_beta, a.gn_eps, a.gn_groups, a.gn_act, a.B, HW, a.gn_out16, a.gn_out16_lo, nullptr, nullptr, a.gn_mr, a.mm_dtype, stream);
   }
   return rc;
+}
+
+
+extern "C" int stedm_conv_igemm(const stedm_conv_args* args, void* stream) {
+  STEDM_CHECK_ARG(args, "conv_igemm: null args");
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.a = *args;
+  const stedm_conv_args& a = p.a;
+  STEDM_CHECK_ARG(!a.chan_stats || a.out || (a.out16_hi && !a.out16_lo && a.npass == 1), "conv_igemm: chan_stats needs the fp32 output (or, single product, the 16-bit-only form)");
+  STEDM_CHECK_ARG(a.out16_stride == 0 || (a.out16_hi && !a.out16_lo && a.npass == 1 && a.out16_stride >= a.cout && a.out16_stride % 4 == 0 && a.cout % 4 == 0 &&
+                                          !a.ln_gamma && !a.qkv_q && !a.act_out),
+                  "conv_igemm: out16_stride needs out16_hi alone (single product), stride >= cout, both multiples of 4, plain epilogue");
+  STEDM_CHECK_ARG(!a.gn_out16 || (a.out && a.chan_stats && a.gn_gamma && a.gn_beta && a.gn_groups > 0 && a.cout % a.gn_groups == 0 &&
+                                  (a.npass == 1 || a.gn_out16_lo) && a.mode == STEDM_CONV_S1 && (a.gn_act == 0 || a.gn_act == 1)),
+                  "conv_igemm: gn_out16 needs out, chan_stats, gamma / beta, groups dividing cout, stride 1 and a single-product mode (or gn_out16_lo)");
+  STEDM_CHECK_ARG(!a.gn_out16_lo || a.gn_out16, "conv_igemm: gn_out16_lo without gn_out16");
+  STEDM_CHECK_ARG(a.ws_bmod == 0, "conv_igemm: ws_bmod belongs to stedm_conv_finish");
+  int rc = conv_dispatch(p, stream);
+  if (rc != 0) return rc;
+  return conv_trailing(p, stream);
+}
+
+// Partials only (stedm_hip.h): the plain 3x3 problem of `args` with everything the finish pass owns taken out. The launch is the ordinary
+// one: with a K split the kernel writes its share's raw tile to ws and conv_rs_try stops before the reduce; without one `out` = ws
+// receives the raw tile sums. The dispatcher sees what a full call with an fp32 output sees, so it picks the same split.
+extern "C" int stedm_conv_partials(const stedm_conv_args* args, int32_t* nshare, int dry, void* stream) {
+  STEDM_CHECK_ARG(args && nshare, "conv_partials: null args");
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.a = *args;
+  stedm_conv_args& a = p.a;
+  STEDM_CHECK_ARG(a.ws && !a.act_out && !a.out16_lo && a.ws_bmod == 0 && a.cout > 0 && a.cout % 4 == 0 && (!a.emb || a.emb_bstride % 4 == 0),
+                  "conv_partials: needs ws, no act_out / out16_lo / ws_bmod, cout %% 4 == 0 (and emb_bstride %% 4 == 0 for the finish pass)");
+  STEDM_CHECK_ARG(a.src16_hi && !a.src1 && a.c2 == 0 && a.ks == 3 && a.mode == STEDM_CONV_S1 && a.npass == 1 && !a.src16b_hi && (a.w_frag || a.w_frag16) && !a.ln_gamma && !a.qkv_q,
+                  "conv_partials: needs a plain 3x3 stride-1 single-product problem on src16 planes with w_frag / w_frag16 and no fused skip phase");
+  STEDM_CHECK_ARG(a.ws_floats >= (int64_t)a.B * a.Hin * a.Win * a.cout, "conv_partials: ws_floats=%lld holds no partial of %d x %d x %d x %d", (long long)a.ws_floats, a.B, a.Hin, a.Win, a.cout);
+  a.out = a.ws;
+  a.bias = a.bias_b = a.emb = a.res = a.res2 = nullptr;
+  a.res_bmod = 0;
+  a.out16_hi = nullptr; a.out16_stride = 0;
+  a.chan_stats = nullptr; a.chan_nslab = 0;
+  a.gn_out16 = a.gn_out16_lo = a.gn_coop = nullptr; a.gn_mr = nullptr; a.gn_only = 0;
+  p.partials = 1;
+  int rc;
+  if (dry) {
+    rc = conv_setup(p);
+    if (rc == 0) rc = conv_launch_dma(p, nullptr, /*dry=*/true);
+  } else rc = conv_dispatch(p, stream);
+  if (rc != 0) return rc;
+  *nshare = p.nshare;
+  return 0;
+}
+
+extern "C" int stedm_conv_finish(const stedm_conv_args* args, int nshare, void* stream) {
+  STEDM_CHECK_ARG(args, "conv_finish: null args");
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.a = *args;
+  const stedm_conv_args& a = p.a;
+  STEDM_CHECK_ARG(a.B > 0 && a.Hin > 0 && a.Win > 0 && a.cout > 0 && a.cout % 4 == 0 && (a.mm_dtype == STEDM_F16 || a.mm_dtype == STEDM_BF16), "conv_finish: bad sizes / mm_dtype");
+  STEDM_CHECK_ARG(nshare >= 1 && nshare <= 16 && a.ws, "conv_finish: nshare=%d must be 1 .. 16 partial planes in ws", nshare);
+  STEDM_CHECK_ARG(a.ws_bmod >= 0 && (a.ws_bmod == 0 || a.B % a.ws_bmod == 0), "conv_finish: ws_bmod=%d must divide B=%d", a.ws_bmod, a.B);
+  STEDM_CHECK_ARG(a.ws_floats >= (int64_t)nshare * (a.ws_bmod ? a.ws_bmod : a.B) * a.Hin * a.Win * a.cout, "conv_finish: ws_floats=%lld is short of %d partial planes", (long long)a.ws_floats, nshare);
+  STEDM_CHECK_ARG((a.out || a.out16_hi) && !a.out16_lo && !a.act_out && !a.src16b_hi && !a.ln_gamma && !a.qkv_q && a.mode == STEDM_CONV_S1 && (!a.emb || a.emb_bstride % 4 == 0),
+                  "conv_finish: needs out or out16_hi, stride 1, emb_bstride %% 4 == 0 and none of out16_lo / act_out / fused skip / LayerNorm / qkv");
+  STEDM_CHECK_ARG(a.res_bmod >= 0 && (a.res_bmod == 0 || a.res) && (!a.res2 || a.res), "conv_finish: res_bmod / res2 need res");
+  STEDM_CHECK_ARG(!a.chan_stats || a.out || a.out16_hi, "conv_finish: chan_stats needs an output");
+  STEDM_CHECK_ARG(a.out16_stride == 0 || (a.out16_hi && a.out16_stride >= a.cout && a.out16_stride % 4 == 0), "conv_finish: out16_stride needs out16_hi, stride >= cout, a multiple of 4");
+  STEDM_CHECK_ARG(!a.gn_out16 || (a.out && a.chan_stats && a.gn_gamma && a.gn_beta && a.gn_groups > 0 && a.cout % a.gn_groups == 0 && (a.npass == 1 || a.gn_out16_lo) &&
+                                  (a.gn_act == 0 || a.gn_act == 1)),
+                  "conv_finish: gn_out16 needs out, chan_stats, gamma / beta, groups dividing cout and a single-product mode (or gn_out16_lo)");
+  STEDM_CHECK_ARG(!a.gn_out16_lo || a.gn_out16, "conv_finish: gn_out16_lo without gn_out16");
+  p.HWout = a.Hin * a.Win;
+  p.ovf = a.mm_dtype == STEDM_F16 ? f16_guard_flag() : nullptr;
+  const int rc = conv_splitk_finish(p, nshare, as_stream(stream));
+  if (rc != 0) return rc;
+  return conv_trailing(p, stream);
 }
 
 // validates the arguments and fills the derived sizes of `p`
@@ -439,6 +505,8 @@ static int conv_setup(ConvParams& p) {
     STEDM_CHECK_ARG(a.res_bmod == 0 || (a.res_bmod > 0 && a.res && plain3),
                     "conv_igemm: res_bmod=%d needs res and a plain 3x3 stride-1 single-product problem on src16 planes with w_frag / w_frag16 and no fused skip phase",
                     a.res_bmod);
+    STEDM_CHECK_ARG(!a.res2 || (a.res && plain3 && a.cout % 4 == 0),
+                    "conv_igemm: res2 needs res, cout %% 4 == 0 and a plain 3x3 stride-1 single-product problem on src16 planes with w_frag / w_frag16 and no fused skip phase");
   }
   p.taps = (a.mode == STEDM_CONV_UP_SUBPIXEL || a.mode == STEDM_CONV_S2D) ? 4 : a.ks * a.ks;
   if (a.mode == STEDM_CONV_UP_SUBPIXEL || a.mode == STEDM_CONV_S2D) {

@@ -29,8 +29,8 @@ int stedm::conv_launch_dma(ConvParams& p, hipStream_t st, bool dry) {
   if (dry) return rc < 0 ? 1 : 0;
   if (rc < 0 && a.ln_gamma) { set_error("conv_igemm(dma): the register-streamed kernel does not run this LayerNorm-epilogue problem (see stedm_conv_rs_ok)"); return 1; }
   if (rc < 0 && a.qkv_q) { set_error("conv_igemm(dma): the register-streamed kernel does not run this qkv-epilogue problem (see stedm_conv_rs_ok)"); return 1; }
-  if (rc < 0 && (a.src16_cstride || a.k_chan0 || a.w_cin || a.res_bmod || a.out16_stride)) {
-    set_error("conv_igemm(dma): the register-streamed kernel does not run this problem, and no other kernel knows a K window, res_bmod or out16_stride (see stedm_conv_rs_ok)");
+  if (rc < 0 && (a.src16_cstride || a.k_chan0 || a.w_cin || a.res_bmod || a.res2 || p.partials || a.out16_stride)) {
+    set_error("conv_igemm(dma): the register-streamed kernel does not run this problem, and no other kernel knows a K window, res_bmod / res2, the partials-only form or out16_stride (see stedm_conv_rs_ok)");
     return 1;
   }
   if (rc < 0 && a.src16b_hi) { set_error("conv_igemm(dma): no kernel runs this fused skip problem (see stedm_conv_fused_skip_ok)"); return 1; }

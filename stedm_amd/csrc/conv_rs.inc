@@ -438,6 +438,7 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
   constexpr bool M16 = KIND == RS_3X3M || G1 || SUBM;    // 16x16x32 MFMA forms: tap-0 gather row + uniform tap offsets, no XOR swizzle
   constexpr bool GEO1 = IS1X1 || G1;                     // the patch is the tile's own pixels
   constexpr bool IS3X3 = KIND == RS_3X3 || KIND == RS_3X3M;
+  constexpr bool RES2 = IS3X3 && !FUSE && !P3;           // stedm_conv_args.res2 (host: the kinds that take res_bmod); every other instantiation compiles none of it
   constexpr int NS = IS3X3 ? 9 : (SUBM ? 4 : (SUBPIX ? 8 : (G1 ? 1 : 4)));   // sub-steps per chunk
   constexpr int NPL = (SUBPIX || KIND == RS_3X3M) ? 2 : 1;      // planes per chunk
   constexpr int NTAB = IS3X3 ? 9 : 4;                    // gather-table rows (taps, or k-slices of the 1x1 row)
@@ -1186,6 +1187,8 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
       // (res_bmod: the sample of this `sub` reads the residual rows of sample b % res_bmod - one block-uniform pointer shift)
       const int rb_ = a.res_bmod ? __builtin_amdgcn_readfirstlane(sMb[rfirst]) : 0;
       const float* __restrict__ resp = a.res_bmod ? a.res - (long)(rb_ - rb_ % a.res_bmod) * p.HWout * a.cout : a.res;
+      // (res2, the plain 3x3 kinds: a second residual behind the same shift; the row's residual is res + res2, added as one value)
+      const float* __restrict__ resp2 = (RES2 && a.res2) ? a.res2 + (resp - a.res) : nullptr;
       float* __restrict__ outp = a.out;
       typedef T V4T16 __attribute__((ext_vector_type(4)));
       T* __restrict__ o16p = only16 ? reinterpret_cast<T*>(a.out16_hi) : nullptr;
@@ -1202,6 +1205,14 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
           mm[k] = row < rfirst + rows_per ? sM[row] : -1;
           r4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
           if (resp && mm[k] >= 0) r4[k] = *reinterpret_cast<const float4*>(resp + (long)mm[k] * a.cout + n);
+        }
+        if (RES2 && resp2) {
+#pragma unroll
+          for (int k = 0; k < RB; ++k)
+            if (mm[k] >= 0) {
+              const float4 s4 = *reinterpret_cast<const float4*>(resp2 + (long)mm[k] * a.cout + n);
+              r4[k].x += s4.x; r4[k].y += s4.y; r4[k].z += s4.z; r4[k].w += s4.w;
+            }
         }
 #pragma unroll
         for (int k = 0; k < RB; ++k) {
@@ -1244,6 +1255,10 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
         }
         if (a.res) {
           const long ro = a.res_bmod ? o - (long)(sMb[row] - sMb[row] % a.res_bmod) * p.HWout * a.cout : o;     // (the rows of sample b % res_bmod)
+          if (RES2 && a.res2) {      // (t = res + res2, then v += t; the host admits res2 with cout % 4 == 0 only)
+            const float4 r4 = *reinterpret_cast<const float4*>(a.res + ro), s4 = *reinterpret_cast<const float4*>(a.res2 + ro);
+            v[0] += r4.x + s4.x; v[1] += r4.y + s4.y; v[2] += r4.z + s4.z; v[3] += r4.w + s4.w;
+          } else
           if (vec_ok) { const float4 r4 = *reinterpret_cast<const float4*>(a.res + ro); v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w; }
           else for (int u = 0; u < nv; ++u) v[u] += a.res[ro + u];
         }
@@ -1450,19 +1465,26 @@ static __global__ void __launch_bounds__(256) conv_splitk_reduce_kernel(const st
       const float4 e4 = *reinterpret_cast<const float4*>(a.emb + (long)b * a.emb_bstride + n);
       add.x += e4.x; add.y += e4.y; add.z += e4.z; add.w += e4.w;
     }
+    // (ws_bmod: the partials were written at batch ws_bmod - the rows of sample b % ws_bmod; `plane` is one partial of THAT batch)
+    const long wshift = a.ws_bmod ? (long)(b - b % a.ws_bmod) * HW * C : 0;
+    const long rshift = a.res_bmod ? (long)(b - b % a.res_bmod) * HW * C : 0;
 #pragma unroll 2
     for (int pix = px0 + tp; pix < px1; pix += npl) {
       const long o = ((long)b * HW + pix) * C + n;
       float4 pz[KSMAX];                           // all partial tiles of this quad are loaded before they are added (fixed order)
 #pragma unroll
       for (int z = 0; z < KSMAX; ++z)
-        if (KSMAX == 2 || z < ksplit) pz[z] = *reinterpret_cast<const float4*>(a.ws + z * plane + o);
+        if (KSMAX == 2 || z < ksplit) pz[z] = *reinterpret_cast<const float4*>(a.ws + z * plane + (o - wshift));
       float4 v = pz[0];
 #pragma unroll
       for (int z = 1; z < KSMAX; ++z)
         if (KSMAX == 2 || z < ksplit) { v.x += pz[z].x; v.y += pz[z].y; v.z += pz[z].z; v.w += pz[z].w; }
       v.x += add.x; v.y += add.y; v.z += add.z; v.w += add.w;
-      if (a.res) { const float4 r4 = *reinterpret_cast<const float4*>(a.res + (a.res_bmod ? o - (long)(b - b % a.res_bmod) * HW * C : o)); v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
+      if (a.res) {
+        float4 r4 = *reinterpret_cast<const float4*>(a.res + (o - rshift));
+        if (a.res2) { const float4 s4 = *reinterpret_cast<const float4*>(a.res2 + (o - rshift)); r4.x += s4.x; r4.y += s4.y; r4.z += s4.z; r4.w += s4.w; }     // t = res + res2
+        v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
+      }
       if (GN || a.out) *reinterpret_cast<float4*>(a.out + o) = v;      // (16-bit-only form: no fp32 tensor; the GN form always has one: host)
       if (a.out16_hi) {      // 16-bit side output (operand planes of the consumer), single-product modes; out16_stride: into a wider plane
         const long o16 = a.out16_stride ? ((long)b * HW + pix) * a.out16_stride + n : o;
@@ -1547,6 +1569,58 @@ static __global__ void __launch_bounds__(256) conv_splitk_reduce_kernel(const st
   }
 }
 
+// Launches the reduce pass over `ksplit` partial planes of `plane` floats each (a.ws) for the output of p.a (HWo pixels per sample): the
+// second half of a split-K call (conv_rs_try) or a call of its own (conv_splitk_finish, where the planes may hold fewer samples than the
+// output: a.ws_bmod, and ksplit may be 1). stats: this pass may write a.chan_stats in the caller's slot layout (fine_ok: ... a partition of
+// its own into equal runs of 8 .. 256 pixels). gn_ok: the consumer's GroupNorm may ride in it. Returns whether the statistics were written;
+// sets p.gn_done.
+static bool splitk_reduce_launch(ConvParams& p, const int HWo, const long plane, const int ksplit, bool stats, const bool fine_ok, const bool gn_ok, hipStream_t st) {
+  int qbs = 64;     // small tensors: fewer channel quads per block, so that the partial tiles are read by many CUs
+  while (qbs > 8 && (long)p.a.B * ((HWo + 255) / 256) * ((p.a.cout / 4 + qbs - 1) / qbs) < 256) qbs >>= 1;
+  // the consumer's GroupNorm in the same pass: a block of 8 channel quads x all pixels of a sample owns whole groups
+  const int cpg = (p.a.gn_out16 && p.a.gn_groups > 0) ? p.a.cout / p.a.gn_groups : 0;
+  const bool gn = cpg > 0 && p.a.out && HWo <= 256 && gn_ok && p.a.chan_stats && stats && (p.a.chan_nslab == 0 || p.a.chan_nslab == 1) && p.a.cout % 32 == 0 &&
+                  cpg % 4 == 0 && 32 % cpg == 0;
+  if (gn) qbs = 8;
+  // pixels per block (= per statistics slot). With statistics: the caller's partition (fine_ok above; the default is 256-pixel runs).
+  // Without: free - short runs when the 256-pixel grid would leave most of the chip idle (batch <= 8: a reduce of 32 - 64 blocks walking
+  // 8 pixel iterations x up to 16 partials each took 10 - 13 us, 27 % of a batch-1 denoising step)
+  int slab_px = 256;
+  if (!gn) {
+    if (p.a.chan_stats && stats && fine_ok) slab_px = HWo / p.a.chan_nslab;
+    else if (!p.a.chan_stats || !stats)
+      while (slab_px > 16 && HWo % (slab_px / 2) == 0 && (long)p.a.B * ((HWo + slab_px - 1) / slab_px) * ((p.a.cout / 4 + 7) / 8) < 512) slab_px >>= 1;
+    if (slab_px < 256) {   // a block is (pixel lanes) x (channel quads) = 256 threads: as many pixel lanes as the run has pixels, at most 32
+      qbs = 256 / (slab_px < 32 ? slab_px : 32);
+      if (qbs > 64) qbs = 64;
+    }
+  }
+  dim3 grid(p.a.B, (HWo + slab_px - 1) / slab_px, (p.a.cout / 4 + qbs - 1) / qbs);
+  stedm_conv_args ra = p.a;
+  if (!stats) ra.chan_stats = nullptr;     // another slot layout than this pass fills: the dispatcher's statistics pass writes the caller's
+  if (gn) {
+    if (ksplit == 2) conv_splitk_reduce_kernel<2, true><<<grid, 256, 0, st>>>(ra, HWo, plane, 2, qbs, p.ovf);
+    else conv_splitk_reduce_kernel<16, true><<<grid, 256, 0, st>>>(ra, HWo, plane, ksplit, qbs, p.ovf);
+    p.gn_done = 1;
+  } else if (ksplit == 2) conv_splitk_reduce_kernel<2><<<grid, 256, 0, st>>>(ra, HWo, plane, 2, qbs, p.ovf, slab_px);
+  else conv_splitk_reduce_kernel<16><<<grid, 256, 0, st>>>(ra, HWo, plane, ksplit, qbs, p.ovf, slab_px);
+  return ra.chan_stats != nullptr;      // only what the reduce pass really wrote in the caller's layout counts as done
+}
+
+// stedm_conv_finish (conv_common.hpp): the pass above on its own. The caller (conv_igemm.hip) has checked the arguments.
+static int splitk_finish_impl(ConvParams& p, const int nshare, hipStream_t st) {
+  const stedm_conv_args& a = p.a;
+  const int HW = a.Hin * a.Win, nrun = (HW + 255) / 256;
+  const bool fine_ok = a.chan_nslab > 0 && HW % a.chan_nslab == 0 && HW / a.chan_nslab >= 8 && HW / a.chan_nslab <= 256;
+  const bool stats = a.chan_stats && (a.chan_nslab == 0 || a.chan_nslab == nrun || fine_ok);
+  const long plane = (long)(a.ws_bmod ? a.ws_bmod : a.B) * HW * a.cout;
+  p.gn_done = 0;
+  const bool wrote = splitk_reduce_launch(p, HW, plane, nshare, stats, fine_ok, true, st);
+  STEDM_LAUNCH_CHECK();
+  p.stats_done = wrote ? 1 : 0;
+  return 0;
+}
+
 template <typename T, int WM, int KIND, bool FUSE = false, bool P3 = false>
 static int conv_rs_try(ConvParams& p, const ConvParams& q, hipStream_t st, bool dry = false) {
   constexpr size_t LDS_MAX = 160 * 1024;
@@ -1603,10 +1677,11 @@ static int conv_rs_try(ConvParams& p, const ConvParams& q, hipStream_t st, bool 
   // write them - there is no fp32 tensor for the dispatcher's extra pass; a strided out16 plane belongs to the generic row loop / reduce pass
   if (!q.a.out && q.a.chan_stats && !stats) return -1;
   if (q.a.out16_stride && (KIND == RS_1X1N || P3)) return -1;
-  // a K window / res_bmod: the plain 3x3 kinds alone (conv_setup has checked the arguments; this keeps every other instantiation out)
+  // a K window / res_bmod / res2 / the partials-only form: the plain 3x3 kinds alone (conv_setup has checked the arguments; this keeps every other instantiation out)
   const bool kwin = q.a.src16_cstride || q.a.k_chan0 || q.a.w_cin;
-  if ((kwin || q.a.res_bmod) && !((KIND == RS_3X3 || KIND == RS_3X3M) && !FUSE && !P3)) return -1;
-  if (dry) return 0;
+  if ((kwin || q.a.res_bmod || q.a.res2 || q.partials) && !((KIND == RS_3X3 || KIND == RS_3X3M) && !FUSE && !P3)) return -1;
+  if (q.a.res2 && q.a.cout % 4 != 0) return -1;     // (both row loops read it as float4)
+  if (dry) { p.nshare = q.ksplit >= 2 ? q.ksplit : 1; return 0; }
   p = q;
   p.mg_hw = flat ? 0u : magic(p.HWout); p.mg_w = magic(p.Wout); p.mg_pw = magic(p.PW); p.mg_prpw = magic(p.PRs * p.PW);
   {
@@ -1674,40 +1749,12 @@ static int conv_rs_try(ConvParams& p, const ConvParams& q, hipStream_t st, bool 
   if (kp.ksplit >= 2) kp.a.chan_stats = nullptr;   // the reduce kernel below writes them
   k<<<p.npers ? p.tiles_m * p.npers : p.tiles_m * p.tiles_n * ((SUBK && !s2d) ? 4 : 1) * (kp.ksplit >= 2 ? kp.ksplit : 1), (16 / WM + 2) * 64, lds_launch, st>>>(kp);
   STEDM_LAUNCH_CHECK();
-  if (kp.ksplit >= 2) {
-    int qbs = 64;     // small tensors: fewer channel quads per block, so that the partial tiles are read by many CUs
-    while (qbs > 8 && (long)p.a.B * ((HWo + 255) / 256) * ((p.a.cout / 4 + qbs - 1) / qbs) < 256) qbs >>= 1;
-    // the consumer's GroupNorm in the same pass: a block of 8 channel quads x all pixels of a sample owns whole groups
-    const int cpg = (p.a.gn_out16 && p.a.gn_groups > 0) ? p.a.cout / p.a.gn_groups : 0;
-    const bool gn = cpg > 0 && p.a.out && HWo <= 256 && !(SUBK && !s2d) && p.a.chan_stats && stats && (p.a.chan_nslab == 0 || p.a.chan_nslab == 1) && p.a.cout % 32 == 0 &&
-                    cpg % 4 == 0 && 32 % cpg == 0;
-    if (gn) qbs = 8;
-    // pixels per block (= per statistics slot). With statistics: the caller's partition (fine_ok above; the default is 256-pixel runs).
-    // Without: free - short runs when the 256-pixel grid would leave most of the chip idle (batch <= 8: a reduce of 32 - 64 blocks walking
-    // 8 pixel iterations x up to 16 partials each took 10 - 13 us, 27 % of a batch-1 denoising step)
-    int slab_px = 256;
-    if (!gn) {
-      if (p.a.chan_stats && stats && fine_ok) slab_px = HWo / p.a.chan_nslab;
-      else if (!p.a.chan_stats || !stats)
-        while (slab_px > 16 && HWo % (slab_px / 2) == 0 && (long)p.a.B * ((HWo + slab_px - 1) / slab_px) * ((p.a.cout / 4 + 7) / 8) < 512) slab_px >>= 1;
-      if (slab_px < 256) {   // a block is (pixel lanes) x (channel quads) = 256 threads: as many pixel lanes as the run has pixels, at most 32
-        qbs = 256 / (slab_px < 32 ? slab_px : 32);
-        if (qbs > 64) qbs = 64;
-      }
-    }
-    dim3 grid(p.a.B, (HWo + slab_px - 1) / slab_px, (p.a.cout / 4 + qbs - 1) / qbs);
-    const long plane = (long)p.a.B * HWo * p.a.cout;          // one partial of the whole output
-    stedm_conv_args ra = p.a;
-    if (!stats) ra.chan_stats = nullptr;     // another slot layout than this pass fills: the dispatcher's statistics pass writes the caller's
-    if (gn) {
-      if (kp.ksplit == 2) conv_splitk_reduce_kernel<2, true><<<grid, 256, 0, st>>>(ra, HWo, plane, 2, qbs, p.ovf);
-      else conv_splitk_reduce_kernel<16, true><<<grid, 256, 0, st>>>(ra, HWo, plane, kp.ksplit, qbs, p.ovf);
-      p.gn_done = 1;
-    } else if (kp.ksplit == 2) conv_splitk_reduce_kernel<2><<<grid, 256, 0, st>>>(ra, HWo, plane, 2, qbs, p.ovf, slab_px);
-    else conv_splitk_reduce_kernel<16><<<grid, 256, 0, st>>>(ra, HWo, plane, kp.ksplit, qbs, p.ovf, slab_px);
+  p.nshare = kp.ksplit >= 2 ? kp.ksplit : 1;
+  if (kp.ksplit >= 2 && !p.partials) {
+    stats = splitk_reduce_launch(p, HWo, (long)p.a.B * HWo * p.a.cout, kp.ksplit, stats, fine_ok, !(SUBK && !s2d), st);
     STEDM_LAUNCH_CHECK();
-    stats = ra.chan_stats != nullptr;      // only what the reduce pass really wrote in the caller's layout counts as done
   }
+  if (p.partials) return 0;     // (stedm_conv_partials: the partial planes are the result)
   if (stats) p.stats_done = 1;
   if (p.gn_tile || p.gn_coop) p.gn_done = 1;
   return 0;

@@ -508,12 +508,16 @@ def conv_igemm(src1: Optional[torch.Tensor], w_hi: torch.Tensor, w_lo: Optional[
                skip: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]] = None, query_fused: bool = False, query_rs: bool = False,
                ws: Optional[torch.Tensor] = None, pad_br: bool = False, w_frag16: Optional[torch.Tensor] = None,
                gn_next: Optional[tuple] = None, qkv_planes: Optional[tuple] = None, ln_after: Optional[tuple] = None, coop: Optional[tuple] = None,
-               out16_stride: int = 0, cout: Optional[int] = None, res_bmod: int = 0):
+               out16_stride: int = 0, cout: Optional[int] = None, res_bmod: int = 0, res2: Optional[torch.Tensor] = None, partials: bool = False):
     """src1 [B,Hin,Win,c1] NHWC fp32 (fused path) and/or src16 = (hi, lo) 16-bit NHWC planes [B,Hin,Win,Cin] from
     gn_apply16 (DMA path) -> out [B,Hout,Wout,cout] NHWC fp32 (see stedm_conv_igemm).
     src16[0] may be a channel-narrowed (and batch-narrowed) view plane[b0:b1, :, :, k0:k1] of a contiguous plane: a K window
     (stedm_conv_args.src16_cstride / k_chan0 / w_cin) - the convolution sums channels [k0, k1) only, against the matching chunks of the
-    fragment pack of the full filter. res_bmod: output sample b adds the residual rows of sample b % res_bmod (stedm_conv_args.res_bmod).
+    fragment pack of the full filter. res_bmod: output sample b adds the residual rows of sample b % res_bmod (stedm_conv_args.res_bmod);
+    res2: a second residual, added as res + res2 (stedm_conv_args.res2).
+    partials=True (stedm_conv_partials): the first half of a split-K call - the K-share partials stay in `ws` as [nshare][B][H][W][cout] raw sums,
+    no reduce pass runs, `out` only names the shape; returns nshare (1: the dispatcher did not split). With query_rs: the share count the
+    call would leave, or 0 when it would not run. conv_finish is the second half.
     qkv_planes = (q, k, vt, T, Tp, heads, qscale): the LSA attention's operand planes as the only output of a flat to_qkv GEMM
     (stedm_conv_args.qkv_*; out and out16 None).
     ln_after = (gamma, beta, eps, res): LayerNorm over the output row (cout <= 128) + optional fp32 residual in the epilogue
@@ -524,7 +528,7 @@ def conv_igemm(src1: Optional[torch.Tensor], w_hi: torch.Tensor, w_lo: Optional[
         if not conv3x3_tiles_ok(Ho_, Wo_):
             if query_fused or query_rs:
                 return False
-            if not src16[0].is_contiguous() or res_bmod:
+            if not src16[0].is_contiguous() or res_bmod or res2 is not None or partials:
                 raise _lib.StedmHipError("conv_igemm: a K window / res_bmod belongs to the tiled register-streamed kernel; this output grid takes the im2col form")
             return _conv3x3_generic(src16, w_hi, w_lo, out, prec=prec, mode=mode, scale=scale, shift=shift, act=act, bias=bias, emb=emb,
                                     emb_offset=emb_offset, emb_bstride=emb_bstride, res=res, act_out=act_out, out16=out16, chan_stats=chan_stats,
@@ -639,6 +643,9 @@ def conv_igemm(src1: Optional[torch.Tensor], w_hi: torch.Tensor, w_lo: Optional[
     a.res_bmod = int(res_bmod)
     if res_bmod:
         assert res is not None and res.is_contiguous() and res.dtype == torch.float32 and B % res_bmod == 0 and res.shape[0] >= res_bmod
+    if res2 is not None:
+        assert res is not None and res2.is_contiguous() and res2.dtype == torch.float32 and tuple(res2.shape) == tuple(res.shape)
+        a.res2 = res2.data_ptr()
     a.c1, a.c2, a.src2_bmod = c1, c2, src2_bmod
     a.B, a.Hin, a.Win = B, Hin, Win
     a.mode, a.ks = mode, ks
@@ -665,11 +672,77 @@ def conv_igemm(src1: Optional[torch.Tensor], w_hi: torch.Tensor, w_lo: Optional[
             "the space-to-depth form runs on the register-streamed kernel only"
     else:
         assert w_hi.shape == (a.cout, ks * ks, a.w_cin if kwin else a.c1 + a.c2), (w_hi.shape, a.cout, ks, a.c1, a.c2)
+    if partials:
+        assert ws is not None and not query_fused
+        n = C.c_int32(0)
+        rc = lib().stedm_conv_partials(C.byref(a), C.byref(n), int(bool(query_rs)), _stream())
+        if query_rs:
+            return int(n.value) if rc == 0 else 0
+        check(rc, "stedm_conv_partials")
+        return int(n.value)
     if query_fused:     # capability query only: would this (fused) problem run as one kernel?
         return bool(lib().stedm_conv_fused_skip_ok(C.byref(a)))
     if query_rs:        # capability query only: would the register-streamed kernel run this problem?
         return bool(lib().stedm_conv_rs_ok(C.byref(a)))
     check(lib().stedm_conv_igemm(C.byref(a), _stream()), "stedm_conv_igemm")
+    return out
+
+
+def conv_finish(ws: torch.Tensor, nshare: int, out: Optional[torch.Tensor], *, prec: Precision, ws_bmod: int = 0, bias: Optional[torch.Tensor] = None,
+                emb: Optional[torch.Tensor] = None, emb_offset: int = 0, emb_bstride: int = 0, res: Optional[torch.Tensor] = None,
+                res2: Optional[torch.Tensor] = None, res_bmod: int = 0, chan_stats: Optional[torch.Tensor] = None,
+                out16: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None, out16_stride: int = 0, cout: Optional[int] = None,
+                gn_next: Optional[tuple] = None):
+    """The second half of a split-K call on its own (stedm_conv_finish): out [B,H,W,cout] = sum of the `nshare` partial planes that
+    conv_igemm(partials=True) left in `ws` at batch ws_bmod (0: B; output sample b sums the rows of sample b % ws_bmod) + (bias + emb row of
+    sample b) + residual, with chan_stats, out16 and the riding GroupNorm gn_next as in conv_igemm."""
+    shape = tuple(out.shape) if out is not None else tuple(out16[0].shape[:-1]) + (int(cout),)
+    B, H, W, co = shape
+    a = ConvArgs()
+    _chk(ws, name="ws")
+    a.ws, a.ws_floats, a.ws_bmod = ws.data_ptr(), ws.numel(), int(ws_bmod)
+    a.B, a.Hin, a.Win, a.cout = B, H, W, co
+    a.mode, a.ks, a.npass, a.mm_dtype = CONV_S1, 3, prec.npass, prec.mm_dtype
+    if out is not None:
+        _chk(out, name="out")
+        a.out = out.data_ptr()
+    a.bias = _ptr(bias)
+    if bias is not None:
+        assert bias.numel() == co
+    if emb is not None:
+        assert emb.dtype == torch.float32 and emb.numel() >= emb_offset + (B - 1) * emb_bstride + co
+        a.emb = emb.data_ptr() + 4 * emb_offset
+    a.emb_bstride = int(emb_bstride)
+    for r in (res, res2):
+        if r is not None:
+            _chk(r, name="res")
+            assert tuple(r.shape[1:]) == (H, W, co) and r.shape[0] >= (res_bmod or B)
+    assert res2 is None or res is not None
+    a.res, a.res2, a.res_bmod = _ptr(res), _ptr(res2), int(res_bmod)
+    if chan_stats is not None:
+        _chk(chan_stats, name="chan_stats")
+        assert chan_stats.shape[0] == B and tuple(chan_stats.shape[2:]) == (co, 2)
+        a.chan_stats, a.chan_nslab = chan_stats.data_ptr(), chan_stats.shape[1]
+    if out16 is not None:
+        assert out16[0].dtype == torch.int16 and out16[0].is_contiguous() and tuple(out16[0].shape) == (B, H, W, out16_stride or co)
+        a.out16_hi, a.out16_stride = out16[0].data_ptr(), int(out16_stride)
+    if gn_next is not None:
+        g_w, g_b, g_eps, g_groups, g_act, g_out = gn_next[:6]
+        g_lo = None
+        if isinstance(g_out, (tuple, list)):
+            g_out, g_lo = g_out[0], g_out[1]
+        g_mr = gn_next[6] if len(gn_next) > 6 else None
+        _chk(g_w, name="gn gamma"); _chk(g_b, name="gn beta")
+        assert out is not None and chan_stats is not None and g_out.dtype == torch.int16 and g_out.is_contiguous() and tuple(g_out.shape) == shape
+        a.gn_gamma, a.gn_beta, a.gn_eps, a.gn_groups, a.gn_act, a.gn_out16 = g_w.data_ptr(), g_b.data_ptr(), float(g_eps), int(g_groups), int(g_act), g_out.data_ptr()
+        if g_lo is not None:
+            assert g_lo.dtype == torch.int16 and g_lo.is_contiguous() and tuple(g_lo.shape) == shape
+            a.gn_out16_lo = g_lo.data_ptr()
+        if g_mr is not None:
+            _chk(g_mr, name="gn mean_rstd")
+            assert tuple(g_mr.shape) == (B, int(g_groups), 2)
+            a.gn_mr = g_mr.data_ptr()
+    check(lib().stedm_conv_finish(C.byref(a), int(nshare), _stream()), "stedm_conv_finish")
     return out
 
 

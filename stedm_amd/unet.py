@@ -236,6 +236,13 @@ class UNetModel(nn.Module):
         # forward_cfg: the skip half of a decoder concat convolution once per CFG pair (_shared_skip). None: the rule of
         # _shared_skip_rule decides per site; True / False: every admissible site / none
         self.cfg_shared_skip: Optional[bool] = None
+        # forward_cfg: the style block's in_layers GroupNorm and convolution once per CFG pair (_shared_front / _res_front). None: the rule of
+        # _shared_front_rule decides; True / False: wherever admissible / never
+        self.cfg_shared_front: Optional[bool] = None
+        # _in_conv: where a routed shared-skip launch splits K two ways, its two partials may go to the 2B launch as res / res2 with no
+        # reduce pass. True: wherever that is the case; None / False: never (the reduce pass forms the partial first) - measured on the
+        # headline step the form gains nothing, so no rule admits it
+        self.cfg_skip_partials: Optional[bool] = None
 
     # ------------------------------------------------------------------------------------ engine plumbing
     def convert_to_fp16(self):  # openaimodel.py:745-751 — a no-op in the reference too (openaimodel.py:25-29)
@@ -686,19 +693,28 @@ class UNetModel(nn.Module):
         if plan is None:
             ops.conv_igemm(None, pk.hi, pk.lo, h, src16=a16, **kw)
             return
-        seam, P = plan
+        seam, P, P2 = plan
         Bs = P.shape[0]
+        if P2 is not None:
+            # the shared launch splits K two ways: its two partials stay where the kernel wrote them and the 2B launch adds p0 + p1 as its
+            # residual (stedm_conv_args.res2) - the bits of the reduced P without the reduce launch, its store and its re-read
+            n = ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:Bs, :, :, seam:], None), w_frag=pk.frag, w_frag16=pk.frag16,
+                               ws=P2.view(-1), partials=True)
+            assert n == 2, n
+            ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P2[0], res2=P2[1], res_bmod=Bs, **kw)
+            return
         ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:Bs, :, :, seam:], None), w_frag=pk.frag, w_frag16=pk.frag16, ws=kw["ws"])
         ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P, res_bmod=Bs, **kw)
 
     def _shared_skip(self, rb: ResBlock, pk, a16, c1: int, x2_bmod: int, h, kw):
-        """(seam, P) when the in_layers convolution of `rb` runs as shared launch + 2B launch (_in_conv), else None. Inference, one CFG pair
-        (decoder batch = 2 x2_bmod), single product, both launches admitted by stedm_conv_rs_ok; then cfg_shared_skip or the rule."""
+        """(seam, P, P2) when the in_layers convolution of `rb` runs as shared launch + 2B launch (_in_conv), else None. Inference, one CFG pair
+        (decoder batch = 2 x2_bmod), single product, both launches admitted by stedm_conv_rs_ok; then cfg_shared_skip or the rule.
+        P2 [2, B, H, W, co] (or None): the shared launch splits K two ways and leaves its partials there, no reduce pass (_in_conv)."""
         Bd, H, W, co = h.shape
         if (self.cfg_shared_skip is False or self._tape is not None or self.precision.npass != 1 or x2_bmod <= 0 or Bd != 2 * x2_bmod or
                 a16[0].shape[0] != Bd or not a16[0].is_contiguous()):
             return None
-        key = ("sskip", id(rb), Bd, H, W, self.cfg_shared_skip)
+        key = ("sskip", id(rb), Bd, H, W, self.cfg_shared_skip, self.cfg_skip_partials)
         hit = self._consts.get(key)
         if hit is None:
             norm = rb.in_layers[0]
@@ -717,10 +733,21 @@ class UNetModel(nn.Module):
                 ok = ok and bool(ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P, res_bmod=x2_bmod, query_rs=True, **kw))
                 if ok and (self.cfg_shared_skip or self._shared_skip_rule(Bd, H, W, co, C, seam)):
                     hit = seam
+                    # a two-way K split of the shared launch (asked with the workspace the plain form would use): partials as res / res2
+                    two = self.cfg_skip_partials is True and kw["ws"] is not None and ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:x2_bmod, :, :, seam:], None), w_frag=pk.frag,
+                                                                  w_frag16=pk.frag16, ws=kw["ws"], partials=True, query_rs=True) == 2
+                    if two:
+                        P2 = self._buf(f"sskip.P2.{x2_bmod}x{H}x{W}x{co}", (2, x2_bmod, H, W, co))
+                        two = (ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:x2_bmod, :, :, seam:], None), w_frag=pk.frag,
+                                              w_frag16=pk.frag16, ws=P2.view(-1), partials=True, query_rs=True) == 2 and
+                               bool(ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P2[0], res2=P2[1], res_bmod=x2_bmod,
+                                                   query_rs=True, **kw)))
+                    self._consts[("sskip2",) + key[1:]] = bool(two)
             self._consts[key] = hit
         if not hit:
             return None
-        return hit, self._buf(f"sskip.P.{x2_bmod}x{H}x{W}x{co}", (x2_bmod, H, W, co))
+        P2 = self._buf(f"sskip.P2.{x2_bmod}x{H}x{W}x{co}", (2, x2_bmod, H, W, co)) if self._consts.get(("sskip2",) + key[1:]) else None
+        return hit, self._buf(f"sskip.P.{x2_bmod}x{H}x{W}x{co}", (x2_bmod, H, W, co)), P2
 
     @staticmethod
     def _shared_skip_rule(Bd: int, H: int, W: int, co: int, C: int, seam: int) -> bool:
@@ -738,6 +765,94 @@ class UNetModel(nn.Module):
         if not fills(Bd):
             return False
         return (C - seam) // 32 >= (14 if fills(Bd // 2) else 32)
+
+    def _replicate(self, h, nrep: int):
+        """the shared tensor h [B,...] and its channel statistics at batch nrep x B = [cond | uncond] (the style-conditioned remainder's input)"""
+        h2 = self._buf("mid.rep", (nrep * h.shape[0],) + tuple(h.shape[1:]))
+        cs1 = self._cs.get(h.data_ptr())
+        cs2 = self._cs_new(h2, nslab=cs1.shape[1]) if cs1 is not None else None
+        # (one broadcast copy per tensor instead of nrep device-to-device memcpys: four launches of ~5 us were 0.4 % of the bench step)
+        h2.view((nrep,) + tuple(h.shape)).copy_(h.unsqueeze(0).expand((nrep,) + tuple(h.shape)))
+        if cs2 is not None:      # the replicas share the statistics of the shared-encoder tensor
+            cs2.view((nrep,) + tuple(cs1.shape)).copy_(cs1.unsqueeze(0).expand((nrep,) + tuple(cs1.shape)))
+        return h2
+
+    # ---- the CFG seam: the style block's shared front --------------------------------------------------------------
+    def _front_ws(self, nel: int) -> torch.Tensor:
+        """workspace of the style block's partials (its own buffer: conv_ws is rewritten by the launches between the two halves)"""
+        return self._buf("sfront.ws", ((16 if nel <= (1 << 20) else (4 if nel <= (1 << 22) else (2 if nel <= (1 << 23) else 1))) * nel,))
+
+    def _front_kw(self, tag: str, rb: ResBlock, x1, next_norm):
+        """operands of _res_front's launches for the shared input x1 [B,H,W,C] (buffers are the model's own, made on first use)"""
+        prec = self.precision
+        B, H, W, _ = x1.shape
+        Bd, co = 2 * B, rb.out_channels
+        pk, pk2 = self._packed[id(rb.in_layers[2])], self._packed[id(rb.out_layers[3])]
+        h = self._buf(f"h.{Bd}x{H}x{W}x{co}", (Bd, H, W, co))
+        out = self._buf(tag + ".out", (Bd, H, W, co))
+        gn2 = rb.out_layers[0]
+        h16 = self._planes(Bd, H, W, co, "g16")
+        gnn = npl = coop2 = None
+        if next_norm is not None and not os.environ.get("STEDM_NO_NEXT_GN"):
+            nn_, nact = next_norm
+            npl = self._planes(Bd, H, W, co)
+            gnn = (nn_.weight, nn_.bias, nn_.eps, nn_.num_groups, nact, npl[0], None, False)
+            coop2 = self._coop_for(tag + ".c2", Bd, H, W, co, prec)
+        part = dict(prec=prec, w_frag=pk.frag, w_frag16=pk.frag16, ws=self._front_ws(B * H * W * co), partials=True)
+        fin = dict(prec=prec, ws_bmod=B, bias=pk.bias, gn_next=(gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1, h16[0], None, True))
+        tail = dict(prec=prec, src16=h16, bias=pk2.bias, res=x1, res_bmod=B, w_frag=pk2.frag, ws=self._splitk_ws_res(Bd * H * W * co), w_frag16=pk2.frag16,
+                    gn_next=gnn, coop=coop2)
+        return pk, pk2, h, out, npl, part, fin, tail
+
+    def _shared_front(self, tag: str, rb: ResBlock, x1shape, next_norm) -> bool:
+        """Does the style block `rb` run as _res_front over the shared tensor of shape x1shape [B,H,W,C]? Inference, single product, identity
+        residual, both convolution launches admitted by a dry query; then cfg_shared_front or the rule. The answer is filed in _consts
+        under ("sfront", ...): the share count of the partials-only launch, 0 when the block is not routed."""
+        B, H, W, C = x1shape
+        if (self.cfg_shared_front is False or self._tape is not None or self.precision.npass != 1 or not isinstance(rb.skip_connection, nn.Identity) or
+                rb.out_channels != C):
+            return False
+        key = ("sfront", id(rb), 2 * B, H, W, self.cfg_shared_front)
+        hit = self._consts.get(key)
+        if hit is None:
+            hit = 0
+            pk, pk2, h, out, npl, part, fin, tail = self._front_kw(tag, rb, self._buf("mid.a.0.out", x1shape), next_norm)      # (the shared tensor's own buffer)
+            if (pk.frag is not None or pk.frag16 is not None) and C % 4 == 0 and (self.cfg_shared_front or self._shared_front_rule(2 * B, H, W, C)):
+                a16 = self._planes(B, H, W, C)
+                n = ops.conv_igemm(None, pk.hi, pk.lo, self._buf(f"h.{B}x{H}x{W}x{C}", (B, H, W, C)), src16=a16, query_rs=True, **part)
+                if n and ops.conv_igemm(None, pk2.hi, pk2.lo, out, chan_stats=self._cs_new(out), query_rs=True, **tail):
+                    hit = int(n)
+            self._consts[key] = hit
+        return bool(hit)
+
+    @staticmethod
+    def _shared_front_rule(Bd: int, H: int, W: int, co: int) -> bool:
+        """Does the shared front beat the 2B block? The saving is half of the in_layers convolution's MFMA work, its GroupNorm pass and the two
+        broadcast copies; the cost is the finish pass at 2B. From the per-site measurement (tools/shared_front_site.py; DESIGN.md section
+        10.14), 1024 channels: decoder batch 128 / 96 / 64 at 8 x 8 win 70 / 51 / 35 us of 480 / 386 / 299, batch 128 at 16 x 16 wins 214 of
+        1571. The smallest grid measured is the decoder batch's own launch on half the chip (128 tiles of 256 rows x 128 channels on 256
+        CUs); smaller ones were not measured and stay on the launches they have."""
+        cus = ops.device_cus()
+        tiles_m = -(-Bd * H * W // 256) if H * W >= 256 else -(-Bd // (256 // (H * W)))
+        return tiles_m * -(-co // 128) * 2 >= cus
+
+    def _res_front(self, tag: str, rb: ResBlock, x1, style_all, next_norm):
+        """The ResBlockStyle at the CFG seam over the SHARED tensor x1 [B,H,W,C] (output of middle_block[0]) -> [2B,H,W,C] = [cond | uncond].
+        The two style vectors first enter as the embedding row added to in_layers' convolution, so that block's GroupNorm, its 3x3
+        convolution and the identity residual carry the same bits in samples b and b + B: the GroupNorm planes come from
+        middle_block[0]'s tail convolution at batch B, the convolution runs once at batch B and leaves its K-share partials
+        (stedm_conv_partials), the finish pass at 2B adds bias and the style row of each sample and writes h's statistics and out_layers'
+        GroupNorm + SiLU planes (stedm_conv_finish, ws_bmod = B), and the tail convolution at 2B reads x1 as its residual modulo B."""
+        B, H, W, C = x1.shape
+        pk, pk2, h, out, npl, part, fin, tail = self._front_kw(tag, rb, x1, next_norm)
+        a16 = self._norm16(rb.in_layers[0], 1, x1)
+        n = ops.conv_igemm(None, pk.hi, pk.lo, self._buf(f"h.{B}x{H}x{W}x{C}", (B, H, W, C)), src16=a16, **part)
+        self._last_h = h
+        ops.conv_finish(part["ws"], n, h, emb=style_all, emb_bstride=style_all.shape[1], chan_stats=self._cs_new(h), **fin)
+        ops.conv_igemm(None, pk2.hi, pk2.lo, out, chan_stats=self._cs_new(out), **tail)
+        if npl is not None:
+            self._pre16[out.data_ptr()] = (id(next_norm[0]), next_norm[1], npl)
+        return out
 
     def _attn(self, tag: str, ab: AttentionBlock, x):
         """AttentionBlock._forward openaimodel.py:340-346 on NHWC (tokens = H*W)."""
@@ -1013,22 +1128,21 @@ class UNetModel(nn.Module):
             h = self._run_block(f"in{i}", blk, h, None, emb_e, emb_stride, None, next_layer=nl)
             hs.append(h)
         # middle block: [0] shared, then replicate the batch for the style-conditioned remainder
-        h = self._run_block("mid.a", mid[:1], h, None, emb_e, emb_stride, None, next_layer=mid[1] if nrep == 1 and len(mid) > 1 else None)
-        if nrep > 1:
-            h2 = self._buf("mid.rep", (Bd,) + tuple(h.shape[1:]))
-            cs1 = self._cs.get(h.data_ptr())
-            cs2 = self._cs_new(h2, nslab=cs1.shape[1]) if cs1 is not None else None
-            # (one broadcast copy per tensor instead of nrep device-to-device memcpys: four launches of ~5 us were 0.4 % of the bench step)
-            h2.view((nrep,) + tuple(h.shape)).copy_(h.unsqueeze(0).expand((nrep,) + tuple(h.shape)))
-            if cs2 is not None:      # the replicas share the statistics of the shared-encoder tensor
-                cs2.view((nrep,) + tuple(cs1.shape)).copy_(cs1.unsqueeze(0).expand((nrep,) + tuple(cs1.shape)))
-            h = h2
+        # (under one CFG pair the style block's front may stay at batch B: _shared_front / _res_front)
+        front = (nrep == 2 and len(mid) > 2 and isinstance(mid[1], ResBlockStyle) and
+                 self._shared_front("mid.b.1", mid[1].block, tuple(h.shape), self._first_norm(mid[2])))
+        h = self._run_block("mid.a", mid[:1], h, None, emb_e, emb_stride, None, next_layer=mid[1] if (nrep == 1 or front) and len(mid) > 1 else None)
+        if front:
+            h = self._res_front("mid.b.1", mid[1].block, h, style_all, self._first_norm(mid[2]))
+        elif nrep > 1:
+            h = self._replicate(h, nrep)
+
         def first_takes_cat(blk):      # a decoder block whose first layer is a ResBlock with a skip_connection convolution (always, in this net)
             l0 = list(blk)[0]
             return isinstance(l0, ResBlock) and not isinstance(l0.skip_connection, nn.Identity)
 
         ob = list(self.output_blocks)
-        h = self._run_block("mid.b", mid[1:], h, None, emb_d, emb_stride, style_all, li0=1,
+        h = self._run_block("mid.b", mid[2:] if front else mid[1:], h, None, emb_d, emb_stride, style_all, li0=2 if front else 1,
                             next_skip_c=hs[-1].shape[-1] if ob and first_takes_cat(ob[0]) else None)
         bmod = B if nrep > 1 else 0
         for i, blk in enumerate(ob):
