@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 24
+#define STEDM_ABI_VERSION 25
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -816,6 +816,22 @@ int stedm_conv1x1_nchw(const float* x, const float* w, const float* bias, float*
  * 16-bit operand planes [rows][ld_out] (hi, lo = v - hi or NULL), columns n..ld_out-1 zero. */
 int stedm_softmax_rows16(const float* x, long ld_in, float scale, void* out_hi, void* out_lo, long rows, int n, long ld_out, int mm_dtype,
                          void* stream);
+/* ---- KL first stage (ABI 25): AutoencoderKL, ldm/models/autoencoder.py:285-342 ------------------------------------------------
+ * Its Encoder / Decoder and glue convs run on the kernels above; this is the posterior's sampling step:
+ * DiagonalGaussianDistribution.sample / .mode (ldm/modules/distributions/distributions.py:24-37, 61-62) fused with the scale of
+ * get_first_stage_encoding (ddpm.py:552). moments NCHW [B][2C][HW] fp32: channels [0, C) of a sample are the mean, [C, 2C) the
+ * log-variance. mode 0:
+ *   z [B][C][HW] = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise)
+ * with the accurate expf and every product and sum rounded once. noise [B][C][HW] N(0, 1), or NULL: drawn in the kernel as row
+ * first_id + b of stedm_philox_normal with (seed, stream STEDM_STREAM_POSTERIOR) - the same bits as that entry writes, so a sample's
+ * latent depends on (seed, its global id) alone, whatever the shard. mode 1: z = scale * mean (one rounding); noise, first_id and seed
+ * are not read and nothing is drawn. Any HW (a row tail that is no multiple of 4 takes scalar loads and stores). No allocation, no
+ * atomics, no host read: capturable in a hipGraph.
+ * Noise streams of stedm_philox_normal in use: 0 (x_T), 1 + iteration (DDIM step noise), 0x8000 + index (mask blend), 0x10000 + t
+ * (ancestral step), STEDM_STREAM_POSTERIOR (this entry). 0x20000 + iteration keys the noise-dropout bits (another counter word). */
+#define STEDM_STREAM_POSTERIOR 0x40000u
+int stedm_gauss_sample(const float* moments, const float* noise, float* z, int B, int C, long HW, float scale, int mode, long first_id,
+                       unsigned long long seed, void* stream);
 
 /* ---- image epilogue of predict_step (integer work, bit-exact) -------------------------------------------------------
  * modules/ldm_diffusion.py:93-95: ((clip(x, -1, 1).permute(0,2,3,1) + 1) * 127.5).astype(uint8): x NCHW fp32 -> out NHWC uint8. */

@@ -10,9 +10,10 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
+STREAM_POSTERIOR = 0x40000          # STEDM_STREAM_POSTERIOR: the stedm_philox_normal stream of the KL posterior's draw (stedm_gauss_sample)
 
 
 class StedmHipError(RuntimeError):
@@ -171,6 +172,7 @@ SIGNATURES = {
     "stedm_ddim_quantize_x0": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_long, _P, _P, _P]),
     "stedm_conv1x1_nchw": (_I, [_P, _P, _P, _P, _I, _I, _I, C.c_long, _P]),
     "stedm_softmax_rows16": (_I, [_P, C.c_long, _F, _P, _P, C.c_long, _I, C.c_long, _I, _P]),
+    "stedm_gauss_sample": (_I, [_P, _P, _P, _I, _I, C.c_long, _F, _I, C.c_long, C.c_ulonglong, _P]),
     "stedm_image_to_uint8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "stedm_seg_merge": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "stedm_argmax_u8": (_I, [_P, _P, C.c_long, _I, _P]),

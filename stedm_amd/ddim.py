@@ -34,7 +34,9 @@ def first_stage_codebook(model, C, option):
     device work."""
     emb = getattr(getattr(getattr(model, "first_stage_model", None), "quantize", None), "embedding", None)
     if emb is None:
-        raise NotImplementedError(f"{option} needs a VQ first stage (first_stage_model.quantize.embedding)")
+        fs = getattr(model, "first_stage_model", None)
+        raise NotImplementedError(f"{option} needs a VQ first stage (first_stage_model.quantize.embedding); this model's first stage is "
+                                  f"{'absent' if fs is None else type(fs).__name__}, which has no codebook")
     w = emb.weight
     if w.dim() != 2 or int(w.shape[1]) != int(C):
         raise ValueError(f"{option}: codebook {tuple(w.shape)} has width {w.shape[-1]}, the latents have {C} channels")

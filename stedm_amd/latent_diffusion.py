@@ -54,19 +54,20 @@ def instantiate_from_config(config):
 
 
 def instantiate_first_stage(config):
-    """ddpm.py:530-535 (`instantiate_first_stage`): the reference target `ldm.models.autoencoder.VQModelInterface` maps to the HIP
-    VQ-f4 stage when this package provides it; any other target must be importable as it stands."""
+    """ddpm.py:530-535 (`instantiate_first_stage`): the reference targets `ldm.models.autoencoder.VQModelInterface`, `.AutoencoderKL` and
+    `.IdentityFirstStage` map to the HIP stages of stedm_amd.vq; any other target must be importable as it stands."""
     cfg = dict(config)
     target = cfg.get("target")
     if target is None:
         raise KeyError("Expected key `target` to instantiate.")
-    if target in ("ldm.models.autoencoder.VQModelInterface", "stedm_amd.vq.VQModelInterface"):
+    module, _, name = target.rpartition(".")
+    if module in ("ldm.models.autoencoder", "stedm_amd.vq") and name in ("VQModelInterface", "AutoencoderKL", "IdentityFirstStage"):
         try:
-            from .vq import VQModelInterface
+            from . import vq
         except ImportError as e:
-            raise NotImplementedError(f"first_stage_config target {target!r}: the HIP VQ-f4 first stage is not available ({e}); pass a module "
+            raise NotImplementedError(f"first_stage_config target {target!r}: the HIP first stage is not available ({e}); pass a module "
                                       "as first_stage_config or leave it None for sampling up to the latents") from e
-        return VQModelInterface(**cfg.get("params", dict())).eval()
+        return getattr(vq, name)(**cfg.get("params", dict())).eval()
     return instantiate_from_config(cfg).eval()
 
 
@@ -365,10 +366,13 @@ class LatentDiffusion(nn.Module):
         return a
 
     # ------------------------------------------------------------------------------------------ the reference's training seam
-    def get_input(self, batch, k, return_first_stage_outputs=False, force_c_encode=False, cond_key=None, return_original_cond=False, bs=None):
+    def get_input(self, batch, k, return_first_stage_outputs=False, force_c_encode=False, cond_key=None, return_original_cond=False, bs=None,
+                  posterior_seed=None, sample_id0=0):
         """ddpm.py:656-706 for the paths the STEDM configs take: batch tensors NHWC (DDPM.get_input, ddpm.py:332-338) -> latents of
         the first stage (encode_first_stage, per-sample loop of ddpm.py:866 batched) and the conditioning: the raw cond input while
-        `cond_stage_trainable` (the caller encodes it: forward / S_ZSS_DM.get_input), its encoding otherwise. -> [z, c]."""
+        `cond_stage_trainable` (the caller encodes it: forward / S_ZSS_DM.get_input), its encoding otherwise. -> [z, c].
+        posterior_seed / sample_id0: a KL first stage samples its posterior for sample b from (posterior_seed, global sample id
+        sample_id0 + b) (get_first_stage_encoding); None draws one seed per call from torch's CPU generator. Ignored by a VQ stage."""
         with torch.no_grad():
             x = batch[k]
             if x.dim() == 3:
@@ -376,7 +380,7 @@ class LatentDiffusion(nn.Module):
             if bs is not None:
                 x = x[:bs]
             x = x.permute(0, 3, 1, 2).float().contiguous().to(self.device)
-            z = self.get_first_stage_encoding(self.encode_first_stage(x)).detach()
+            z = self.get_first_stage_encoding(self.encode_first_stage(x), seed=posterior_seed, sample_id0=sample_id0).detach()
             c = xc = None
             if self.model.conditioning_key is not None:
                 cond_key = self.cond_stage_key if cond_key is None else cond_key
@@ -408,6 +412,11 @@ class LatentDiffusion(nn.Module):
         params = self._split_params(split)
         if params is None:
             return self.first_stage_model.encode(x)
+        from .vq import AutoencoderKL
+        if isinstance(self.first_stage_model, AutoencoderKL):
+            # ddpm.py:849-856 stacks the crops' `encode` outputs, which are distributions there: the reference's tiled encode cannot run on a KL stage
+            raise NotImplementedError("encode_first_stage: the patch-distributed (tiled) encode is not available for an AutoencoderKL first stage "
+                                      "(its encode returns a distribution per crop, which the reference's fold cannot blend); tiled decode works")
         if split is None:
             self.split_input_params['original_image_size'] = x.shape[-2:]       # ddpm.py:835
         return self._tiled_first_stage(x, params, True, tile_batch)
@@ -472,8 +481,14 @@ class LatentDiffusion(nn.Module):
             stack[l0:l0 + nl].copy_(o.view(nl, B, o.shape[1], th, tw))
         return stack
 
-    def get_first_stage_encoding(self, encoder_posterior):
-        """ddpm.py:537-544: the VQ interface returns the latent tensor itself."""
+    def get_first_stage_encoding(self, encoder_posterior, noise=None, seed=None, sample_id0=0):
+        """ddpm.py:545-552. A tensor (the VQ interface returns the latent itself): scale_factor * it. The KL stage's
+        DiagonalGaussianDistribution: scale_factor * its sample, the scale folded into the sampling kernel; noise / seed / sample_id0 as
+        DiagonalGaussianDistribution.sample takes them (given noise, or the per-sample stream of (seed, sample_id0 + b), the seed drawn from
+        torch's CPU generator when neither is given)."""
+        from .distributions import DiagonalGaussianDistribution
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            return encoder_posterior.sample(noise=noise, seed=seed, sample_id0=sample_id0, scale=self.scale_factor)
         if not isinstance(encoder_posterior, torch.Tensor):
             raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
         return self.scale_factor * encoder_posterior
@@ -807,7 +822,7 @@ class LatentDiffusion(nn.Module):
         instead of the fp32 one; on the tiled path it comes out of the blend kernel's registers, no fp32 image is written."""
         if self.first_stage_model is None:
             raise NotImplementedError("decode_first_stage: this LatentDiffusion was built without a first stage; pass first_stage_config "
-                                      "(built as stedm_amd.vq.VQModelInterface) or a first_stage module")
+                                      "(built as stedm_amd.vq.VQModelInterface / AutoencoderKL) or a first_stage module")
         params = self._split_params(split)
         if params is not None:
             return self._tiled_first_stage(1. / self.scale_factor * z, params, False, tile_batch, out_u8=out_u8)
@@ -867,7 +882,8 @@ class S_ZSS_DM(LatentDiffusion):
         predict_only=True: z is a zero placeholder of the latent shape and the VQ encode is skipped — predict_step uses len(z) alone
         (ldm_diffusion.py:79-90), so the reference's two VQ encodes there are wasted work. Default (None): encode when a first stage
         exists (the reference's literal behaviour); without one, the placeholder in eval mode and an error in training mode (the
-        latents are the training target: never silently zeros)."""
+        latents are the training target: never silently zeros). posterior_seed / sample_id0 (keywords of LatentDiffusion.get_input: the
+        KL first stage's per-sample posterior draw) pass through with the other keywords."""
         skip_encode = predict_only is True or (predict_only is None and self.first_stage_model is None and not self.training)
         dev = self.device
         if skip_encode or self.first_stage_model is None:

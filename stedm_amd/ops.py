@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import BF16, CONV_DOWN, CONV_S1, CONV_S2D, CONV_UP, CONV_UP_SUBPIXEL, F16, ConvArgs, check, lib
+from ._lib import BF16, CONV_DOWN, CONV_S1, CONV_S2D, CONV_UP, CONV_UP_SUBPIXEL, F16, STREAM_POSTERIOR, ConvArgs, check, lib
 
 
 @dataclass(frozen=True)
@@ -1758,6 +1758,30 @@ def conv1x1_nchw(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor])
     out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
     check(lib().stedm_conv1x1_nchw(x.data_ptr(), w2.data_ptr(), _ptr(None if bias is None else bias.detach().float().contiguous()), out.data_ptr(),
                                    B, cin, cout, H * W, _stream()), "stedm_conv1x1_nchw")
+    return out
+
+
+def gauss_sample(moments: torch.Tensor, noise: Optional[torch.Tensor] = None, *, scale: float = 1.0, mode: bool = False, seed: Optional[int] = None,
+                 first_id: int = 0) -> torch.Tensor:
+    """moments [B,2C,H,W] fp32 (mean | log-variance) -> z [B,C,H,W] = scale * (mean + exp(0.5 clamp(logvar, -30, 20)) noise): the KL
+    posterior's sample (distributions.py:24-37) with get_first_stage_encoding's scale (ddpm.py:552) folded in. noise [B,C,H,W], or None:
+    drawn in the kernel as row first_id + b of philox_normal(seed, stream STREAM_POSTERIOR), the same bits. mode=True: z = scale * mean,
+    nothing read or drawn. See stedm_gauss_sample."""
+    _chk(moments, name="moments")
+    if moments.dim() != 4 or moments.shape[1] % 2:
+        raise ValueError(f"moments must be [B, 2C, H, W], got {tuple(moments.shape)}")
+    B, C2, H, W = moments.shape
+    C = C2 // 2
+    if not mode:
+        if noise is not None:
+            _chk(noise, name="noise")
+            if tuple(noise.shape) != (B, C, H, W):
+                raise ValueError(f"noise {tuple(noise.shape)} does not match the sample's shape {(B, C, H, W)}")
+        elif seed is None:
+            raise ValueError("gauss_sample: give noise, a seed for the in-kernel draw, or mode=True")
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=moments.device)
+    check(lib().stedm_gauss_sample(moments.data_ptr(), None if mode else _ptr(noise), out.data_ptr(), B, C, H * W, float(scale), 1 if mode else 0,
+                                   int(first_id), int(seed or 0) & 0xFFFFFFFFFFFFFFFF, _stream()), "stedm_gauss_sample")
     return out
 
 

@@ -10,7 +10,10 @@ same state-dict names (`encoder.down.0.block.0.norm1.weight`, `decoder.up.2.upsa
 
 The architecture is written down once: `first_stage_layout(**ddconfig)` lists, for the encoder and for the decoder, the rows that run
 (ResNet block, attention block, downsample, upsample) in execution order with their state-dict prefixes and channel counts.
-`_containers` builds the parameter containers from it, `_prepare` packs the weights row by row and `_walk` runs the rows.
+`_containers` builds the parameter containers from it, `_prepare` packs the weights row by row and `_walk` runs the rows. That engine
+(`FirstStageEngine`) is shared by the two frozen stages built on it: `VQModelInterface` and `AutoencoderKL` (autoencoder.py:285-342, the
+KL stage: the encoder emits 2 * z_channels moments and `encode` returns their `DiagonalGaussianDistribution`). `IdentityFirstStage`
+(autoencoder.py:426-443) passes its input through.
 
 torch.nn modules are parameter containers; the arithmetic runs in the kernels the U-Net uses: GroupNorm(+SiLU) from producer-side
 channel statistics into 16-bit operand planes (stedm_gn_apply16c), 3x3 / 1x1 / fused-shortcut / sub-pixel-upsample /
@@ -31,7 +34,7 @@ from .ops import Precision
 
 class Row(NamedTuple):
     """One step of the encoder or of the decoder."""
-    kind: str        # "res" | "attn" | "down" | "up": VQModelInterface._res / _attn / _down / _up runs it
+    kind: str        # "res" | "attn" | "down" | "up": FirstStageEngine._res / _attn / _down / _up runs it
     prefix: str      # where its parameters live in the state dict, under `encoder.` / `decoder.` (`down.1.block.0`, `mid.attn_1`, ...)
     cin: int
     cout: int
@@ -168,46 +171,35 @@ class _Packed:
         self.hi, self.lo, self.bias, self.frag, self.extra, self.frag16, self.extra_src = hi, lo, bias, frag, extra, frag16, extra_src
 
 
-class VQModelInterface(nn.Module):
-    """autoencoder.py:264-282 over VQModel (:14-110). Extra (non-reference) argument: `precision` (ops.Precision name; the parity mode
-    is the one asserted against the oracle, bf16 / f16 are the single-product fast modes)."""
+class FirstStageEngine(nn.Module):
+    """What the frozen first stages share (VQModelInterface, AutoencoderKL): the reference's Encoder / Decoder (model.py:368-568) built from
+    `first_stage_layout`, their weight packing (`_prepare`) and the walk over the layout's rows on the HIP kernels (`_encoder`, `_decoder`).
+    A subclass calls `_build_halves` first (it registers `encoder` and `decoder`, so they lead the state dict as in the reference), then
+    registers its own modules — `quant_conv` and `post_quant_conv` among them — and ends its constructor with `_freeze`."""
 
-    def __init__(self, embed_dim, ddconfig=None, lossconfig=None, n_embed=None, ckpt_path=None, ignore_keys=(), image_key="image",
-                 colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None, lr_g_factor=1.0, remap=None,
-                 sane_index_shape=False, use_ema=False, precision: str = "parity"):
-        super().__init__()
-        if ddconfig is None or n_embed is None:
-            raise TypeError("VQModelInterface needs ddconfig and n_embed (conf/diffusion/first_stage_config/vq-f4.yaml)")
-        if use_ema or colorize_nlabels is not None or batch_resize_range is not None:
-            raise NotImplementedError("use_ema / colorize_nlabels / batch_resize_range: training-side options of VQModel, unused by the frozen stage")
-        self.embed_dim, self.n_embed, self.image_key = embed_dim, n_embed, image_key
-        dd = dict(ddconfig)
-        self.layout = first_stage_layout(**dd)
+    def _build_halves(self, ddconfig, precision):
+        self.layout = first_stage_layout(**dict(ddconfig))
         self._steps = {}                              # per half: [(buffer tag, row, leaves)] in execution order
         for name in ("encoder", "decoder"):
             net, self._steps[name] = _containers(name, getattr(self.layout, name), self.layout.levels)
             setattr(self, name, net)
         self.encoder.num_resolutions = self.layout.levels      # latent_diffusion.latent_mask checks an image mask's factor against it
-        self.loss = nn.Identity()                     # lossconfig: torch.nn.Identity (vq-f4.yaml:22-23)
-        self.quantize = VectorQuantizer(n_embed, embed_dim, beta=0.25, remap=remap, sane_index_shape=sane_index_shape)
-        self.quant_conv = nn.Conv2d(dd["z_channels"], embed_dim, 1)
-        self.post_quant_conv = nn.Conv2d(embed_dim, dd["z_channels"], 1)
-        if monitor is not None:
-            self.monitor = monitor
         self.precision = Precision.parse(precision) if isinstance(precision, str) else precision
         self.batch_invariant = False                  # True: encode / decode give a sample the same bits in every batch (see _ws)
         self._packed: Dict = {}
         self._pack_key = None
         self._bufs: Dict[Tuple, torch.Tensor] = {}
         self._cs: Dict[int, torch.Tensor] = {}
+
+    def _freeze(self, ckpt_path, ignore_keys):
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
         for p in self.parameters():                   # instantiate_first_stage freezes it (ddpm.py:530-535)
             p.requires_grad = False
 
     def init_from_ckpt(self, path, ignore_keys=()):
-        """autoencoder.py:78-90."""
-        # a third-party checkpoint (vq-f4.ckpt): tensors only, never a full unpickle — if the safe loader refuses the file, say so and stop
+        """autoencoder.py:78-90, 313-322."""
+        # a third-party checkpoint (vq-f4.ckpt, kl-f8's model.ckpt): tensors only, never a full unpickle — if the safe loader refuses the file, say so and stop
         try:
             ck = torch.load(path, map_location="cpu", weights_only=True)
         except Exception as e:
@@ -275,7 +267,7 @@ class VQModelInterface(nn.Module):
         params = list(self.parameters())
         dev = params[0].device
         if dev.type != "cuda":
-            raise StedmHipError("VQModelInterface needs its parameters on the GPU; there is no CPU fallback")
+            raise StedmHipError(f"{type(self).__name__} needs its parameters on the GPU; there is no CPU fallback")
         key = (self.precision, dev, tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
         if key == self._pack_key:
             return
@@ -511,6 +503,30 @@ class VQModelInterface(nn.Module):
         self._conv(self._packed[id(ci)], self._norm16(None, 0, zp, kind="z16"), h)
         return self._walk("decoder", h)
 
+
+class VQModelInterface(FirstStageEngine):
+    """autoencoder.py:264-282 over VQModel (:14-110). Extra (non-reference) argument: `precision` (ops.Precision name; the parity mode
+    is the one asserted against the oracle, bf16 / f16 are the single-product fast modes)."""
+
+    def __init__(self, embed_dim, ddconfig=None, lossconfig=None, n_embed=None, ckpt_path=None, ignore_keys=(), image_key="image",
+                 colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None, lr_g_factor=1.0, remap=None,
+                 sane_index_shape=False, use_ema=False, precision: str = "parity"):
+        super().__init__()
+        if ddconfig is None or n_embed is None:
+            raise TypeError("VQModelInterface needs ddconfig and n_embed (conf/diffusion/first_stage_config/vq-f4.yaml)")
+        if use_ema or colorize_nlabels is not None or batch_resize_range is not None:
+            raise NotImplementedError("use_ema / colorize_nlabels / batch_resize_range: training-side options of VQModel, unused by the frozen stage")
+        self.embed_dim, self.n_embed, self.image_key = embed_dim, n_embed, image_key
+        dd = dict(ddconfig)
+        self._build_halves(dd, precision)
+        self.loss = nn.Identity()                     # lossconfig: torch.nn.Identity (vq-f4.yaml:22-23)
+        self.quantize = VectorQuantizer(n_embed, embed_dim, beta=0.25, remap=remap, sane_index_shape=sane_index_shape)
+        self.quant_conv = nn.Conv2d(dd["z_channels"], embed_dim, 1)
+        self.post_quant_conv = nn.Conv2d(embed_dim, dd["z_channels"], 1)
+        if monitor is not None:
+            self.monitor = monitor
+        self._freeze(ckpt_path, ignore_keys)
+
     # ------------------------------------------------------------------------------------------------ the reference's surface
     @torch.no_grad()
     def encode(self, x):
@@ -541,3 +557,79 @@ class VQModelInterface(nn.Module):
 
     def forward(self, input, return_pred_indices=False):
         raise NotImplementedError("VQModel.forward (autoencoder training) is outside the frozen first stage")
+
+
+CONV_OUT_MAX = 8      # output channels stedm_conv_out writes (the encoder's conv_out of a KL stage has 2 * z_channels)
+
+
+class AutoencoderKL(FirstStageEngine):
+    """autoencoder.py:285-342: the KL first stage (kl-f4, kl-f8, ...), frozen. The encoder's conv_out writes 2 * z_channels moments,
+    `quant_conv` maps them to 2 * embed_dim and `encode` returns their DiagonalGaussianDistribution; `decode` is `post_quant_conv` and the
+    decoder. Encoder, decoder and the glue convolutions run on the engine VQModelInterface uses; the posterior's sample is
+    stedm_gauss_sample (stedm_amd/distributions.py). Extra (non-reference) argument: `precision`, as on VQModelInterface."""
+
+    def __init__(self, ddconfig, lossconfig, embed_dim, ckpt_path=None, ignore_keys=(), image_key="image", colorize_nlabels=None, monitor=None,
+                 precision: str = "parity"):
+        super().__init__()
+        dd = dict(ddconfig)
+        if not dd.get("double_z", True):
+            raise ValueError("AutoencoderKL needs ddconfig['double_z'] true: the encoder emits the mean and the log-variance "
+                             "(the reference asserts it, autoencoder.py:301)")
+        if 2 * dd["z_channels"] > CONV_OUT_MAX or 2 * embed_dim > 16:
+            raise NotImplementedError(f"AutoencoderKL: the encoder's conv_out writes 2 * z_channels = {2 * dd['z_channels']} channels; "
+                                      f"stedm_conv_out covers up to {CONV_OUT_MAX} (z_channels <= {CONV_OUT_MAX // 2}: kl-f4, kl-f8) and the glue "
+                                      f"convolutions up to 16 (embed_dim <= 8)")
+        if colorize_nlabels is not None:
+            raise NotImplementedError("colorize_nlabels: a logging option of the autoencoder's own training, unused by the frozen stage")
+        self.embed_dim, self.image_key = embed_dim, image_key
+        self._build_halves(dd, precision)
+        self.loss = nn.Identity()                     # whatever lossconfig names (LPIPSWithDiscriminator): a checkpoint's loss.* keys are dropped
+        self.quant_conv = nn.Conv2d(2 * dd["z_channels"], 2 * embed_dim, 1)
+        self.post_quant_conv = nn.Conv2d(embed_dim, dd["z_channels"], 1)
+        if monitor is not None:
+            self.monitor = monitor
+        self._freeze(ckpt_path, ignore_keys)
+
+    @torch.no_grad()
+    def encode(self, x):
+        """autoencoder.py:324-328: encoder, quant_conv -> the posterior over the latents."""
+        from .distributions import DiagonalGaussianDistribution
+        self._prepare()
+        self._cs = {}
+        h = self._encoder(x.float().contiguous())
+        return DiagonalGaussianDistribution(ops.conv1x1_nchw(h, self.quant_conv.weight, self.quant_conv.bias))
+
+    @torch.no_grad()
+    def decode(self, z, *args, **kwargs):
+        """autoencoder.py:330-333: post_quant_conv, decoder."""
+        self._prepare()
+        self._cs = {}
+        z = ops.conv1x1_nchw(z.float().contiguous(), self.post_quant_conv.weight, self.post_quant_conv.bias)
+        return self._decoder(z)
+
+    @torch.no_grad()
+    def forward(self, input, sample_posterior=True):
+        """autoencoder.py:335-342 -> (dec, posterior)."""
+        posterior = self.encode(input)
+        z = posterior.sample() if sample_posterior else posterior.mode()
+        return self.decode(z), posterior
+
+
+class IdentityFirstStage(nn.Module):
+    """autoencoder.py:426-443: a diffusion model over the pixels themselves."""
+
+    def __init__(self, *args, vq_interface=False, **kwargs):
+        super().__init__()
+        self.vq_interface = vq_interface
+
+    def encode(self, x, *args, **kwargs):
+        return x
+
+    def decode(self, x, *args, **kwargs):
+        return x
+
+    def quantize(self, x, *args, **kwargs):
+        return (x, None, [None, None, None]) if self.vq_interface else x
+
+    def forward(self, x, *args, **kwargs):
+        return x
