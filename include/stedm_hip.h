@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 25
+#define STEDM_ABI_VERSION 26
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -792,6 +792,29 @@ int stedm_adamw_ema_sched(const void* table, const int* chunk_tensor, const long
                           float weight_decay, const float* sched, const int* sched_idx, float grad_scale, void* stream);
 int stedm_adamw_ema_pack_sched(const void* descs, int ndesc, int total_blocks, float beta1, float beta2, float eps, float weight_decay,
                                const float* sched, const int* sched_idx, float grad_scale, void* stream);
+/* ---- gradient-norm clipping (ABI 26): torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False) without a host read ---------------
+ * g: n fp32 values (the flat gradient arena, alignment padding included: it is zero), 4-byte aligned; 16-byte loads from the first aligned
+ * address, scalar loads before it and for the ragged tail. out[3] on the DEVICE:
+ *   out[0] = total_norm = grad_scale * sqrt(sum g^2): squares, sum and root in fp64 (per-block partials added in block order: no atomics, the
+ *            same bits every run), rounded once to fp32
+ *   out[1] = clip_coef = c < 1 ? c : 1 with c = max_norm / (total_norm + 1e-6) in fp32; a NaN c stays NaN (non-finite gradients propagate
+ *            as in torch); max_norm <= 0: 1 (norm reporting only)
+ *   out[2] = 1 when the sum is not finite or total_norm overflows fp32 (the coefficient is then 0 or NaN), else 0
+ * ws: stedm_grad_norm_blocks(n) doubles (at most 512). Two launches, shape-static: runs under graph capture. */
+int stedm_grad_norm_blocks(long n);
+int stedm_grad_norm(const float* g, long n, float grad_scale, float max_norm, double* ws, float* out, void* stream);
+/* The four optimizer passes above with the gradient scale grad_scale * *clip_coef (fp32 product, clip_coef a DEVICE float read once per block:
+ * out + 1 of stedm_grad_norm). clip_coef NULL: the call above, bit for bit; so is *clip_coef == 1.0f. */
+int stedm_adamw_ema_clip(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float lr, float beta1,
+                         float beta2, float eps, float weight_decay, int step, float ema_decay, float grad_scale, const float* clip_coef,
+                         void* stream);
+int stedm_adamw_ema_pack_clip(const void* descs, int ndesc, int total_blocks, float lr, float beta1, float beta2, float eps,
+                              float weight_decay, int step, float ema_decay, float grad_scale, const float* clip_coef, void* stream);
+int stedm_adamw_ema_sched_clip(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float beta1, float beta2,
+                               float eps, float weight_decay, const float* sched, const int* sched_idx, float grad_scale,
+                               const float* clip_coef, void* stream);
+int stedm_adamw_ema_pack_sched_clip(const void* descs, int ndesc, int total_blocks, float beta1, float beta2, float eps, float weight_decay,
+                                    const float* sched, const int* sched_idx, float grad_scale, const float* clip_coef, void* stream);
 /* LitEma.forward alone (ldm/modules/ema.py:25-44; on_train_batch_end, ddpm.py:369-371, runs it once per micro-batch, also on the
  * micro-batches of an accumulation window that do not step the optimizer): ema -= (1 - ema_decay) * (ema - p) over the same table
  * (entries without a shadow are skipped; g / m / v are not read). */

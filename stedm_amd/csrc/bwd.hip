@@ -989,6 +989,68 @@ __global__ void __launch_bounds__(DL_THREADS) diffusion_loss_final_kernel(const 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ gradient norm
+// total_norm = grad_scale * sqrt(sum g^2) over the flat gradient arena and the coefficient of torch.nn.utils.clip_grad_norm_ (stedm_grad_norm).
+// Two stages like the losses above: block b owns float4 b * 1024 + lane, + gridDim.x * 1024, ... of the 16-byte aligned body (a fixed
+// assignment: no atomics, the same bits every run), block 0 also the at most 3 floats before the first aligned address and the at most 3
+// after the last whole float4; squares and sums in fp64 (the square of an fp32 is exact there).
+constexpr int GNORM_THREADS = 1024;
+constexpr int GNORM_BLOCK_ELEMS = GNORM_THREADS * 4 * 4;      // elements of a block per round of its unrolled stride loop
+constexpr int GNORM_MAX_BLOCKS = 512;                         // 2 per CU = 32 waves; few partials: the final launch adds them serially (4 KiB of LDS)
+constexpr int GNORM_FINAL_THREADS = 256;
+static int gnorm_blocks(long n) {
+  const long b = (n + GNORM_BLOCK_ELEMS - 1) / GNORM_BLOCK_ELEMS;
+  return (int)(b > GNORM_MAX_BLOCKS ? GNORM_MAX_BLOCKS : b);
+}
+__device__ __forceinline__ double gnorm_sq4(double s, const float4 a) {
+  s = fma((double)a.x, (double)a.x, s); s = fma((double)a.y, (double)a.y, s);
+  s = fma((double)a.z, (double)a.z, s); return fma((double)a.w, (double)a.w, s);
+}
+__global__ void __launch_bounds__(GNORM_THREADS) grad_norm_partial_kernel(const float* __restrict__ g, long n, double* __restrict__ part) {
+  __shared__ double red[GNORM_THREADS];
+  long head = (long)(((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) >> 2);      // floats before the first 16-byte boundary
+  if (head > n) head = n;
+  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + head);
+  const long n4 = (n - head) >> 2;
+  const long stride = (long)gridDim.x * GNORM_THREADS;
+  long i = (long)blockIdx.x * GNORM_THREADS + threadIdx.x;
+  double s = 0.0;
+  for (; i + 3 * stride < n4; i += 4 * stride) {           // four independent 16-byte loads in flight per lane
+    const float4 a = g4[i], b = g4[i + stride], c = g4[i + 2 * stride], d = g4[i + 3 * stride];
+    s = gnorm_sq4(gnorm_sq4(gnorm_sq4(gnorm_sq4(s, a), b), c), d);
+  }
+  for (; i < n4; i += stride) s = gnorm_sq4(s, g4[i]);
+  if (blockIdx.x == 0) {                                    // the unaligned start and the ragged tail: at most 3 floats each
+    const long tail0 = head + 4 * n4;
+    if ((long)threadIdx.x < head) { const double x = (double)g[threadIdx.x]; s = fma(x, x, s); }
+    if (tail0 + threadIdx.x < n) { const double x = (double)g[tail0 + threadIdx.x]; s = fma(x, x, s); }
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = GNORM_THREADS / 2; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+// One block: the partials in index order, then out = {total_norm, clip_coef, flag of a non-finite sum or norm}. clip_coef = min(max_norm / (total_norm + 1e-6), 1)
+// in fp32 as torch forms it, written so that a NaN quotient stays NaN (fminf would return 1); max_norm <= 0: norm reporting only, coefficient 1.
+__global__ void __launch_bounds__(GNORM_FINAL_THREADS) grad_norm_final_kernel(const double* __restrict__ part, int nb, float grad_scale, float max_norm,
+                                                                        float* __restrict__ out) {
+  __shared__ double sh[GNORM_MAX_BLOCKS];
+  for (int i = threadIdx.x; i < nb; i += GNORM_FINAL_THREADS) sh[i] = part[i];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double s = 0.0;
+  for (int i = 0; i < nb; ++i) s += sh[i];
+  const float norm = (float)((double)grad_scale * sqrt(s));
+  float coef = 1.0f;
+  if (max_norm > 0.f) {
+    const float c = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+    coef = c >= 1.0f ? 1.0f : c;
+  }
+  out[0] = norm;
+  out[1] = coef;
+  out[2] = isfinite(s) && isfinite(norm) ? 0.f : 1.f;      // (a finite sum can still overflow the fp32 norm: coefficient 0 then, flagged too)
+}
+
 // ------------------------------------------------------------------------------------------------ optimizer
 // AdamW (torch.optim.AdamW semantics) + LitEma (ema.py:25-44) over many tensors in one launch. table[t] = {p, g, m, v, ema, n};
 // chunk_tensor[blockIdx.x] / chunk_off[blockIdx.x] map a block to 4096 elements of one tensor.
@@ -1007,7 +1069,8 @@ __device__ __forceinline__ void adamw_one(float& p, float g_raw, float& m, float
 __global__ void __launch_bounds__(256) adamw_ema_kernel(const OptTensor* __restrict__ table, const int* __restrict__ chunk_tensor,
                                                         const long* __restrict__ chunk_off, float lr, float beta1, float beta2, float eps, float wd, float bc1,
                                                         float bc2_sqrt, float ema_decay, float grad_scale, const float* __restrict__ sched,
-                                                        const int* __restrict__ sched_idx) {
+                                                        const int* __restrict__ sched_idx, const float* __restrict__ clip_coef) {
+  if (clip_coef) grad_scale = __fmul_rn(grad_scale, *clip_coef);      // stedm_grad_norm's coefficient, read once per block; 1.0f leaves the scale's bits
   if (sched) {      // graph replay: this step's row of the host-built schedule {bc1, sqrt(bc2), ema_decay, lr} (stedm_adamw_ema_sched)
     const float* r = sched + 4 * (long)*sched_idx;
     bc1 = r[0]; bc2_sqrt = r[1]; ema_decay = r[2]; lr = r[3];
@@ -1067,8 +1130,10 @@ static_assert(sizeof(FusedPackOut) == 24 && sizeof(FusedOptDesc) == 160, "FusedO
 template <int ROWS, int CIW>
 __global__ void __launch_bounds__(256) adamw_ema_pack_kernel(const FusedOptDesc* __restrict__ descs, const int nd, float lr, float beta1, float beta2,
                                                              float eps, float wd, float bc1, float bc2_sqrt, float ema_decay, float grad_scale,
-                                                             const float* __restrict__ sched, const int* __restrict__ sched_idx) {
+                                                             const float* __restrict__ sched, const int* __restrict__ sched_idx,
+                                                             const float* __restrict__ clip_coef) {
   extern __shared__ float ftile[];        // [ROWS][CIW * taps + 1]
+  if (clip_coef) grad_scale = __fmul_rn(grad_scale, *clip_coef);
   if (sched) {
     const float* r = sched + 4 * (long)*sched_idx;
     bc1 = r[0]; bc2_sqrt = r[1]; ema_decay = r[2]; lr = r[3];
@@ -1417,27 +1482,50 @@ extern "C" int stedm_diffusion_loss(const float* pred, const float* target, cons
   return 0;
 }
 
-extern "C" int stedm_adamw_ema(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float lr, float beta1, float beta2, float eps,
-                               float weight_decay, int step, float ema_decay, float grad_scale, void* stream) {
+// The gradient arena's norm and clip coefficient (see grad_norm_partial_kernel): ws = stedm_grad_norm_blocks(n) doubles, out = 3 floats on the device.
+extern "C" int stedm_grad_norm_blocks(long n) { return n > 0 ? gnorm_blocks(n) : 0; }
+
+extern "C" int stedm_grad_norm(const float* g, long n, float grad_scale, float max_norm, double* ws, float* out, void* stream) {
+  STEDM_CHECK_ARG(g && ws && out && n > 0 && (reinterpret_cast<uintptr_t>(g) & 3) == 0, "grad_norm: bad args");
+  const int nb = gnorm_blocks(n);
+  grad_norm_partial_kernel<<<nb, GNORM_THREADS, 0, as_stream(stream)>>>(g, n, ws);
+  grad_norm_final_kernel<<<1, GNORM_FINAL_THREADS, 0, as_stream(stream)>>>(ws, nb, grad_scale, max_norm, out);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+// The four optimizer entry points exist in two forms: *_clip takes clip_coef, a DEVICE float (out[1] of stedm_grad_norm) that multiplies grad_scale
+// inside the kernel, so a clipped step needs no host read; the plain forms pass NULL and keep their bits.
+extern "C" int stedm_adamw_ema_clip(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float lr, float beta1, float beta2,
+                                    float eps, float weight_decay, int step, float ema_decay, float grad_scale, const float* clip_coef, void* stream) {
   STEDM_CHECK_ARG(table && chunk_tensor && chunk_off && nchunks > 0 && step >= 1, "adamw_ema: bad args");
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2 = (float)(1.0 - pow((double)beta2, (double)step));
   adamw_ema_kernel<<<nchunks, 256, 0, as_stream(stream)>>>((const OptTensor*)table, chunk_tensor, chunk_off, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2),
-                                                          ema_decay, grad_scale, nullptr, nullptr);
+                                                          ema_decay, grad_scale, nullptr, nullptr, clip_coef);
   STEDM_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int stedm_adamw_ema(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, int step, float ema_decay, float grad_scale, void* stream) {
+  return stedm_adamw_ema_clip(table, chunk_tensor, chunk_off, nchunks, lr, beta1, beta2, eps, weight_decay, step, ema_decay, grad_scale, nullptr, stream);
 }
 
 // The two optimizer passes with the step-dependent scalars read on the device: sched [n][4] = {1 - beta1^s, sqrt(1 - beta2^s), ema decay of step s,
 // learning rate of step s} built by the host for a window of steps, *sched_idx = the row of the step being replayed (advanced by stedm_step_advance
 // inside the captured step). A captured training step (UNetTrainer.capture_step) replays with nothing but that index changing.
-extern "C" int stedm_adamw_ema_sched(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float beta1, float beta2, float eps,
-                                     float weight_decay, const float* sched, const int* sched_idx, float grad_scale, void* stream) {
+extern "C" int stedm_adamw_ema_sched_clip(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float beta1, float beta2, float eps,
+                                          float weight_decay, const float* sched, const int* sched_idx, float grad_scale, const float* clip_coef,
+                                          void* stream) {
   STEDM_CHECK_ARG(table && chunk_tensor && chunk_off && nchunks > 0 && sched && sched_idx, "adamw_ema_sched: bad args");
   adamw_ema_kernel<<<nchunks, 256, 0, as_stream(stream)>>>((const OptTensor*)table, chunk_tensor, chunk_off, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, 0.f,
-                                                          grad_scale, sched, sched_idx);
+                                                          grad_scale, sched, sched_idx, clip_coef);
   STEDM_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int stedm_adamw_ema_sched(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float beta1, float beta2, float eps,
+                                     float weight_decay, const float* sched, const int* sched_idx, float grad_scale, void* stream) {
+  return stedm_adamw_ema_sched_clip(table, chunk_tensor, chunk_off, nchunks, beta1, beta2, eps, weight_decay, sched, sched_idx, grad_scale, nullptr, stream);
 }
 
 // piece geometry of stedm_adamw_ema_pack: a tensor takes (cout / rows) * (cin / ciw) blocks. 32 x 32, 64 x 32, 32 x 64 and 64 x 64 measured the
@@ -1450,26 +1538,34 @@ extern "C" int stedm_adamw_ema_pack_piece(int* rows, int* ciw) {
   return 0;
 }
 
-extern "C" int stedm_adamw_ema_pack(const void* descs, int ndesc, int total_blocks, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                    int step, float ema_decay, float grad_scale, void* stream) {
+extern "C" int stedm_adamw_ema_pack_clip(const void* descs, int ndesc, int total_blocks, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                         int step, float ema_decay, float grad_scale, const float* clip_coef, void* stream) {
   STEDM_CHECK_ARG(descs && ndesc > 0 && total_blocks > 0 && step >= 1, "adamw_ema_pack: bad args");
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2 = (float)(1.0 - pow((double)beta2, (double)step));
   const size_t lds = (size_t)kOptRows * (kOptCiw * 9 + 1) * sizeof(float);
   adamw_ema_pack_kernel<kOptRows, kOptCiw><<<total_blocks, 256, lds, as_stream(stream)>>>((const FusedOptDesc*)descs, ndesc, lr, beta1, beta2, eps, weight_decay,
-                                                                                          bc1, sqrtf(bc2), ema_decay, grad_scale, nullptr, nullptr);
+                                                                                          bc1, sqrtf(bc2), ema_decay, grad_scale, nullptr, nullptr, clip_coef);
   STEDM_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int stedm_adamw_ema_pack(const void* descs, int ndesc, int total_blocks, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                    int step, float ema_decay, float grad_scale, void* stream) {
+  return stedm_adamw_ema_pack_clip(descs, ndesc, total_blocks, lr, beta1, beta2, eps, weight_decay, step, ema_decay, grad_scale, nullptr, stream);
+}
 
-extern "C" int stedm_adamw_ema_pack_sched(const void* descs, int ndesc, int total_blocks, float beta1, float beta2, float eps, float weight_decay,
-                                          const float* sched, const int* sched_idx, float grad_scale, void* stream) {
+extern "C" int stedm_adamw_ema_pack_sched_clip(const void* descs, int ndesc, int total_blocks, float beta1, float beta2, float eps, float weight_decay,
+                                               const float* sched, const int* sched_idx, float grad_scale, const float* clip_coef, void* stream) {
   STEDM_CHECK_ARG(descs && ndesc > 0 && total_blocks > 0 && sched && sched_idx, "adamw_ema_pack_sched: bad args");
   const size_t lds = (size_t)kOptRows * (kOptCiw * 9 + 1) * sizeof(float);
   adamw_ema_pack_kernel<kOptRows, kOptCiw><<<total_blocks, 256, lds, as_stream(stream)>>>((const FusedOptDesc*)descs, ndesc, 0.f, beta1, beta2, eps, weight_decay,
-                                                                                          1.f, 1.f, 0.f, grad_scale, sched, sched_idx);
+                                                                                          1.f, 1.f, 0.f, grad_scale, sched, sched_idx, clip_coef);
   STEDM_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int stedm_adamw_ema_pack_sched(const void* descs, int ndesc, int total_blocks, float beta1, float beta2, float eps, float weight_decay,
+                                          const float* sched, const int* sched_idx, float grad_scale, void* stream) {
+  return stedm_adamw_ema_pack_sched_clip(descs, ndesc, total_blocks, beta1, beta2, eps, weight_decay, sched, sched_idx, grad_scale, nullptr, stream);
 }
 
 extern "C" int stedm_ema_update(const void* table, const int* chunk_tensor, const long* chunk_off, int nchunks, float ema_decay, void* stream) {

@@ -173,7 +173,7 @@ class LatentDiffusion(nn.Module):
                  cond_stage_config=None, first_stage_config=None, cond_stage_trainable=False, first_stage_key="image",
                  cond_stage_key="image", log_every_t=100, scale_factor=1.0, use_graph=False, use_ema=True, scale_by_std=False,
                  l_simple_weight=1.0, original_elbo_weight=0.0, learn_logvar=False, logvar_init=0., clip_denoised=True, v_posterior=0.,
-                 **ignored):
+                 scheduler_config=None, **ignored):
         super().__init__()
         if parameterization != "eps":
             raise NotImplementedError(f"parameterization {parameterization!r}: every sampler and the training step are built for eps-prediction")
@@ -197,7 +197,14 @@ class LatentDiffusion(nn.Module):
         self.scale_factor = scale_factor
         self.learn_logvar = bool(learn_logvar)
         self.use_ema = use_ema          # ddpm.py:58,91-94: LitEma over `model`; the shadows live in the trainer (stedm_amd/train.py)
-        self.use_scheduler = False      # ddpm.py:95: scheduler_config is absent from the reference configs
+        # ddpm.py:95-97, 1364-1386: a {target, params} config of one of ldm/lr_scheduler.py's classes becomes the fused optimizer's
+        # per-step LambdaLR (stedm_amd/lr_scheduler.py; configure_trainer hands its `schedule` over). Built here or refused, never dropped
+        self.use_scheduler = scheduler_config is not None
+        self.scheduler_config = scheduler_config
+        self.lr_scheduler = None
+        if self.use_scheduler:
+            from .lr_scheduler import instantiate_from_config as instantiate_scheduler
+            self.lr_scheduler = instantiate_scheduler(scheduler_config)
         self.restarted_from_ckpt = False
         self.use_graph = use_graph
         self.model = DiffusionWrapper(unet_config, conditioning_key)
@@ -582,9 +589,14 @@ class LatentDiffusion(nn.Module):
 
     # ------------------------------------------------------------------------------------------ training step (fused fast path)
     def configure_trainer(self, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                          ema_decay: Optional[float] = 0.9999, accumulate_grad_batches: int = 1):
+                          ema_decay: Optional[float] = 0.9999, accumulate_grad_batches: int = 1, gradient_clip_val: Optional[float] = None,
+                          gradient_clip_algorithm: str = "norm"):
         """AdamW over the U-Net's parameters (modules/ldm_diffusion.py:224-234 builds `torch.optim.AdamW(self._model.model.parameters()
         ...)`) + the EMA shadow of ddpm.py:369-371 / ema.py:25-44, as one fused kernel (stedm_amd/train.py).
+        gradient_clip_val / gradient_clip_algorithm: Lightning's `Trainer` arguments of the same names (which it refuses under manual
+        optimisation): the total gradient norm over the optimizer's parameters is clipped on the device before AdamW ("norm"; "value" is
+        not built and raises). None or 0 (Lightning's "no clipping"): off. With a `scheduler_config` the learning rate follows its schedule,
+        one scheduler step per optimizer step (ddpm.py:1374-1385: LambdaLR at interval "step").
         accumulate_grad_batches: `Trainer(accumulate_grad_batches=4)` of train_diff.py:76. A checkpoint loaded before this call
         (load_reference_state_dict) hands its EMA shadows / update counter and its AdamW state over to the new trainer."""
         from .train import UNetTrainer
@@ -598,14 +610,35 @@ class LatentDiffusion(nn.Module):
             # ddpm.py:1370-1372 / ldm_diffusion.py:228-229: appended after the cond stage's; no EMA shadow (LitEma covers `model` only). Its
             # gradient is written by the loss kernel into its slot of the arena's tail: it accumulates and all-reduces with that bucket
             extra.append(self.logvar)
+        algorithm = str(gradient_clip_algorithm or "norm").lower()
+        if algorithm != "norm":
+            if algorithm == "value":
+                raise NotImplementedError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: the fused step clips the total gradient norm "
+                                          "(\"norm\"); clipping by value is not built")
+            raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: \"norm\" or \"value\"")
+        max_norm = None if gradient_clip_val is None or float(gradient_clip_val) == 0.0 else float(gradient_clip_val)
+        if max_norm is not None and not max_norm > 0:
+            raise ValueError(f"gradient_clip_val {gradient_clip_val!r}: a positive norm (None or 0: no clipping)")
         tr = UNetTrainer(self.model.diffusion_model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                         ema_decay=ema_decay if self.use_ema else None, accumulate_grad_batches=accumulate_grad_batches, extra_params=extra)
+                         ema_decay=ema_decay if self.use_ema else None, accumulate_grad_batches=accumulate_grad_batches, extra_params=extra,
+                         max_grad_norm=max_norm, lr_lambda=self.lr_scheduler.schedule if self.lr_scheduler is not None else None)
         self.__dict__["_trainer"] = tr
         if self.__dict__.get("_ema_loaded"):
             tr.load_ema({n[len("diffusion_model."):]: v for n, v in self._ema_loaded.items()}, self._ema_num_updates)
         if self.__dict__.get("_opt_loaded") is not None:
             tr.load_optimizer_state_dict(self._opt_loaded)
         return tr
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """total gradient norm of the last optimizer step (0-d device tensor; reading it is the caller's sync). None without
+        gradient_clip_val, or before the first optimizer step."""
+        tr = self.__dict__.get("_trainer")
+        return None if tr is None else tr.last_grad_norm
+
+    def current_lr(self) -> float:
+        """the learning rate the next optimizer step runs with (the base rate without a scheduler_config)"""
+        return self._trainer_or_default().current_lr()
 
     @torch.no_grad()
     def p_losses_backward(self, x_start, cond, t, noise=None, cond_input=None):

@@ -84,8 +84,13 @@ class LDM_Diffusion(_Base):
     # ------------------------------------------------------------------------------------------ training
     def configure_optimizers(self):
         """ldm_diffusion.py:224-234: AdamW(lr) over model.model (+ cond_stage_model while cond_stage_trainable; the aggregation block is
-        not in the reference's list). Built as the fused HIP optimizer; Lightning gets no optimizer object (manual optimisation)."""
-        self._model.configure_trainer(lr=self._lr, accumulate_grad_batches=self._accumulate)
+        not in the reference's list). Built as the fused HIP optimizer; Lightning gets no optimizer object (manual optimisation) — and
+        refuses `Trainer(gradient_clip_val=...)` for that reason, so the optional config keys `gradient_clip_val` / `gradient_clip_algorithm`
+        (Lightning's names) are read here instead; configs without them run as before. A `scheduler_config` under cfg.diffusion reaches
+        the trainer through the model (LatentDiffusion.configure_trainer)."""
+        cfg = self._cfg
+        self._model.configure_trainer(lr=self._lr, accumulate_grad_batches=self._accumulate, gradient_clip_val=getattr(cfg, "gradient_clip_val", None),
+                                      gradient_clip_algorithm=getattr(cfg, "gradient_clip_algorithm", None) or "norm")
         return None
 
     def training_step(self, batch, batch_idx):

@@ -1689,8 +1689,42 @@ def note_raw_write() -> None:
     _RAW_WRITES[0] += 1
 
 
+def grad_norm_blocks(n: int) -> int:
+    """doubles of workspace stedm_grad_norm needs for n gradient values (one partial per block)"""
+    return int(lib().stedm_grad_norm_blocks(int(n)))
+
+
+def grad_norm(g: torch.Tensor, grad_scale: float = 1.0, max_norm: float = 0.0, ws: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [3] = {grad_scale * ||g||_2, clip coefficient of clip_grad_norm_(max_norm), non-finite flag} on the device (include/stedm_hip.h:
+    stedm_grad_norm); g: flat contiguous fp32 (any 4-byte aligned start). max_norm <= 0: the coefficient is 1. No host read."""
+    _chk(g, name="g")
+    n = g.numel()
+    assert n > 0
+    need = grad_norm_blocks(n)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.float64, device=g.device)
+    if out is None:
+        out = torch.empty((3,), dtype=torch.float32, device=g.device)
+    assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.numel() >= need and out.dtype == torch.float32 and out.numel() >= 3
+    check(lib().stedm_grad_norm(g.data_ptr(), n, float(grad_scale), float(max_norm), ws.data_ptr(), out.data_ptr(), _stream()), "stedm_grad_norm")
+    return out
+
+
+def _coef_ptr(clip_coef: torch.Tensor) -> int:
+    assert clip_coef.dtype == torch.float32 and clip_coef.numel() >= 1 and clip_coef.is_cuda, "clip_coef: a device fp32 scalar (grad_norm(...)[1:2])"
+    return clip_coef.data_ptr()
+
+
 def adamw_ema(table: torch.Tensor, chunk_tensor: torch.Tensor, chunk_off: torch.Tensor, lr: float, beta1: float, beta2: float, eps: float,
-              weight_decay: float, step: int, ema_decay: float, grad_scale: float = 1.0) -> None:
+              weight_decay: float, step: int, ema_decay: float, grad_scale: float = 1.0, clip_coef: Optional[torch.Tensor] = None) -> None:
+    """clip_coef (here and in the three forms below): a device fp32 scalar that multiplies grad_scale inside the kernel (stedm_*_clip)"""
+    if clip_coef is not None:
+        check(lib().stedm_adamw_ema_clip(table.data_ptr(), chunk_tensor.data_ptr(), chunk_off.data_ptr(), chunk_tensor.numel(), float(lr), float(beta1),
+                                         float(beta2), float(eps), float(weight_decay), int(step), float(ema_decay), float(grad_scale),
+                                         _coef_ptr(clip_coef), _stream()), "stedm_adamw_ema_clip")
+        note_raw_write()
+        return
     check(lib().stedm_adamw_ema(table.data_ptr(), chunk_tensor.data_ptr(), chunk_off.data_ptr(), chunk_tensor.numel(), float(lr), float(beta1),
                                 float(beta2), float(eps), float(weight_decay), int(step), float(ema_decay), float(grad_scale), _stream()), "stedm_adamw_ema")
     note_raw_write()
@@ -1704,17 +1738,29 @@ def adamw_ema_pack_piece() -> Tuple[int, int]:
 
 
 def adamw_ema_pack(descs: torch.Tensor, ndesc: int, total_blocks: int, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
-                   step: int, ema_decay: float, grad_scale: float = 1.0) -> None:
+                   step: int, ema_decay: float, grad_scale: float = 1.0, clip_coef: Optional[torch.Tensor] = None) -> None:
     """AdamW + EMA over convolution weights, refreshing their fragment-order packs in the same pass (stedm_adamw_ema_pack)"""
+    if clip_coef is not None:
+        check(lib().stedm_adamw_ema_pack_clip(descs.data_ptr(), int(ndesc), int(total_blocks), float(lr), float(beta1), float(beta2), float(eps),
+                                              float(weight_decay), int(step), float(ema_decay), float(grad_scale), _coef_ptr(clip_coef), _stream()),
+              "stedm_adamw_ema_pack_clip")
+        note_raw_write()
+        return
     check(lib().stedm_adamw_ema_pack(descs.data_ptr(), int(ndesc), int(total_blocks), float(lr), float(beta1), float(beta2), float(eps),
                                      float(weight_decay), int(step), float(ema_decay), float(grad_scale), _stream()), "stedm_adamw_ema_pack")
     note_raw_write()
 
 
 def adamw_ema_sched(table: torch.Tensor, chunk_tensor: torch.Tensor, chunk_off: torch.Tensor, beta1: float, beta2: float, eps: float, weight_decay: float,
-                    sched: torch.Tensor, sched_idx: torch.Tensor, grad_scale: float = 1.0) -> None:
+                    sched: torch.Tensor, sched_idx: torch.Tensor, grad_scale: float = 1.0, clip_coef: Optional[torch.Tensor] = None) -> None:
     """stedm_adamw_ema with {bias corrections, EMA decay, learning rate} read from row *sched_idx of sched [n][4] on the device (captured step)"""
     assert sched.dtype == torch.float32 and sched.is_contiguous() and sched.shape[-1] == 4 and sched_idx.dtype == torch.int32
+    if clip_coef is not None:
+        check(lib().stedm_adamw_ema_sched_clip(table.data_ptr(), chunk_tensor.data_ptr(), chunk_off.data_ptr(), chunk_tensor.numel(), float(beta1),
+                                               float(beta2), float(eps), float(weight_decay), sched.data_ptr(), sched_idx.data_ptr(), float(grad_scale),
+                                               _coef_ptr(clip_coef), _stream()), "stedm_adamw_ema_sched_clip")
+        note_raw_write()
+        return
     check(lib().stedm_adamw_ema_sched(table.data_ptr(), chunk_tensor.data_ptr(), chunk_off.data_ptr(), chunk_tensor.numel(), float(beta1), float(beta2),
                                       float(eps), float(weight_decay), sched.data_ptr(), sched_idx.data_ptr(), float(grad_scale), _stream()),
           "stedm_adamw_ema_sched")
@@ -1722,9 +1768,15 @@ def adamw_ema_sched(table: torch.Tensor, chunk_tensor: torch.Tensor, chunk_off: 
 
 
 def adamw_ema_pack_sched(descs: torch.Tensor, ndesc: int, total_blocks: int, beta1: float, beta2: float, eps: float, weight_decay: float,
-                         sched: torch.Tensor, sched_idx: torch.Tensor, grad_scale: float = 1.0) -> None:
+                         sched: torch.Tensor, sched_idx: torch.Tensor, grad_scale: float = 1.0, clip_coef: Optional[torch.Tensor] = None) -> None:
     """stedm_adamw_ema_pack with the step-dependent scalars read on the device (see adamw_ema_sched)"""
     assert sched.dtype == torch.float32 and sched.is_contiguous() and sched.shape[-1] == 4 and sched_idx.dtype == torch.int32
+    if clip_coef is not None:
+        check(lib().stedm_adamw_ema_pack_sched_clip(descs.data_ptr(), int(ndesc), int(total_blocks), float(beta1), float(beta2), float(eps),
+                                                    float(weight_decay), sched.data_ptr(), sched_idx.data_ptr(), float(grad_scale), _coef_ptr(clip_coef),
+                                                    _stream()), "stedm_adamw_ema_pack_sched_clip")
+        note_raw_write()
+        return
     check(lib().stedm_adamw_ema_pack_sched(descs.data_ptr(), int(ndesc), int(total_blocks), float(beta1), float(beta2), float(eps), float(weight_decay),
                                            sched.data_ptr(), sched_idx.data_ptr(), float(grad_scale), _stream()), "stedm_adamw_ema_pack_sched")
     note_raw_write()

@@ -1,5 +1,5 @@
 """Training step of the U-Net on the HIP path: forward (the inference kernels, every block's intermediates kept), L1 loss,
-hand-scheduled backward, AdamW + EMA.
+hand-scheduled backward, AdamW + EMA, optionally behind gradient-norm clipping (max_grad_norm) and a per-step learning-rate lambda (lr_lambda).
 
 Mirrors what autograd does for the reference in `LatentDiffusion.p_losses` / `training_step` (ddpm.py:1015-1048, 345-358) with
 `torch.optim.AdamW` (modules/ldm_diffusion.py:224-234) and `LitEma` (ldm/modules/ema.py:25-44); SURVEY §8 row A15.
@@ -61,8 +61,17 @@ class UNetTrainer:
     land in their `.grad`, so DDP-style all-reduce and checkpointing see the usual tensors)."""
 
     def __init__(self, unet: UNetModel, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 ema_decay: Optional[float] = 0.9999, accumulate_grad_batches: int = 1, extra_params=()):
+                 ema_decay: Optional[float] = 0.9999, accumulate_grad_batches: int = 1, extra_params=(), max_grad_norm: Optional[float] = None,
+                 lr_lambda=None):
         self.m = unet
+        # Trainer(gradient_clip_val=..., gradient_clip_algorithm="norm"): torch.nn.utils.clip_grad_norm_ over every parameter of the optimizer,
+        # applied to the gradient AdamW sees (after accumulation and the all-reduce). The norm and the coefficient stay on the device
+        # (stedm_grad_norm); None: off, the optimizer runs its plain entry points; 0: last_grad_norm is reported, nothing is clipped
+        self.max_grad_norm = max_grad_norm
+        # LambdaLR at interval "step": optimizer step s (1-based) runs with lr * lr_lambda(s - 1) — a pure function of step_count, so a
+        # resumed run needs no scheduler state. self.lr stays the base rate (torch's initial_lr)
+        self.lr_lambda = lr_lambda
+        self.last_grad_norm: Optional[torch.Tensor] = None    # 0-d device tensor, overwritten by every optimizer step that computes the norm
         # parameters outside the U-Net that the same AdamW instance updates (the reference adds cond_stage_model's when
         # cond_stage_trainable, ldm_diffusion.py:224-234); their gradients are filled by the caller; no EMA (LitEma covers `model` only)
         self.extra_params = list(extra_params)
@@ -897,19 +906,51 @@ class UNetTrainer:
         if r["ct"].numel():
             self._adamw(st["table"], r["ct"], r["co"], decay, gs)
 
-    def _adamw(self, table, ct, co, decay: float, gs: float) -> None:
+    def _lr_at(self, step: int) -> float:
+        """learning rate of optimizer step `step` (1-based): lr * lr_lambda(step - 1), LambdaLR stepped once per optimizer step"""
+        if self.lr_lambda is None:
+            return self.lr
+        if step < 1:
+            raise ValueError(f"optimizer steps count from 1 (got {step})")
+        return self.lr * float(self.lr_lambda(int(step) - 1))
+
+    def current_lr(self) -> float:
+        """what torch reports as the param group's lr under LambdaLR after step_count optimizer steps: the rate the NEXT step runs with"""
+        return self._lr_at(self.step_count + 1)
+
+    def _adamw(self, table, ct, co, decay: float, gs: float, coef: Optional[torch.Tensor] = None) -> None:
         cs = getattr(self, "_cap_sched", None)
         if cs is not None:       # inside capture_step(): bias corrections / EMA decay / lr of the replayed step come from the device schedule
-            ops.adamw_ema_sched(table, ct, co, self.betas[0], self.betas[1], self.eps, self.wd, cs[0], cs[1], grad_scale=gs)
+            ops.adamw_ema_sched(table, ct, co, self.betas[0], self.betas[1], self.eps, self.wd, cs[0], cs[1], grad_scale=gs, clip_coef=coef)
         else:
-            ops.adamw_ema(table, ct, co, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, decay, grad_scale=gs)
+            ops.adamw_ema(table, ct, co, self._lr_at(self.step_count), self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, decay, grad_scale=gs,
+                          clip_coef=coef)
 
-    def _adamw_pack(self, descs, n: int, blocks: int, decay: float, gs: float) -> None:
+    def _adamw_pack(self, descs, n: int, blocks: int, decay: float, gs: float, coef: Optional[torch.Tensor] = None) -> None:
         cs = getattr(self, "_cap_sched", None)
         if cs is not None:
-            ops.adamw_ema_pack_sched(descs, n, blocks, self.betas[0], self.betas[1], self.eps, self.wd, cs[0], cs[1], grad_scale=gs)
+            ops.adamw_ema_pack_sched(descs, n, blocks, self.betas[0], self.betas[1], self.eps, self.wd, cs[0], cs[1], grad_scale=gs, clip_coef=coef)
         else:
-            ops.adamw_ema_pack(descs, n, blocks, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, decay, gs)
+            ops.adamw_ema_pack(descs, n, blocks, self._lr_at(self.step_count), self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, decay, gs,
+                               clip_coef=coef)
+
+    def _grad_norm(self, gs: float) -> Optional[torch.Tensor]:
+        """stedm_grad_norm over the whole arena (its alignment padding is zero) with the scale the optimizer folds in: last_grad_norm is the
+        norm of the gradient AdamW applies, identical on every rank (each reduces the same all-reduced arena in the same order). Returns the
+        device coefficient for the optimizer kernels, None when nothing is to be clipped."""
+        if self.max_grad_norm is None:
+            return None
+        mx = float(self.max_grad_norm)
+        if mx < 0 or mx != mx:
+            raise ValueError(f"max_grad_norm {self.max_grad_norm!r}: a positive norm, 0 (report the norm only) or None")
+        if getattr(self, "_gnorm", None) is None:
+            dev = self.grad_arena.device
+            self._gnorm = (torch.empty((ops.grad_norm_blocks(self.grad_arena.numel()),), dtype=torch.float64, device=dev),
+                           torch.zeros((3,), dtype=torch.float32, device=dev))
+        ws, out = self._gnorm
+        ops.grad_norm(self.grad_arena, gs, mx, ws, out)
+        self.last_grad_norm = out[0]
+        return out[1:2] if mx > 0 else None
 
     def _after_optimizer(self, fu) -> None:
         self.m.invalidate()      # parameters changed through raw pointers: repack on the next forward
@@ -924,7 +965,7 @@ class UNetTrainer:
     @torch.no_grad()
     def optimizer_step(self) -> None:
         """AdamW over every parameter + EMA shadow update (ema.py:25-44: decay = min(decay, (1+n)/(10+n))) in one launch; gradients
-        are read from the flat arena."""
+        are read from the flat arena. With max_grad_norm set, the arena's norm is taken first (accumulation folded back, all-reduce done)."""
         assert self._grads_ready, "optimizer_step() needs gradients from backward()"
         if self._opt is None:
             self._build_opt()
@@ -932,14 +973,15 @@ class UNetTrainer:
         self.step_count += 1
         decay = self._next_ema_decay() if self.ema_decay is not None else 0.0
         gs = getattr(self, "_grad_scale", 1.0)
+        coef = self._grad_norm(gs)       # gradient-norm clipping: the kernels below read the coefficient from the device (no host sync)
         fu = self._fused_opt() if self.fuse_packs else None
         if fu is None:
-            self._adamw(st["table"], st["ct"], st["co"], decay, gs)
+            self._adamw(st["table"], st["ct"], st["co"], decay, gs, coef)
         else:
             # convolution weights with fragment-order packs: the optimizer pass writes the packs of the next forward / backward itself
-            self._adamw_pack(fu["descs"], fu["n"], fu["blocks"], decay, gs)
+            self._adamw_pack(fu["descs"], fu["n"], fu["blocks"], decay, gs, coef)
             if fu["ct"].numel():
-                self._adamw(st["table"], fu["ct"], fu["co"], decay, gs)
+                self._adamw(st["table"], fu["ct"], fu["co"], decay, gs, coef)
         self._after_optimizer(fu)
 
     @torch.no_grad()
@@ -999,7 +1041,7 @@ class UNetTrainer:
             j = pos[id(p)]
             state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": self._opt["m"][j].detach().clone(),
                         "exp_avg_sq": self._opt["v"][j].detach().clone()}
-        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd, "amsgrad": False, "maximize": False,
+        group = {"lr": self.current_lr(), "initial_lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(order)))}
         return {"state": state, "param_groups": [group]}
 
@@ -1029,7 +1071,7 @@ class UNetTrainer:
         if steps:
             self.step_count = steps.pop()
         g = (sd.get("param_groups") or [{}])[0]
-        self.lr = float(g.get("lr", self.lr))
+        self.lr = float(g.get("initial_lr", g.get("lr", self.lr)))      # under LambdaLR torch keeps the base rate in initial_lr; lr is derived
         self.betas = tuple(float(b) for b in g.get("betas", self.betas))
         self.eps, self.wd = float(g.get("eps", self.eps)), float(g.get("weight_decay", self.wd))
 
@@ -1092,7 +1134,8 @@ class UNetTrainer:
         if k > 1 and getattr(self, "_acc_arena", None) is None:
             self._acc_arena = torch.empty_like(self.grad_arena)
         fu = None
-        if self.overlap_optimizer and not multi and k == 1 and self.fuse_packs and self._opt is not None:
+        # (not with clipping: the overlapped pass updates parameters before the last gradient, hence the norm, exists)
+        if self.overlap_optimizer and not multi and k == 1 and self.fuse_packs and self._opt is not None and self.max_grad_norm is None:
             fu = self._fused_opt()      # (None until the forward's and the backward's pack plans exist: the first steps run the plain order)
         if fu is not None and fu.get("runs"):
             osched = self._opt_sched()
@@ -1162,11 +1205,35 @@ class UNetTrainer:
     GRAPH_WARMUP = 3          # eager steps before the capture: the forward's and the backward's pack plans and the fused optimizer table exist from the 3rd
     GRAPH_WINDOW = 4096       # steps per upload of the device schedule
 
-    def _sched_rows(self, first_step: int, first_ema: int, n: int):
+    def _lr_rows(self, first_step: int, n: int):
+        """(fp32 learning rates of steps first_step .. first_step + n - 1, number of leading rows that hold one). A window reaches up to
+        GRAPH_WINDOW steps ahead, further than the run may go and further than a scheduler with finite cycles is defined (the reference's
+        raise past their last cycle): the rows end where the lambda first refuses a step, the rest are NaN (never read: _graph_window's
+        caller refills before the index gets there). A row for step 0 — row 0 of the very first window, the "step already taken" that
+        nobody reads — repeats step 1's. The lambda's own error is raised when not even the step after first_step has a rate, as the eager
+        step raises on reaching it."""
+        import numpy as np
+        lrs = np.full((n,), np.nan, np.float32)
+        if self.lr_lambda is None:
+            lrs[:] = np.float32(self.lr)
+            return lrs, n
+        valid = 0
+        for i in range(n):
+            try:
+                lrs[i] = np.float32(self._lr_at(max(first_step + i, 1)))
+            except Exception:
+                if i < min(n, 2):
+                    raise
+                break
+            valid = i + 1
+        return lrs, valid
+
+    def _sched_rows(self, first_step: int, first_ema: int, n: int, with_valid: bool = False):
         """{1 - beta1^s, sqrtf(1 - beta2^s), LitEma decay, lr} for steps first_step .. first_step + n - 1 with the arithmetic of stedm_adamw_ema
         (bwd.hip: betas arrive as C floats, the powers are taken in double) and of _next_ema_decay — a replayed step uses the very scalars the
-        eager step would have been launched with"""
+        eager step would have been launched with. The lr column: _lr_rows (with_valid: also its count of usable rows)."""
         import numpy as np
+        lrs, valid = self._lr_rows(first_step, n)
         b1, b2 = float(np.float32(self.betas[0])), float(np.float32(self.betas[1]))
         rows = np.empty((n, 4), np.float32)
         for i in range(n):
@@ -1175,16 +1242,18 @@ class UNetTrainer:
             rows[i, 1] = np.sqrt(np.float32(1.0 - b2 ** s_))
             e = first_ema + i
             rows[i, 2] = np.float32(min(self.ema_decay, (1 + e) / (10 + e))) if self.ema_decay is not None else 0.0
-            rows[i, 3] = np.float32(self.lr)
-        return rows
+            rows[i, 3] = lrs[i]
+        return (rows, valid) if with_valid else rows
 
     def _graph_window(self, g) -> None:
         """(re)fill the device schedule so that row 1 is the NEXT step (the captured step advances the index first) and rewind the index"""
         n = self.GRAPH_WINDOW
-        rows = self._sched_rows(self.step_count, self.ema_updates, n)      # row 0 = the step already taken (never read), row k = step_count + k
+        # row 0 = the step already taken (never read), row k = step_count + k; rows [0, valid) hold a learning rate (fewer than n only where
+        # the lr_lambda is not defined that far ahead: the window then ends there)
+        rows, valid = self._sched_rows(self.step_count, self.ema_updates, n, with_valid=True)
         g["sched"].copy_(torch.from_numpy(rows), non_blocking=False)
         g["idx"].zero_()
-        g["base"], g["lr"] = self.step_count, self.lr
+        g["base"], g["lr"], g["lam"], g["valid"] = self.step_count, self.lr, self.lr_lambda, valid
 
     @torch.no_grad()
     def train_step_graphed(self, x, c_concat, t, context, target, objective: Optional[Objective] = None) -> torch.Tensor:
@@ -1196,7 +1265,10 @@ class UNetTrainer:
         a time (stedm_adamw_ema_sched); the step index advances inside the graph. Same kernels on the same values as the eager step: the
         parameters after k replayed steps equal those after k eager steps bit for bit (tests/test_gpu_train.py). The graph is dropped (and
         re-captured after GRAPH_WARMUP eager steps) when the shapes change or anything outside this method touched the parameters (EMA swap,
-        checkpoint load, an eager step). Returns the loss [1] (device tensor, overwritten by the next step)."""
+        checkpoint load, an eager step). With max_grad_norm set the two stedm_grad_norm launches and the coefficient pointer of the optimizer
+        kernels are part of the capture (max_norm is a baked argument: changing it, or switching clipping on or off, drops the graph like any
+        other stale key) and last_grad_norm is valid after a replay; with an lr_lambda the schedule's learning-rate column follows it, so a rate
+        that moves every step costs no refill. Returns the loss [1] (device tensor, overwritten by the next step)."""
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("train_step_graphed: one rank only (the bucketed all-reduce of train_step() is issued by the host)")
@@ -1209,6 +1281,8 @@ class UNetTrainer:
         key = tuple(None if a is None else (tuple(a.shape), a.dtype) for a in args)
         if objective is not None and not objective.plain:
             key = key + (objective.key(),)           # the captured loss launch holds the objective's scalars and table pointers
+        if self.max_grad_norm is not None:
+            key = key + (("max_grad_norm", float(self.max_grad_norm)),)      # a baked argument of the captured norm launch
         g = getattr(self, "_graph", None)
         if g is not None and (g["key"] != key or g["token"] != self.m.freshness_token() or g["host_step"] != self.step_count):
             g = self._graph = None                    # someone else moved the parameters or the counters: the captured plan is stale
@@ -1220,7 +1294,8 @@ class UNetTrainer:
                 self._graph_eager += 1
                 return self.train_step(x, c_concat, t, context, target, objective=objective)
             g = self._capture(args, key, objective)
-        if self.step_count + 1 - g["base"] >= self.GRAPH_WINDOW or g["lr"] != self.lr:
+        # (the rows hold the schedule's own movement: only a base rate or a lambda replaced by hand refills them early)
+        if self.step_count + 1 - g["base"] >= min(self.GRAPH_WINDOW, g["valid"]) or g["lr"] != self.lr or g["lam"] is not self.lr_lambda:
             self._graph_window(g)
         for dst, src in zip(g["inputs"], args):
             if dst is not None:

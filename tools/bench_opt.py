@@ -35,3 +35,20 @@ for name, f in (("fused adamw+pack", k_fused), ("plain adamw (all tensors)", k_p
     print(f"{name}: {e0.elapsed_time(e1) / 20 * 1000:.0f} us")
 n = sum(p.numel() for p in st["params"])
 print("parameters", n)
+# the gradient-norm kernel alone (stedm_grad_norm: one read of the arena per clipped optimizer step) at this model's arena size
+HBM_PEAK = 8.0e12        # bytes / s, the MI355X's HBM3E specification
+arena = tr.grad_arena
+ws = torch.empty((ops.grad_norm_blocks(arena.numel()),), dtype=torch.float64, device=dev); out = torch.empty((3,), device=dev)
+for _ in range(3): ops.grad_norm(arena, 1.0, 1.0, ws, out)
+torch.cuda.synchronize()
+ts = []
+for _ in range(5):
+    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20): ops.grad_norm(arena, 1.0, 1.0, ws, out)
+    e1.record(); torch.cuda.synchronize()
+    ts.append(e0.elapsed_time(e1) / 20 * 1e-3)
+ts.sort()
+byts = 4 * arena.numel()
+print(f"grad_norm over the arena ({arena.numel()} floats, {byts / 1e9:.3f} GB): median {ts[2] * 1e6:.1f} us (min {ts[0] * 1e6:.1f}, max {ts[-1] * 1e6:.1f}) = "
+      f"{byts / ts[2] / 1e12:.2f} TB/s, {100 * byts / ts[2] / HBM_PEAK:.0f} % of the {HBM_PEAK / 1e12:.0f} TB/s HBM peak; norm {float(out[0]):.4f}")
