@@ -1,7 +1,8 @@
 """Plain torch restatements of the training step's helper kernels (stedm_amd/csrc/bwd.hip), written from the formulas in the kernel
 comments and the docstrings of stedm_amd/ops.py. Every function runs in the dtype and on the device of its inputs: the tests feed
 fp64 for a reference, fp32 to pin a reference's own rounding against its bound. Shared by tests/test_bwd_refs_cpu.py (pins these
-functions against torch autograd) and tests/test_gpu_bwd_kernels.py (pins the kernels against these functions).
+functions against torch autograd), tests/test_gpu_bwd_kernels.py (pins the kernels against these functions) and
+tests/test_gpu_bwd_conv_exact.py (pins the trainer's dgrad / wgrad dispatch against the convolution-backward references).
 
 Also here: the two input generators and the derived error bounds of the kernels that round (u = 2^-24 is the fp32 unit roundoff:
 one correctly rounded operation has relative error <= u, "1 ulp" of the hardware exp / rcp is taken as 2u)."""
@@ -100,6 +101,99 @@ def split16(x32, dtype):
     """fp32 -> (hi, lo) 16-bit planes: hi = round-to-nearest-even cast, lo = cast of the fp32 remainder x - hi"""
     hi = x32.to(dtype)
     return hi, (x32 - hi.to(torch.float32)).to(dtype)
+
+
+# ------------------------------------------------------------------------------------------------ convolution backward
+# What UNetTrainer's dispatch (_dgrad / _wgrad / _up_bwd / _down_bwd) must compute, from the formulas: with y = conv(x, w) + bias and
+# dy = dL/dy, dW[co][ci][ky][kx] = sum_p x[p * stride + (ky, kx) - pad][ci] dy[p][co], dx[q][ci] = sum_(k, co) dy[(q - k + pad) / stride][co]
+# w[co][ci][k] (terms whose quotient is not a pixel of dy vanish), dbias[co] = sum_p dy[p][co]. Not written with torch.nn.grad.
+def wgrad_ref(src_nhwc, dy_nhwc, ks, mode):
+    """src [B, Hs, Ws, cin], dy [B, Ho, Wo, cout] (the convolution's output grid) -> dW OIHW [cout, cin, ks, ks]: the transposed im2col of
+    the source times the flat gradient. mode as im2col_t: 0 stride 1, 1 nearest 2x then stride 1, 2 stride 2."""
+    B, Ho, Wo, cout = dy_nhwc.shape
+    cin = src_nhwc.shape[-1]
+    P = B * Ho * Wo
+    dw = (im2col_t(src_nhwc, ks, mode, P) @ dy_nhwc.reshape(P, cout)).view(1, ks * ks, cin, cout)
+    return wgrad_to_oihw(dw, cout, cin).view(cout, cin, ks, ks)
+
+
+def dgrad_ref(dy_nhwc, w_oihw):
+    """dy [B, H, W, cout], w OIHW [cout, cin, ks, ks] -> dx [B, H, W, cin] of the stride-1 convolution with padding ks // 2: the stride-1
+    convolution of dy with the flipped, transposed filter, one matmul per tap. Stride 2: dgrad_ref(zero_insert(dy), w); nearest-2x
+    upsample in front of the convolution: sum2x2(dgrad_ref(dy, w))."""
+    B, H, W, cout = dy_nhwc.shape
+    co, cin, ks, _ = w_oihw.shape
+    assert co == cout
+    pad = ks // 2
+    dyp = dy_nhwc.new_zeros((B, H + 2 * pad, W + 2 * pad, cout))
+    dyp[:, pad:pad + H, pad:pad + W] = dy_nhwc
+    acc = None
+    for ky in range(ks):
+        for kx in range(ks):
+            # dx[q] takes w[k] from dy[q - k + pad]: row q - ky + pad of dy is row q - ky + 2 pad of the padded plane
+            patch = dyp[:, 2 * pad - ky:2 * pad - ky + H, 2 * pad - kx:2 * pad - kx + W]
+            t = patch.reshape(-1, cout) @ w_oihw[:, :, ky, kx]
+            acc = t if acc is None else acc + t
+    return acc.view(B, H, W, cin)
+
+
+def bias_ref(dy_nhwc):
+    """the bias gradient: the sum over batch and pixels"""
+    return dy_nhwc.sum((0, 1, 2))
+
+
+def backward_dyadic_ok(K):
+    """proof obligation of a bit-exact backward case on `dyadic` data: values are multiples of 1/8 of magnitude <= 1, products multiples of
+    1/64 of magnitude <= 1, and every fp32 partial sum of K of them is exact in every order while 64 K <= 2^24. dgrad: K = taps * cout;
+    wgrad: K = the total pixel count; + 1 for a prior value of an accumulated output (itself a multiple of 1/8, <= 1)."""
+    assert 64 * K <= 2 ** 24, K
+
+
+# tier-2 data of the dispatch tests, and the shapes of their tier-2 cases (B, H, W of the convolution's INPUT grid, cin -> cout of the forward
+# convolution, ks[, mode]); shared so that the CPU tier holds the bound against fp32 torch on the GPU tier's own shapes and inputs
+def t2_act(shape, seed):
+    """silu(1.3 x + 0.1), x ~ N(0, 1): stands for a normalised + activated activation"""
+    return silu(1.3 * normal(shape, seed, "bwd.act") + 0.1)
+
+
+def t2_grad(shape, seed):
+    return normal(shape, seed, "bwd.dy", std=0.1)
+
+
+def t2_weight(shape_oihw, seed, K):
+    return normal(shape_oihw, seed, "bwd.w", std=1.0 / math.sqrt(K))
+
+
+DGRAD_T2 = {"d_frag_rs": (25, 32, 32, 32, 64, 3), "d_frag_rs_full": (48, 32, 32, 32, 64, 3), "d_frag_lds": (3, 8, 8, 32, 64, 3),
+            "d_frag_lds_declined": (129, 8, 8, 32, 64, 3), "d_m16": (97, 16, 16, 64, 288, 3), "d_m16_small": (2, 8, 8, 128, 256, 3),
+            "d_m16_full": (769, 8, 8, 32, 256, 3), "d_splitk": (2, 8, 8, 64, 1024, 3)}
+DGRAD_T2_PARITY = {"d_parity_frag_lds": (3, 8, 8, 32, 64, 3)}
+WGRAD_T2 = {"w_direct_n": (2, 32, 32, 128, 64, 3, 0), "w_gemm_frag": (2, 8, 8, 64, 96, 3, 0), "w_chunks": (5, 128, 128, 32, 32, 3, 0)}
+WGRAD_T2_PARITY = {"w_parity_nofrag": (2, 8, 8, 64, 96, 3, 0), "w_parity_nofrag_ragged": (3, 10, 10, 64, 96, 3, 0),
+                   "w_parity_mode2": (2, 16, 16, 64, 64, 3, 2)}
+
+
+def case_seed(name):
+    return 100 * sum(ord(ch) for ch in name)
+
+
+def wgrad_out_hw(H, W, mode):
+    return (2 * H, 2 * W) if mode == 1 else ((H // 2, W // 2) if mode == 2 else (H, W))
+
+
+def dgrad_t2_inputs(name, shape):
+    """(dy fp32 [B, H, W, cout], w fp32 OIHW) of a tier-2 dgrad case"""
+    B, H, W, cin, cout, ks = shape
+    s = case_seed(name)
+    return t2_grad((B, H, W, cout), s), t2_weight((cout, cin, ks, ks), s + 1, ks * ks * cout)
+
+
+def wgrad_t2_inputs(name, shape):
+    """(src fp32 [B, H, W, cin], dy fp32 [B, Ho, Wo, cout]) of a tier-2 wgrad case"""
+    B, H, W, cin, cout, ks, mode = shape
+    s = case_seed(name)
+    Ho, Wo = wgrad_out_hw(H, W, mode)
+    return t2_act((B, H, W, cin), s), t2_grad((B, Ho, Wo, cout), s + 1)
 
 
 # ------------------------------------------------------------------------------------------------ SpatialTransformer backward

@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import refs_bwd as R
+from tests import refs_conv as RC
 
 # the GPU test modules switch autograd off at import; the tests below that differentiate switch it on for themselves
 with_grad = torch.enable_grad()
@@ -127,6 +128,98 @@ def test_sum2x2_is_upsample_gradient():
     _close64(R.sum2x2(dy).permute(0, 3, 1, 2), gx)
     prior = R.normal((2, 3, 5, 4), 23, "prior").double()
     _close64(R.sum2x2(dy, prior), R.sum2x2(dy) + prior)
+
+
+# ------------------------------------------------------------------------------------------------ convolution backward references
+def _conv_fwd(x_nhwc, w, mode):
+    xn = x_nhwc.permute(0, 3, 1, 2)
+    if mode == 1:
+        xn = F.interpolate(xn, scale_factor=2, mode="nearest")
+    return F.conv2d(xn, w, None, stride=2 if mode == 2 else 1, padding=w.shape[-1] // 2)
+
+
+@pytest.mark.parametrize("ks,mode", [(1, 0), (3, 0), (3, 1), (3, 2)])
+@pytest.mark.parametrize("B,H,W", [(1, 2, 2), (3, 6, 10), (2, 4, 14)])
+@with_grad
+def test_conv_backward_refs_are_autograd(ks, mode, B, H, W):
+    """wgrad_ref, dgrad_ref (+ zero_insert for stride 2, + sum2x2 behind the nearest-2x upsample) and bias_ref against autograd through
+    F.conv2d, F.interpolate(nearest) + conv2d and conv2d(stride=2, padding=1), in fp64, on ragged small shapes"""
+    cin, cout = 7, 5
+    Ho, Wo = R.wgrad_out_hw(H, W, mode)
+    x = R.normal((B, H, W, cin), 31, "x").double().requires_grad_()
+    w = R.normal((cout, cin, ks, ks), 31, "w").double().requires_grad_()
+    b = R.normal((cout,), 31, "b").double().requires_grad_()
+    dy = R.normal((B, Ho, Wo, cout), 31, "dy").double()
+    y = _conv_fwd(x, w, mode) + b[None, :, None, None]
+    assert tuple(y.shape) == (B, cout, Ho, Wo)
+    gx, gw, gb = torch.autograd.grad((y * dy.permute(0, 3, 1, 2)).sum(), (x, w, b))
+    xd, wd = x.detach(), w.detach()
+    _close64(R.wgrad_ref(xd, dy, ks, mode), gw)
+    _close64(R.bias_ref(dy), gb)
+    if mode == 0:
+        dx = R.dgrad_ref(dy, wd)
+    elif mode == 1:
+        dx = R.sum2x2(R.dgrad_ref(dy, wd))
+    else:
+        dx = R.dgrad_ref(R.zero_insert(dy), wd)
+    _close64(dx, gx)                  # (x is NHWC itself: so is its gradient)
+
+
+def test_backward_dyadic_ok_states_the_exactness_condition():
+    R.backward_dyadic_ok(2 ** 18)
+    with pytest.raises(AssertionError):
+        R.backward_dyadic_ok(2 ** 18 + 1)
+    # at the limit the fp32 sum of K products of magnitude 1 is still exact; every tier-1 case of the GPU file stays below it
+    assert float(torch.tensor(2.0 ** 18, dtype=torch.float32) - 1.0 / 64) != 2.0 ** 18
+    assert float(torch.tensor(2.0 ** 19, dtype=torch.float32) - 1.0 / 64) == 2.0 ** 19
+
+
+def test_dyadic_backward_in_fp32_equals_fp64_bit_for_bit():
+    """the tier-1 argument on the references themselves: on dyadic data the fp32 evaluation of every reference IS the fp64 one"""
+    x, dy, w = R.dyadic((3, 6, 10, 16), 1), R.dyadic((3, 6, 10, 24), 2), R.dyadic((24, 16, 3, 3), 3)
+    R.backward_dyadic_ok(9 * 24); R.backward_dyadic_ok(3 * 6 * 10)
+    assert torch.equal(R.dgrad_ref(dy, w).double(), R.dgrad_ref(dy.double(), w.double()))
+    assert torch.equal(R.wgrad_ref(x, dy, 3, 0).double(), R.wgrad_ref(x.double(), dy.double(), 3, 0))
+    assert torch.equal(R.bias_ref(dy).double(), R.bias_ref(dy.double()))
+    hi, lo = R.split16(x, torch.bfloat16)
+    assert torch.equal(hi.float(), x) and not bool(lo.float().any())           # the 16-bit planes hold the values themselves, lo is zero
+
+
+def _planes64(x32, parity):
+    hi, lo = R.split16(x32, torch.bfloat16)
+    return hi.double(), (lo.double() if parity else None)
+
+
+def _t2_ratio(fn, a, b, parity):
+    """max |fp32 torch - fp64| / (u S) of fn over the rounded planes of (a, b): what the GPU tier asserts of the kernels, here of torch"""
+    ah, al = _planes64(a, parity)
+    bh, bl = _planes64(b, parity)
+    if parity:
+        ref = RC.three_products(ah, al, bh, bl, fn)
+        got = RC.three_products(ah.float(), al.float(), bh.float(), bl.float(), fn).double()
+        S = fn(ah.abs() + al.abs(), bh.abs() + bl.abs())
+    else:
+        ref, got, S = fn(ah, bh), fn(ah.float(), bh.float()).double(), fn(ah.abs(), bh.abs())
+    return float(((got - ref).abs() / (R.U * S)).max())
+
+
+@pytest.mark.parametrize("name", list(R.DGRAD_T2) + list(R.DGRAD_T2_PARITY))
+def test_dgrad_tier2_bound_holds_for_fp32_torch(name):
+    parity = name in R.DGRAD_T2_PARITY
+    dy, w = R.dgrad_t2_inputs(name, (R.DGRAD_T2_PARITY if parity else R.DGRAD_T2)[name])
+    r = _t2_ratio(R.dgrad_ref, dy, w, parity)
+    print(f"fp32 torch {name} max err / (u S) = {r:.3f}")
+    assert r <= RC.G
+
+
+@pytest.mark.parametrize("name", list(R.WGRAD_T2) + list(R.WGRAD_T2_PARITY))
+def test_wgrad_tier2_bound_holds_for_fp32_torch(name):
+    parity = name in R.WGRAD_T2_PARITY
+    shape = (R.WGRAD_T2_PARITY if parity else R.WGRAD_T2)[name]
+    src, dy = R.wgrad_t2_inputs(name, shape)
+    r = _t2_ratio(lambda s_, d_: R.wgrad_ref(s_, d_, shape[5], shape[6]), src, dy, parity)
+    print(f"fp32 torch {name} max err / (u S) = {r:.3f}")
+    assert r <= RC.G
 
 
 def test_chan_sum_fold_and_q_sample_and_l1():

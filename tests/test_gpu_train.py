@@ -699,8 +699,10 @@ def test_attention_backward_vs_autograd(dev, B, T, heads, ch):
 
 def test_unet_backward_reference_native_128_latents_vs_oracle(dev):
     """REF128 (the reference's own configuration: 128x128x3 latents, 6 input / 3 output channels, attention over 1024 tokens): one
-    loss + backward at batch 1 against autograd over the oracle — the general-T attention backward, batch-chunked GEMM weight gradients
-    (W = 128 is outside the direct kernel) and the padded first / last convolutions at full size."""
+    loss + backward at batch 1 against autograd over the oracle — the general-T attention backward, GEMM-form weight gradients (W = 128 is
+    outside the direct kernel) and the padded first / last convolutions at full size. Nothing is batch-chunked here: at B = 1 and 128 x 128
+    the chunk holds 4 samples, so every weight gradient is one chunk and never accumulates (two chunks are reached by w_chunks in
+    tests/test_gpu_bwd_conv_exact.py)."""
     from oracle import train as otrain
     from oracle import unet as ounet
     from stedm_amd.train import UNetTrainer
