@@ -501,7 +501,10 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn_flash_kernel(co
     const float up = first ? fmaxf(mx, -30000.f) : fmaxf(mx, 0.f);
     const float m_new = (float)(T)(m_ref + up);
     const float delta = m_new - m_ref;
-    const float alpha = __builtin_amdgcn_exp2f(-delta * a.c);
+    // (the exponent is positive only on the first tile, where O and l are still zero: kept finite, since 0 * inf = NaN - the input that
+    // needs it: EVERY logit of a query's first 64 keys below -128 / c, i.e. -128 sqrt(ch) / log2(e) in raw q.k units. A clamp and not
+    // `first ? 1 : ..`: the latter moved the ch = 128 form from 3 to 4 spilled registers)
+    const float alpha = __builtin_amdgcn_exp2f(fminf(-delta * a.c, 64.f));
     m_ref = m_new;
     if (h == 0) qa[0] = (T)(-m_new);
     l_run *= alpha;

@@ -241,7 +241,9 @@ __global__ void __launch_bounds__(256, 2) lsa_flash64_mx8_kernel(Mx8Args a) {
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     mx -= kPShift;                                 // (the logits arrive with the + 4 of the byte scale)
     const float delta = first ? fmaxf(mx, -30000.f) : fmaxf(mx, 0.f);
-    const float alpha = __builtin_amdgcn_exp2f(-delta);
+    // (first: O and l are still zero, and a query whose first 64 keys ALL have logits below -128 (log2 units) would make this
+    // exponential inf: 0 * inf = NaN in every output of the row. Not dead code.)
+    const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
     m_ref[qb] += delta;
 #pragma unroll
     for (int e = 0; e < 16; ++e) cinit[qb][e] = kPShift - m_ref[qb];

@@ -779,7 +779,9 @@ __global__ void __launch_bounds__(256, 2) lsa_flash64_kernel(FlashArgs a) {
     const float up = first ? fmaxf(mx, -30000.f) : fmaxf(mx, 0.f);
     const float m_new = (float)(T)(m_ref[qb] + up);
     const float delta = m_new - m_ref[qb];
-    const float alpha = __builtin_amdgcn_exp2f(-delta);
+    // (first: O and l are still zero, and a query whose first 64 keys ALL have logits below -128 (log2 units) would make this
+    // exponential inf: 0 * inf = NaN in every output of the row. Not dead code.)
+    const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
     m_ref[qb] = m_new;
     if (h == 0) qa[qb][0] = (T)(-m_new);
     l_run[qb] *= alpha;

@@ -324,22 +324,16 @@ def test_lsa_flash_mx8_kernel(dev, B, H, T, src16):
     pad = lambda t: torch.cat([t, t.new_zeros(t.shape[0], Tp - T, 64)], 1)
     q, k, v = pad(q * tau), pad(k), pad(v)
 
-    def mx(x):      # x [..., 32] -> (bytes as e4m3 tensor, scale exponents)
-        amax = x.abs().amax(-1)
-        e = torch.where(amax > 0, torch.frexp(amax / 448.0)[1], torch.full_like(amax, -127, dtype=torch.int32)).clamp(-127, 127)
-        y = (x * torch.ldexp(torch.ones_like(amax), -e).unsqueeze(-1)).to(torch.float8_e4m3fn)
-        return y, e
+    from tests.refs_attn import mx, mx_deq as deq, mx_keys      # the format, restated: (e4m3 tensor, scale exponents) per 32 elements
     qb_, qe = mx(q.reshape(B * H, Tp, 2, 32)); kb_, ke = mx(k.reshape(B * H, Tp, 2, 32))
     assert torch.equal(q8.cpu().view(torch.float8_e4m3fn).view(u8), qb_.reshape(B * H, Tp, 64).view(u8)) and torch.equal(qs.cpu().int() - 127, qe.int())
     assert torch.equal(k8.cpu().view(u8), kb_.reshape(B * H, Tp, 64).view(u8)) and torch.equal(ks.cpu().int() - 127, ke.int())
-    j = torch.arange(32)
-    keys = torch.stack([32 * h + ((j & 15) >> 2) * 8 + 4 * (j >> 4) + (j & 3) for h in range(2)])        # [block h][j] -> key inside the tile (position 32 h + j)
+    keys = mx_keys()                                                                                     # [block h][j] -> key inside the tile (position 32 h + j)
     vt = v.reshape(B * H, Tp // 64, 64, 64)[:, :, keys, :]                                               # [bh][kt][h][j][d]
     vb_, ve = mx(vt.permute(0, 1, 2, 4, 3).contiguous())                                                  # blocks [bh][kt][h][d][32]
     want_v8 = vb_.permute(0, 3, 1, 2, 4).reshape(B * H, 64, Tp)                                           # [bh][d][kt*64 + h*32 + j]
     assert torch.equal(v8.cpu().view(u8), want_v8.contiguous().view(u8)) and torch.equal(vs.cpu().int().reshape(B * H, Tp // 64, 2, 64) - 127, ve.int())
     # ---- (ii) attention on the dequantised operands, fp64
-    deq = lambda y, e: (y.double() * torch.ldexp(torch.ones_like(e, dtype=torch.float64), e).unsqueeze(-1))
     qd = deq(qb_, qe).reshape(B * H, Tp, 64)[:, :T]; kd = deq(kb_, ke).reshape(B * H, Tp, 64)[:, :T]
     vd_perm = deq(vb_, ve)                                                                                # [bh][kt][h][d][j]
     vd = torch.zeros(B * H, Tp // 64, 64, 64, dtype=torch.float64)                                        # [bh][kt][key][d]
