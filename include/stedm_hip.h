@@ -391,7 +391,7 @@ int stedm_attn_legacy16(const void* qkv, int qkv_is16, void* out16, int B, int T
  * x, e_c, e_u, noise, x_prev, pred_x0: NCHW fp32 [B][C][H][W]. e_u NULL => no guidance.
  * coefs: DEVICE table [nsteps][4] = {a_t, a_prev, sigma_t, sqrt(1-a_t)}; step_idx: DEVICE int
  * (NULL => row 0) so that a captured graph can be replayed for every step. noise may be NULL
- * (sigma*noise == 0). pred_x0 may be NULL. x_prev may alias x. */
+ * (sigma*noise == 0). pred_x0 may be NULL. x_prev may alias x, element for element (the kernel declares neither __restrict__). */
 int stedm_ddim_step(const float* x, const float* e_c, const float* e_u, const float* noise,
                     const float* coefs, const int32_t* step_idx, float cfg_scale, float rescale_phi,
                     float* x_prev, float* pred_x0, int B, int C, int H, int W, void* stream);
@@ -406,7 +406,8 @@ int stedm_ddim_step(const float* x, const float* e_c, const float* e_u, const fl
  * whenever p > 0, also below p = 2^-17, where the threshold rounds to 0 and every element is kept.
  * draw and the dropout need step_idx and n_iters > 0. With temperature 1, p = 0 and no eps_out / noise_out the result equals
  * stedm_ddim_step fed the same z, bit for bit (both compute sqrt(a_prev) x0 + dir with each product rounded, then fma(sigma, z, .)). eps_out (may be NULL, may alias e_c): the guided eps after the rescale (ddim.py:184).
- * noise_out (may be NULL): the noise term above, what stedm_ddim_quantize_x0 adds. */
+ * noise_out (may be NULL): the noise term above, what stedm_ddim_quantize_x0 adds. x_prev may alias x and eps_out may alias e_c, element
+ * for element; no other operands may overlap. */
 int stedm_ddim_step_ex(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs, const int32_t* step_idx,
                        int n_iters, float cfg_scale, float rescale_phi, int draw, float temperature, float noise_dropout, long first_id,
                        unsigned long long seed, float* x_prev, float* pred_x0, float* eps_out, float* noise_out, int B, int C, int H, int W,
@@ -419,7 +420,7 @@ int stedm_ddim_step_ex(const float* x, const float* e_c, const float* e_u, const
  * x0, the direction term and the noise term are stedm_ddim_step's expressions (both products of sqrt(a_prev) x0 + dir e rounded, the noise
  * added as fma(sigma, z, .)). z: noise [B][C][H][W] (given), or with draw != 0 element e of row first_id + b of stedm_philox_normal with
  * (seed, stream 1 + iteration), iteration = n_iters - 1 - *step_idx, as stedm_ddim_step_ex draws it (needs step_idx and n_iters > 0);
- * neither: no noise term. No temperature, dropout, eps_out or noise_out. pred_x0 may be NULL; x_prev may alias x.
+ * neither: no noise term. No temperature, dropout, eps_out or noise_out. pred_x0 may be NULL; x_prev may alias x, element for element.
  * One workgroup = (sample, chunk of 16 columns): the columns of a sample are independent, so a sample spans ceil(W / 16) workgroups; any
  * W (no W <= 256 limit), any H, C H >= 2 with e_u. A row's result depends on that row's operands and scale alone. */
 int stedm_ddim_step_rows(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,

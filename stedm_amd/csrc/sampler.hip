@@ -1,20 +1,35 @@
 // The sampler kernels: the DDIM update, the step counter helpers, the DPM-Solver++(2M) and PLMS updates, per-sample normal noise, the mask
 // blend and the ancestral DDPM step. (The general DPM-Solver is in dpm.hip.)
 #include <initializer_list>
+#include <type_traits>
 
 #include "common.hpp"
 #include "dropmask.hpp"
+#include "ddim_math.hpp"
 #include "ddpm_math.hpp"
 
 using namespace stedm;
 
 // ------------------------------------------------------------------------------------------------
-// DDIM update + rescaled CFG. One block per sample; thread = (w, part) with part striding (c,h).
-// Template flags (stedm_ddim_step runs <false, false>; stedm_ddim_step_ex picks the others):
-//   DRAW  the step noise z of element e of sample b is drawn here: row first_id + b of stedm_philox_normal, stream 1 + iteration
-//         (iteration = n_iters - 1 - *step_idx), instead of being read from `noise`;
-//   EXT   the reference's temperature and noise dropout (ddim.py:206-208, each product rounded on its own: ((sigma z) T) keep / (1 - p)),
-//         then x_prev = (sqrt(a_prev) x0 + dir) + noise; optional outputs of the guided eps and of that noise term.
+// DDIM update + rescaled CFG (ddim.py:179-210). stedm_ddim_step, stedm_ddim_step_ex and stedm_ddim_step_rows run one kernel,
+// ddim_step_kernel<Form, R, DRAW, EXT>: thread = (col, part); part strides the C H rows of column w, so a thread's sums run over
+// r = part, part + parts, ... and the parts of a column meet in LDS. The rescale statistic of ddim.py:182-183 is a std over (C,H) for
+// every column on its own, so columns are independent and the Form only says how they are laid over workgroups:
+//   DdimScalarForm  one workgroup per sample, 256 / W parts of W columns (W <= 256), the guidance scale a launch argument;
+//   DdimRowsForm    one workgroup per (sample, chunk of 16 columns), 16 parts: any W, ceil(W / 16) workgroups per sample and nothing
+//                   exchanged between them. scales[b] is read here, from device memory: a captured launch replays with whatever the
+//                   array then holds. scales[b] == 1 (or e_u NULL): the reference's unguided branch (ddim.py:170-171), e = e_c; e_u is
+//                   not read and no statistic is computed.
+//   R > 0   a thread's R rows of every operand are held in registers (one round of independent loads);
+//   R == 0  the looped form: three passes over e_c / e_u.
+//   DRAW    the step noise z of element e of sample b is drawn here: row first_id + b of stedm_philox_normal, stream 1 + iteration
+//           (iteration = n_iters - 1 - *step_idx), instead of being read from `noise`;
+//   EXT     the reference's temperature and noise dropout (ddim.py:206-208, each product rounded on its own: ((sigma z) T) keep / (1 - p)),
+//           then x_prev = (sqrt(a_prev) x0 + dir) + noise; optional outputs of the guided eps and of that noise term.
+// Contraction is off and every fusion is spelled out, so a result's bits do not depend on R, DRAW or EXT, nor on the compiler. They do
+// depend on the Form, in the three expressions its k... constants name: each entry keeps the pairing it has always had.
+// x_prev may alias x and eps_out may alias e_c, element for element (the samplers step in place): a thread reads its elements of every
+// operand before it writes them and no other thread touches them, and none of the four is declared __restrict__.
 // ------------------------------------------------------------------------------------------------
 struct DdimEx {
   float* eps_out;            // guided eps after the rescale (ddim.py:184); may alias e_c element for element
@@ -25,11 +40,54 @@ struct DdimEx {
   int drop;                  // noise_dropout > 0 (thr16 may still be 0 for p < 2^-17: then every element is kept, and scaled)
 };
 
-// sqrt(a_prev) x0 + dir e as stedm_ddim_step has always computed it (both products rounded, then the sum; the compiler issued the two
-// products as one packed multiply). Spelled out so that no form of either kernel, and no later compiler, contracts it into an FMA.
-__device__ __forceinline__ float ddim_base_rounded(float sqrt_ap, float x0, float dir_c, float e) {
+struct DdimScalarForm {
+  static constexpr bool kExactR = true;          // R > 0: every thread owns exactly R rows (the host dispatches so), no guard
+  static constexpr bool kFusedCombine = false;   // (e_w ratio) phi and (1 - phi) e_c both rounded, then the sum
+  static constexpr bool kFusedDir = true;        // dir = sqrt(fma(-sigma, sigma, 1 - a_prev))
+  static constexpr bool kSwap01 = true;          // R > 0: the squares of a thread's first two rows enter as fma(d0, d0, d1 d1)
+  float s;
+  __device__ int sample() const { return blockIdx.x; }
+  __device__ int first_col() const { return 0; }
+  __device__ int cols(int W) const { return W; }
+  __device__ int parts(int W) const { return 256 / W; }
+  __device__ bool owns(int w, int part, int W) const { return part < 256 / W; }       // 256 % W threads idle
+  __device__ float scale(int b, const float* e_u, bool& guided) const {
+    guided = e_u != nullptr;
+    return s;
+  }
+};
+
+struct DdimRowsForm {
+  static constexpr int kChunk = 16;              // columns per workgroup: 16 fp32 = the 64-byte segment a quarter-wave reads from one row
+  static constexpr bool kExactR = false;         // R = ceil(C H / 16): the last rows and the columns past W are guarded
+  static constexpr bool kFusedCombine = true;    // fma(e_w ratio, phi, (1 - phi) e_c)
+  static constexpr bool kFusedDir = false;       // dir = sqrt((1 - a_prev) - sigma sigma), the product rounded
+  static constexpr bool kSwap01 = false;
+  const float* scales;       // DEVICE [B]
+  int nchunk;                // ceil(W / kChunk)
+  __device__ int sample() const { return blockIdx.x / nchunk; }
+  __device__ int first_col() const { return (blockIdx.x % nchunk) * kChunk; }
+  __device__ int cols(int) const { return kChunk; }
+  __device__ int parts(int) const { return 256 / kChunk; }
+  __device__ bool owns(int w, int, int W) const { return w < W; }
+  __device__ float scale(int b, const float* e_u, bool& guided) const {
+    const float s = scales[b];
+    guided = e_u != nullptr && s != 1.0f;          // uniform over the workgroup
+    return s;
+  }
+};
+
+__device__ __forceinline__ float ddim_ew(float ec, float eu, float s) {          // e_u + s (e_c - e_u)
 #pragma clang fp contract(off)
-  return sqrt_ap * x0 + dir_c * e;
+  return __builtin_fmaf(s, ec - eu, eu);
+}
+
+template <bool FUSED>
+__device__ __forceinline__ float ddim_guided(float ec, float eu, float s, float ratio, float phi) {
+#pragma clang fp contract(off)
+  const float rescaled = ddim_ew(ec, eu, s) * ratio, keep = (1.0f - phi) * ec;
+  if constexpr (FUSED) return __builtin_fmaf(rescaled, phi, keep);
+  else return rescaled * phi + keep;
 }
 
 __device__ __forceinline__ float ddim_shaped_noise(float xp, float sigma, float z, float temperature, float keep_scale) {
@@ -49,7 +107,7 @@ __device__ __forceinline__ float ddim_add_noise(float xp, float sigma, const flo
   float z = nzv;
   if constexpr (DRAW) z = philox_normal1((uint32_t)e, 1u + iter, ex.seed, sid);
   if constexpr (!EXT) {
-    return __builtin_fmaf(sigma, z, xp);      // what both forms of stedm_ddim_step compile `xp += sigma * noise` to
+    return __builtin_fmaf(sigma, z, xp);
   } else {
     const float ks = !ex.drop ? 1.0f : ddim_drop_keep((uint32_t)e, iter, ex.seed, sid, ex.thr16) ? ex.drop_scale : 0.0f;
     const float out = ddim_shaped_noise(xp, sigma, z, ex.temperature, ks);
@@ -58,198 +116,167 @@ __device__ __forceinline__ float ddim_add_noise(float xp, float sigma, const flo
   }
 }
 
-template <bool DRAW, bool EXT>
-__global__ void __launch_bounds__(256) ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ e_c,
-                                                        const float* __restrict__ e_u, const float* __restrict__ noise,
-                                                        const float* __restrict__ coefs, const int32_t* __restrict__ step_idx,
-                                                        float s, float phi, float* __restrict__ x_prev,
-                                                        float* __restrict__ pred_x0, int C, int H, int W, DdimEx ex) {
+// std_(c,h)(e_c) / std_(c,h)(e_w) of this thread's column (unbiased: torch.std's default, ddim.py:183). each(swap01, f) calls f(e_c, e_u)
+// on the thread's rows in their order, the first two exchanged if swap01. Column totals: the parts' sums added in the order of part.
+template <bool SWAP01, class Each>
+__device__ __forceinline__ float ddim_rescale_ratio(const Each& each, float s, int CH, int parts, int cols, int col) {
+#pragma clang fp contract(off)
   __shared__ float red[2][256];
-  __shared__ float ratio_w[256];
-  const int b = blockIdx.x;
-  const int idx = step_idx ? *step_idx : 0;
-  const float a_t = coefs[idx * 4 + 0], a_prev = coefs[idx * 4 + 1], sigma = coefs[idx * 4 + 2], sq1m = coefs[idx * 4 + 3];
-  const int CH = C * H;
-  const long base = (long)b * CH * W;
-  const int parts = 256 / W;  // W <= 256 checked on host
-  const int w = threadIdx.x % W, part = threadIdx.x / W;
-  const bool active = part < parts;
-
-  if (e_u) {
-    // pass A: means over (c,h) for column w
-    float sc = 0.f, sw = 0.f;
-    if (active)
-      for (int r = part; r < CH; r += parts) {
-        const float ec = e_c[base + (long)r * W + w], eu = e_u[base + (long)r * W + w];
-        sc += ec;
-        sw += eu + s * (ec - eu);
-      }
-    red[0][threadIdx.x] = active ? sc : 0.f;
-    red[1][threadIdx.x] = active ? sw : 0.f;
-    __syncthreads();
-    float mc = 0.f, mw = 0.f;
-    for (int p = 0; p < parts; ++p) {
-      mc += red[0][p * W + w];
-      mw += red[1][p * W + w];
-    }
-    mc /= (float)CH;
-    mw /= (float)CH;
-    __syncthreads();
-    // pass B: centred sums of squares -> unbiased std (torch.std default, ddim.py:183)
-    float qc = 0.f, qw = 0.f;
-    if (active)
-      for (int r = part; r < CH; r += parts) {
-        const float ec = e_c[base + (long)r * W + w], eu = e_u[base + (long)r * W + w];
-        const float ew = eu + s * (ec - eu);
-        qc += (ec - mc) * (ec - mc);
-        qw += (ew - mw) * (ew - mw);
-      }
-    red[0][threadIdx.x] = active ? qc : 0.f;
-    red[1][threadIdx.x] = active ? qw : 0.f;
-    __syncthreads();
-    if (threadIdx.x < W) {
-      float vc = 0.f, vw = 0.f;
-      for (int p = 0; p < parts; ++p) {
-        vc += red[0][p * W + threadIdx.x];
-        vw += red[1][p * W + threadIdx.x];
-      }
-      ratio_w[threadIdx.x] = sqrtf(vc / (float)(CH - 1)) / sqrtf(vw / (float)(CH - 1));
-    }
-    __syncthreads();
+  __shared__ float ratio_s[256];
+  float sc = 0.f, sw = 0.f;
+  each(false, [&](float ec, float eu) {
+    sc += ec;
+    sw += ddim_ew(ec, eu, s);
+  });
+  red[0][threadIdx.x] = sc;
+  red[1][threadIdx.x] = sw;
+  __syncthreads();
+  float mc = 0.f, mw = 0.f;
+  for (int p = 0; p < parts; ++p) {
+    mc += red[0][p * cols + col];
+    mw += red[1][p * cols + col];
   }
-  const float sqrt_at = sqrtf(a_t);
-  const float dir_c = sqrtf(1.0f - a_prev - sigma * sigma);
-  const float sqrt_ap = sqrtf(a_prev);
-  if (active)
-    for (int r = part; r < CH; r += parts) {
-      const long o = base + (long)r * W + w;
-      float e = e_c[o];
-      if (e_u) {
-        const float eu = e_u[o];
-        const float ew = eu + s * (e - eu);
-        e = (ew * ratio_w[w]) * phi + (1.0f - phi) * e;
-      }
-      const float x0 = (x[o] - sq1m * e) / sqrt_at;
-      float xp = ddim_base_rounded(sqrt_ap, x0, dir_c, e);
-      xp = ddim_add_noise<DRAW, EXT>(xp, sigma, noise, (!DRAW && noise) ? noise[o] : 0.0f, o, r * W + w, b, e, ex, idx);
-      x_prev[o] = xp;
-      if (pred_x0) pred_x0[o] = x0;
+  mc /= (float)CH;
+  mw /= (float)CH;
+  __syncthreads();
+  float qc = 0.f, qw = 0.f;
+  each(SWAP01, [&](float ec, float eu) {
+    const float dc = ec - mc, dw = ddim_ew(ec, eu, s) - mw;
+    qc = __builtin_fmaf(dc, dc, qc);
+    qw = __builtin_fmaf(dw, dw, qw);
+  });
+  red[0][threadIdx.x] = qc;
+  red[1][threadIdx.x] = qw;
+  __syncthreads();
+  if (threadIdx.x < cols) {
+    float vc = 0.f, vw = 0.f;
+    for (int p = 0; p < parts; ++p) {
+      vc += red[0][p * cols + threadIdx.x];
+      vw += red[1][p * cols + threadIdx.x];
     }
+    ratio_s[threadIdx.x] = sqrtf(vc / (float)(CH - 1)) / sqrtf(vw / (float)(CH - 1));
+  }
+  __syncthreads();
+  return ratio_s[col];
 }
 
-// The same update with a thread's R = C H / (256 / W) elements of every operand held in registers: one round of independent loads instead of
-// three dependent passes over e_c / e_u (the kernel above is one block per sample, i.e. 64 busy CUs at the bench batch: all latency, 24 us per
-// step). Same operations in the same order as above (the sums run over r = part, part + parts, ...), so the results are the same bits.
-template <int R, bool DRAW, bool EXT>
-__global__ void __launch_bounds__(256) ddim_step_reg_kernel(const float* __restrict__ x, const float* __restrict__ e_c, const float* __restrict__ e_u,
-                                                            const float* __restrict__ noise, const float* __restrict__ coefs,
-                                                            const int32_t* __restrict__ step_idx, float s, float phi, float* __restrict__ x_prev,
-                                                            float* __restrict__ pred_x0, int C, int H, int W, DdimEx ex) {
-  __shared__ float red[2][256];
-  __shared__ float ratio_w[256];
-  const int b = blockIdx.x;
+template <class Form, int R, bool DRAW, bool EXT>
+__global__ void __launch_bounds__(256) ddim_step_kernel(const float* x, const float* e_c, const float* __restrict__ e_u,
+                                                        const float* __restrict__ noise, const float* __restrict__ coefs,
+                                                        const int32_t* __restrict__ step_idx, float phi, float* x_prev,
+                                                        float* __restrict__ pred_x0, int C, int H, int W, Form form, DdimEx ex) {
+#pragma clang fp contract(off)
+  const int cols = form.cols(W), parts = form.parts(W);
+  const int col = threadIdx.x % cols, part = threadIdx.x / cols;
+  const int b = form.sample(), w = form.first_col() + col;
+  const bool mine = form.owns(w, part, W);
   const int idx = step_idx ? *step_idx : 0;
   const float a_t = coefs[idx * 4 + 0], a_prev = coefs[idx * 4 + 1], sigma = coefs[idx * 4 + 2], sq1m = coefs[idx * 4 + 3];
   const int CH = C * H;
   const long base = (long)b * CH * W;
-  const int parts = 256 / W;               // host: 256 % W == 0 and CH == R * parts, every thread active
-  const int w = threadIdx.x % W, part = threadIdx.x / W;
-  float ec[R], eu[R], xv[R], nz[R];
-#pragma unroll
-  for (int j = 0; j < R; ++j) ec[j] = e_c[base + (long)(part + j * parts) * W + w];
-#pragma unroll
-  for (int j = 0; j < R; ++j) xv[j] = x[base + (long)(part + j * parts) * W + w];
-  if (e_u) {
-#pragma unroll
-    for (int j = 0; j < R; ++j) eu[j] = e_u[base + (long)(part + j * parts) * W + w];
-  }
-  if (!DRAW && noise) {
-#pragma unroll
-    for (int j = 0; j < R; ++j) nz[j] = noise[base + (long)(part + j * parts) * W + w];
-  }
-  if (e_u) {
-    float sc = 0.f, sw = 0.f;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      sc += ec[j];
-      sw += eu[j] + s * (ec[j] - eu[j]);
-    }
-    red[0][threadIdx.x] = sc;
-    red[1][threadIdx.x] = sw;
-    __syncthreads();
-    float mc = 0.f, mw = 0.f;
-    for (int p = 0; p < parts; ++p) {
-      mc += red[0][p * W + w];
-      mw += red[1][p * W + w];
-    }
-    mc /= (float)CH;
-    mw /= (float)CH;
-    __syncthreads();
-    float qc = 0.f, qw = 0.f;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const float ew = eu[j] + s * (ec[j] - eu[j]);
-      qc += (ec[j] - mc) * (ec[j] - mc);
-      qw += (ew - mw) * (ew - mw);
-    }
-    red[0][threadIdx.x] = qc;
-    red[1][threadIdx.x] = qw;
-    __syncthreads();
-    if (threadIdx.x < W) {
-      float vc = 0.f, vw = 0.f;
-      for (int p = 0; p < parts; ++p) {
-        vc += red[0][p * W + threadIdx.x];
-        vw += red[1][p * W + threadIdx.x];
-      }
-      ratio_w[threadIdx.x] = sqrtf(vc / (float)(CH - 1)) / sqrtf(vw / (float)(CH - 1));
-    }
-    __syncthreads();
-  }
-  const float sqrt_at = sqrtf(a_t);
-  const float dir_c = sqrtf(1.0f - a_prev - sigma * sigma);
-  const float sqrt_ap = sqrtf(a_prev);
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const long o = base + (long)(part + j * parts) * W + w;
-    float e = ec[j];
-    if (e_u) {
-      const float ew = eu[j] + s * (e - eu[j]);
-      e = (ew * ratio_w[w]) * phi + (1.0f - phi) * e;
-    }
-    const float x0 = (xv[j] - sq1m * e) / sqrt_at;
-    float xp = ddim_base_rounded(sqrt_ap, x0, dir_c, e);
-    xp = ddim_add_noise<DRAW, EXT>(xp, sigma, noise, (!DRAW && noise) ? nz[j] : 0.0f, o, (part + j * parts) * W + w, b, e, ex, idx);
+  bool guided;
+  const float s = form.scale(b, e_u, guided);
+  const bool noisy = !DRAW && noise != nullptr;
+  const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev);
+  const float dir_c = sqrtf(Form::kFusedDir ? __builtin_fmaf(-sigma, sigma, 1.0f - a_prev) : 1.0f - a_prev - sigma * sigma);
+
+  // x_prev / pred_x0 of row r of this thread's column from the operands' values there
+  auto finish = [&](int r, float xv, float ec, float eu, float nzv, float ratio) {
+    const long o = base + (long)r * W + w;
+    const float e = guided ? ddim_guided<Form::kFusedCombine>(ec, eu, s, ratio, phi) : ec;
+    const float x0 = __builtin_fmaf(-sq1m, e, xv) / sqrt_at;
+    const float xp = ddim_add_noise<DRAW, EXT>(ddim_base_rounded(sqrt_ap, x0, dir_c, e), sigma, noise, nzv, o, r * W + w, b, e, ex, idx);
     x_prev[o] = xp;
     if (pred_x0) pred_x0[o] = x0;
+  };
+
+  if constexpr (R > 0) {
+    float ec[R], xv[R], eu[R] = {}, nz[R];      // eu: passed to finish also when unguided, where it is not used
+    bool ok[R];                                 // kept as an array: recomputed at each use, the masks cost 14 VGPRs and spilled SGPRs at R = 24
+#pragma unroll
+    for (int j = 0; j < R; ++j) ok[j] = Form::kExactR || (mine && part + j * parts < CH);
+    auto at = [&](int j) { return base + (long)(part + j * parts) * W + w; };
+#pragma unroll
+    for (int j = 0; j < R; ++j) ec[j] = ok[j] ? e_c[at(j)] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < R; ++j) xv[j] = ok[j] ? x[at(j)] : 0.0f;
+    if (guided) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) eu[j] = ok[j] ? e_u[at(j)] : 0.0f;
+    }
+    if (noisy) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) nz[j] = ok[j] ? noise[at(j)] : 0.0f;
+    }
+    float ratio = 1.0f;
+    if (guided)
+      ratio = ddim_rescale_ratio<Form::kSwap01>([&](bool swap01, auto f) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          const int k = swap01 && j < 2 ? 1 - j : j;
+          if (ok[k]) f(ec[k], eu[k]);
+        }
+      }, s, CH, parts, cols, col);
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+      if (ok[j]) finish(part + j * parts, xv[j], ec[j], eu[j], noisy ? nz[j] : 0.0f, ratio);
+  } else {
+    float ratio = 1.0f;
+    if (guided)
+      ratio = ddim_rescale_ratio<false>([&](bool, auto f) {
+        if (mine)
+          for (int r = part; r < CH; r += parts) f(e_c[base + (long)r * W + w], e_u[base + (long)r * W + w]);
+      }, s, CH, parts, cols, col);
+    if (mine)
+      for (int r = part; r < CH; r += parts) {
+        const long o = base + (long)r * W + w;
+        finish(r, x[o], e_c[o], guided ? e_u[o] : 0.0f, noisy ? noise[o] : 0.0f, ratio);
+      }
   }
 }
 
-template <bool DRAW, bool EXT>
-static void launch_ddim_step(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs, const int32_t* step_idx,
-                             float s, float phi, float* x_prev, float* pred_x0, int B, int C, int H, int W, const DdimEx& ex, hipStream_t st) {
-  const int parts = 256 / W;
-  const bool reg = 256 % W == 0 && (C * H) % parts == 0;
-  const int per = reg ? C * H / parts : 0;
-#define DDIM_REG(RR) ddim_step_reg_kernel<RR, DRAW, EXT><<<B, 256, 0, st>>>(x, e_c, e_u, noise, coefs, step_idx, s, phi, x_prev, pred_x0, C, H, W, ex)
-  if (per == 16) DDIM_REG(16);          // 32 x 32 x 4 latents (the bench's)
-  else if (per == 4) DDIM_REG(4);       // 16 x 16 x 4
-  else if (per == 8) DDIM_REG(8);
-  else ddim_step_kernel<DRAW, EXT><<<B, 256, 0, st>>>(x, e_c, e_u, noise, coefs, step_idx, s, phi, x_prev, pred_x0, C, H, W, ex);
-#undef DDIM_REG
+struct DdimOperands {      // host side: what the three entries hand to the launch
+  const float *x, *e_c, *e_u, *noise, *coefs;
+  const int32_t* step_idx;
+  float phi;
+  float *x_prev, *pred_x0;
+  int C, H, W;
+};
+
+// launches the instantiation with R rows per thread; Rs lists the ones the entry's dispatch can select
+template <class Form, bool DRAW, bool EXT, int... Rs>
+static void launch_ddim_step(int R, unsigned grid, const Form& form, const DdimOperands& a, const DdimEx& ex, hipStream_t st) {
+  auto go = [&](auto r) {
+    ddim_step_kernel<Form, decltype(r)::value, DRAW, EXT><<<grid, 256, 0, st>>>(a.x, a.e_c, a.e_u, a.noise, a.coefs, a.step_idx, a.phi, a.x_prev,
+                                                                                a.pred_x0, a.C, a.H, a.W, form, ex);
+    return true;
+  };
+  (void)((R == Rs && go(std::integral_constant<int, Rs>{})) || ...);
 }
 
+// scalar entries: registers when the 256 threads tile the sample exactly with 16 (32 x 32 x 4, the bench's latents), 4 (16 x 16 x 4) or 8
+// rows each, looped otherwise
+template <bool DRAW, bool EXT>
+static void launch_ddim_scalar(float s, int B, const DdimOperands& a, const DdimEx& ex, hipStream_t st) {
+  const int parts = 256 / a.W, CH = a.C * a.H;
+  const int per = 256 % a.W == 0 && CH % parts == 0 ? CH / parts : 0;
+  launch_ddim_step<DdimScalarForm, DRAW, EXT, 0, 4, 8, 16>(per == 16 || per == 4 || per == 8 ? per : 0, (unsigned)B, DdimScalarForm{s}, a, ex, st);
+}
+
+// x_prev may alias x, element for element (and, in _ex, eps_out may alias e_c)
 extern "C" int stedm_ddim_step(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
                                const int32_t* step_idx, float cfg_scale, float rescale_phi, float* x_prev, float* pred_x0,
                                int B, int C, int H, int W, void* stream) {
   STEDM_CHECK_ARG(x && e_c && coefs && x_prev, "ddim_step: null pointer");
   STEDM_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && W <= 256, "ddim_step: bad shape B=%d C=%d H=%d W=%d (W <= 256)", B, C, H, W);
   STEDM_CHECK_ARG(!e_u || C * H > 1, "ddim_step: std over (C,H) needs C*H > 1");
-  launch_ddim_step<false, false>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, DdimEx{},
-                                 as_stream(stream));
+  launch_ddim_scalar<false, false>(cfg_scale, B, {x, e_c, e_u, noise, coefs, step_idx, rescale_phi, x_prev, pred_x0, C, H, W}, DdimEx{},
+                                   as_stream(stream));
   STEDM_LAUNCH_CHECK();
   return 0;
 }
 
+// x_prev may alias x and eps_out may alias e_c, element for element
 extern "C" int stedm_ddim_step_ex(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
                                   const int32_t* step_idx, int n_iters, float cfg_scale, float rescale_phi, int draw, float temperature,
                                   float noise_dropout, long first_id, unsigned long long seed, float* x_prev, float* pred_x0, float* eps_out,
@@ -264,227 +291,26 @@ extern "C" int stedm_ddim_step_ex(const float* x, const float* e_c, const float*
   STEDM_CHECK_ARG(!((draw || drop) && !step_idx), "ddim_step_ex: the in-kernel draw and the dropout need the device step index");
   STEDM_CHECK_ARG(!((draw || drop) && n_iters <= 0), "ddim_step_ex: the in-kernel draw and the dropout need n_iters > 0 (got %d)", n_iters);
   STEDM_CHECK_ARG(first_id >= 0 && first_id + B <= (1L << 32), "ddim_step_ex: sample ids %ld + %d outside [0, 2^32]", first_id, B);
-  DdimEx ex{eps_out, noise_out, temperature, (float)(1.0 / (1.0 - (double)noise_dropout)), thr, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)first_id, n_iters,
-           drop ? 1 : 0};
+  const DdimEx ex{eps_out, noise_out, temperature, (float)(1.0 / (1.0 - (double)noise_dropout)), thr, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)first_id,
+                 n_iters, drop ? 1 : 0};
+  const DdimOperands a{x, e_c, e_u, noise, coefs, step_idx, rescale_phi, x_prev, pred_x0, C, H, W};
   const bool ext = temperature != 1.0f || drop || eps_out || noise_out;
   hipStream_t st = as_stream(stream);
-  if (draw && ext) launch_ddim_step<true, true>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, ex, st);
-  else if (draw) launch_ddim_step<true, false>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, ex, st);
-  else if (ext) launch_ddim_step<false, true>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, ex, st);
-  else launch_ddim_step<false, false>(x, e_c, e_u, noise, coefs, step_idx, cfg_scale, rescale_phi, x_prev, pred_x0, B, C, H, W, ex, st);
+  if (draw && ext) launch_ddim_scalar<true, true>(cfg_scale, B, a, ex, st);
+  else if (draw) launch_ddim_scalar<true, false>(cfg_scale, B, a, ex, st);
+  else if (ext) launch_ddim_scalar<false, true>(cfg_scale, B, a, ex, st);
+  else launch_ddim_scalar<false, false>(cfg_scale, B, a, ex, st);
   STEDM_LAUNCH_CHECK();
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// DDIM update with one guidance scale per sample (stedm_ddim_step_rows). The rescale statistic of ddim.py:182-183 is a std over (C,H) for
-// every column w on its own, so a sample's columns are independent: one workgroup = (sample b, chunk of ROWS_CHUNK columns), a sample
-// spans ceil(W / ROWS_CHUNK) workgroups and nothing is exchanged between them. thread = (col = tid % 16, part = tid / 16); part strides
-// the C H rows, so a wave reads four rows' 64-byte segments per load and a thread's sums run over r = part, part + 16, ...; the 16 parts
-// of a column meet in LDS. scales[b] is read here, from device memory: a captured launch replays with whatever the array then holds.
-// scales[b] == 1 (or e_u NULL): the reference's unguided branch (ddim.py:170-171), e = e_c; e_u is not read and no statistic is computed.
-//   R > 0   a thread's R = ceil(C H / 16) elements of every operand are held in registers (one round of independent loads);
-//   R == 0  the looped form for C H > 16 * 24: three passes over e_c / e_u.
-// x_prev may alias x: a thread reads its elements of x before it writes them, and no other thread touches them.
-// ------------------------------------------------------------------------------------------------
-constexpr int ROWS_CHUNK = 16;                   // columns per workgroup: 16 fp32 = the 64-byte segment a quarter-wave reads from one row
-constexpr int ROWS_PARTS = 256 / ROWS_CHUNK;     // row strides per workgroup
-
-struct DdimRows {
-  const float* scales;       // DEVICE [B]
-  uint32_t seed, id0;
-  int n_iters;
-  int nchunk;                // ceil(W / ROWS_CHUNK)
-};
-
-// The fusions are spelled out and contraction is off in everything below: left to the compiler, the pairing of products and sums into
-// FMAs differed between the instantiations, and a row's bits must not depend on the variant that computes it.
-__device__ __forceinline__ float ddim_rows_ew(float ec, float eu, float s) {          // e_u + s (e_c - e_u)
-#pragma clang fp contract(off)
-  return __builtin_fmaf(s, ec - eu, eu);
-}
-
-__device__ __forceinline__ float ddim_rows_guided(float ec, float eu, float s, float ratio, float phi) {
-#pragma clang fp contract(off)
-  return __builtin_fmaf(ddim_rows_ew(ec, eu, s) * ratio, phi, (1.0f - phi) * ec);
-}
-
-// x_prev / pred_x0 of one element from its (guided) eps: ddim_step_kernel's expressions
+// One guidance scale per sample (DdimRowsForm). x_prev may alias x, element for element.
 template <bool DRAW>
-__device__ __forceinline__ void ddim_rows_finish(float xv, float e, float nzv, bool noisy, float sq1m, float sqrt_at, float sqrt_ap, float dir_c,
-                                                 float sigma, uint32_t el, uint32_t stream, uint32_t seed, uint32_t sid, long o,
-                                                 float* x_prev, float* pred_x0) {
-#pragma clang fp contract(off)
-  const float x0 = __builtin_fmaf(-sq1m, e, xv) / sqrt_at;
-  float xp = ddim_base_rounded(sqrt_ap, x0, dir_c, e);
-  if constexpr (DRAW) xp = __builtin_fmaf(sigma, philox_normal1(el, stream, seed, sid), xp);
-  else if (noisy) xp = __builtin_fmaf(sigma, nzv, xp);
-  x_prev[o] = xp;
-  if (pred_x0) pred_x0[o] = x0;
-}
-
-template <int R, bool DRAW>
-__global__ void __launch_bounds__(256) ddim_step_rows_kernel(const float* x, const float* __restrict__ e_c, const float* __restrict__ e_u,
-                                                             const float* __restrict__ noise, const float* __restrict__ coefs,
-                                                             const int32_t* __restrict__ step_idx, float phi, float* x_prev,
-                                                             float* __restrict__ pred_x0, int C, int H, int W, DdimRows rw) {
-#pragma clang fp contract(off)
-  __shared__ float red[2][256];
-  __shared__ float ratio_s[ROWS_CHUNK];
-  const int b = blockIdx.x / rw.nchunk, chunk = blockIdx.x - b * rw.nchunk;
-  const int col = threadIdx.x % ROWS_CHUNK, part = threadIdx.x / ROWS_CHUNK;
-  const int w = chunk * ROWS_CHUNK + col;
-  const bool in_w = w < W;
-  const int idx = step_idx ? *step_idx : 0;
-  const float a_t = coefs[idx * 4 + 0], a_prev = coefs[idx * 4 + 1], sigma = coefs[idx * 4 + 2], sq1m = coefs[idx * 4 + 3];
-  const int CH = C * H;
-  const long base = (long)b * CH * W;
-  const float s = rw.scales[b];
-  const bool guided = e_u != nullptr && s != 1.0f;      // uniform over the workgroup
-  const bool noisy = !DRAW && noise != nullptr;
-  const uint32_t stream = 1u + (uint32_t)(rw.n_iters - 1 - idx), sid = rw.id0 + (uint32_t)b;
-  const float sqrt_at = sqrtf(a_t);
-  const float dir_c = sqrtf(1.0f - a_prev - sigma * sigma);
-  const float sqrt_ap = sqrtf(a_prev);
-
-  if constexpr (R > 0) {
-    float ec[R], eu[R], xv[R], nz[R];
-    bool ok[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) ok[j] = in_w && part + j * ROWS_PARTS < CH;
-#pragma unroll
-    for (int j = 0; j < R; ++j) ec[j] = ok[j] ? e_c[base + (long)(part + j * ROWS_PARTS) * W + w] : 0.0f;
-#pragma unroll
-    for (int j = 0; j < R; ++j) xv[j] = ok[j] ? x[base + (long)(part + j * ROWS_PARTS) * W + w] : 0.0f;
-    if (guided) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) eu[j] = ok[j] ? e_u[base + (long)(part + j * ROWS_PARTS) * W + w] : 0.0f;
-    }
-    if (noisy) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) nz[j] = ok[j] ? noise[base + (long)(part + j * ROWS_PARTS) * W + w] : 0.0f;
-    }
-    float ratio = 1.0f;
-    if (guided) {
-      // means over (c,h) of column w, then centred sums of squares -> unbiased std (torch.std default, ddim.py:183)
-      float sc = 0.f, sw = 0.f;
-#pragma unroll
-      for (int j = 0; j < R; ++j)
-        if (ok[j]) {
-          sc += ec[j];
-          sw += ddim_rows_ew(ec[j], eu[j], s);
-        }
-      red[0][threadIdx.x] = sc;
-      red[1][threadIdx.x] = sw;
-      __syncthreads();
-      float mc = 0.f, mw = 0.f;
-#pragma unroll
-      for (int p = 0; p < ROWS_PARTS; ++p) {
-        mc += red[0][p * ROWS_CHUNK + col];
-        mw += red[1][p * ROWS_CHUNK + col];
-      }
-      mc /= (float)CH;
-      mw /= (float)CH;
-      __syncthreads();
-      float qc = 0.f, qw = 0.f;
-#pragma unroll
-      for (int j = 0; j < R; ++j)
-        if (ok[j]) {
-          const float dc = ec[j] - mc, dw = ddim_rows_ew(ec[j], eu[j], s) - mw;
-          qc = __builtin_fmaf(dc, dc, qc);
-          qw = __builtin_fmaf(dw, dw, qw);
-        }
-      red[0][threadIdx.x] = qc;
-      red[1][threadIdx.x] = qw;
-      __syncthreads();
-      if (threadIdx.x < ROWS_CHUNK) {
-        float vc = 0.f, vw = 0.f;
-#pragma unroll
-        for (int p = 0; p < ROWS_PARTS; ++p) {
-          vc += red[0][p * ROWS_CHUNK + threadIdx.x];
-          vw += red[1][p * ROWS_CHUNK + threadIdx.x];
-        }
-        ratio_s[threadIdx.x] = sqrtf(vc / (float)(CH - 1)) / sqrtf(vw / (float)(CH - 1));
-      }
-      __syncthreads();
-      ratio = ratio_s[col];
-    }
-#pragma unroll
-    for (int j = 0; j < R; ++j)
-      if (ok[j]) {
-        const int r = part + j * ROWS_PARTS;
-        const float e = guided ? ddim_rows_guided(ec[j], eu[j], s, ratio, phi) : ec[j];
-        ddim_rows_finish<DRAW>(xv[j], e, noisy ? nz[j] : 0.0f, noisy, sq1m, sqrt_at, sqrt_ap, dir_c, sigma, (uint32_t)(r * W + w), stream,
-                               rw.seed, sid, base + (long)r * W + w, x_prev, pred_x0);
-      }
-  } else {
-    float ratio = 1.0f;
-    if (guided) {
-      float sc = 0.f, sw = 0.f;
-      if (in_w)
-        for (int r = part; r < CH; r += ROWS_PARTS) {
-          const float ec = e_c[base + (long)r * W + w], eu = e_u[base + (long)r * W + w];
-          sc += ec;
-          sw += ddim_rows_ew(ec, eu, s);
-        }
-      red[0][threadIdx.x] = sc;
-      red[1][threadIdx.x] = sw;
-      __syncthreads();
-      float mc = 0.f, mw = 0.f;
-      for (int p = 0; p < ROWS_PARTS; ++p) {
-        mc += red[0][p * ROWS_CHUNK + col];
-        mw += red[1][p * ROWS_CHUNK + col];
-      }
-      mc /= (float)CH;
-      mw /= (float)CH;
-      __syncthreads();
-      float qc = 0.f, qw = 0.f;
-      if (in_w)
-        for (int r = part; r < CH; r += ROWS_PARTS) {
-          const float ec = e_c[base + (long)r * W + w], eu = e_u[base + (long)r * W + w];
-          const float dc = ec - mc, dw = ddim_rows_ew(ec, eu, s) - mw;
-          qc = __builtin_fmaf(dc, dc, qc);
-          qw = __builtin_fmaf(dw, dw, qw);
-        }
-      red[0][threadIdx.x] = qc;
-      red[1][threadIdx.x] = qw;
-      __syncthreads();
-      if (threadIdx.x < ROWS_CHUNK) {
-        float vc = 0.f, vw = 0.f;
-        for (int p = 0; p < ROWS_PARTS; ++p) {
-          vc += red[0][p * ROWS_CHUNK + threadIdx.x];
-          vw += red[1][p * ROWS_CHUNK + threadIdx.x];
-        }
-        ratio_s[threadIdx.x] = sqrtf(vc / (float)(CH - 1)) / sqrtf(vw / (float)(CH - 1));
-      }
-      __syncthreads();
-      ratio = ratio_s[col];
-    }
-    if (in_w)
-      for (int r = part; r < CH; r += ROWS_PARTS) {
-        const long o = base + (long)r * W + w;
-        const float ec = e_c[o];
-        const float e = guided ? ddim_rows_guided(ec, e_u[o], s, ratio, phi) : ec;
-        ddim_rows_finish<DRAW>(x[o], e, noisy ? noise[o] : 0.0f, noisy, sq1m, sqrt_at, sqrt_ap, dir_c, sigma, (uint32_t)(r * W + w), stream,
-                               rw.seed, sid, o, x_prev, pred_x0);
-      }
-  }
-}
-
-template <bool DRAW>
-static void launch_ddim_step_rows(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
-                                  const int32_t* step_idx, float phi, float* x_prev, float* pred_x0, int B, int C, int H, int W,
-                                  const DdimRows& rw, hipStream_t st) {
-  const int per = (C * H + ROWS_PARTS - 1) / ROWS_PARTS;      // a thread's elements
-  const unsigned grid = (unsigned)((long)B * rw.nchunk);
-#define DDIM_ROWS(RR) ddim_step_rows_kernel<RR, DRAW><<<grid, 256, 0, st>>>(x, e_c, e_u, noise, coefs, step_idx, phi, x_prev, pred_x0, C, H, W, rw)
-  if (per <= 2) DDIM_ROWS(2);            // 8 x 8 x 4 and smaller
-  else if (per <= 4) DDIM_ROWS(4);       // 16 x 16 x 4
-  else if (per <= 8) DDIM_ROWS(8);       // 32 x 32 x 4 (the bench's latents)
-  else if (per <= 16) DDIM_ROWS(16);     // 64 x 64 x 4
-  else if (per <= 24) DDIM_ROWS(24);     // 128 x 128 x 3 (the reference's native latents)
-  else DDIM_ROWS(0);
-#undef DDIM_ROWS
+static void launch_ddim_rows(const DdimRowsForm& form, int B, const DdimOperands& a, const DdimEx& ex, hipStream_t st) {
+  const int per = (a.C * a.H + 15) / 16;      // a thread's rows
+  // 2: 8 x 8 x 4 and smaller; 4: 16 x 16 x 4; 8: 32 x 32 x 4 (the bench's latents); 16: 64 x 64 x 4; 24: 128 x 128 x 3 (the reference's native latents)
+  const int R = per <= 2 ? 2 : per <= 4 ? 4 : per <= 8 ? 8 : per <= 16 ? 16 : per <= 24 ? 24 : 0;
+  launch_ddim_step<DdimRowsForm, DRAW, false, 0, 2, 4, 8, 16, 24>(R, (unsigned)((long)B * form.nchunk), form, a, ex, st);
 }
 
 extern "C" int stedm_ddim_step_rows(const float* x, const float* e_c, const float* e_u, const float* noise, const float* coefs,
@@ -498,12 +324,13 @@ extern "C" int stedm_ddim_step_rows(const float* x, const float* e_c, const floa
   STEDM_CHECK_ARG(!(draw && !step_idx), "ddim_step_rows: the in-kernel draw needs the device step index");
   STEDM_CHECK_ARG(!(draw && n_iters <= 0), "ddim_step_rows: the in-kernel draw needs n_iters > 0 (got %d)", n_iters);
   STEDM_CHECK_ARG(first_id >= 0 && first_id + B <= (1L << 32), "ddim_step_rows: sample ids %ld + %d outside [0, 2^32]", first_id, B);
-  const int nchunk = (W + ROWS_CHUNK - 1) / ROWS_CHUNK;
+  const int nchunk = (W + DdimRowsForm::kChunk - 1) / DdimRowsForm::kChunk;
   STEDM_CHECK_ARG((long)B * nchunk <= 0x7FFFFFFFL, "ddim_step_rows: %d samples of %d column chunks exceed one launch", B, nchunk);
-  const DdimRows rw{scales, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)first_id, n_iters, nchunk};
-  hipStream_t st = as_stream(stream);
-  if (draw) launch_ddim_step_rows<true>(x, e_c, e_u, noise, coefs, step_idx, rescale_phi, x_prev, pred_x0, B, C, H, W, rw, st);
-  else launch_ddim_step_rows<false>(x, e_c, e_u, noise, coefs, step_idx, rescale_phi, x_prev, pred_x0, B, C, H, W, rw, st);
+  const DdimRowsForm form{scales, nchunk};
+  const DdimEx ex{nullptr, nullptr, 1.0f, 1.0f, 0u, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)first_id, n_iters, 0};
+  const DdimOperands a{x, e_c, e_u, noise, coefs, step_idx, rescale_phi, x_prev, pred_x0, C, H, W};
+  if (draw) launch_ddim_rows<true>(form, B, a, ex, as_stream(stream));
+  else launch_ddim_rows<false>(form, B, a, ex, as_stream(stream));
   STEDM_LAUNCH_CHECK();
   return 0;
 }

@@ -12,6 +12,7 @@
 //   nearest-codebook arithmetic is written WITHOUT fused multiply-adds and in a fixed order (the index is an integer
 //   result and must not depend on contraction choices of the compiler)
 #include "common.hpp"
+#include "ddim_math.hpp"
 #include "ddpm_math.hpp"
 using namespace stedm;
 
@@ -26,11 +27,6 @@ __device__ __forceinline__ float vq_straight_through(float z, float e) {
 __device__ __forceinline__ float vq_add_rounded(float a, float b) {
 #pragma clang fp contract(off)
   return a + b;
-}
-// sqrt(a_prev) x0 + dir e with both products rounded, then the sum: the update kernel's form (ddim_base_rounded in sampler.hip)
-__device__ __forceinline__ float vq_ddim_base(float sqrt_ap, float x0, float dir_c, float e) {
-#pragma clang fp contract(off)
-  return sqrt_ap * x0 + dir_c * e;
 }
 
 constexpr int VQ_TILE = 1024;   // codebook entries staged in LDS at a time (+ their squared norms)
@@ -129,7 +125,7 @@ __global__ void __launch_bounds__(256) ddim_quantize_kernel(float* __restrict__ 
     const long o = (b * E + c) * HW + hw;
     const float q = vq_straight_through(zv[c], cb[(long)bi * E + c]);
     pred_x0[o] = q;
-    const float xp = vq_ddim_base(sqrt_ap, q, dir_c, eps[o]);
+    const float xp = ddim_base_rounded(sqrt_ap, q, dir_c, eps[o]);
     x_prev[o] = noise ? vq_add_rounded(xp, noise[o]) : xp;
   }
 }

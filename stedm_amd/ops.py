@@ -1056,17 +1056,36 @@ def philox_normal(rows: int, shape, seed: int, stream: int, device, sample_ids: 
 
 
 # ------------------------------------------------------------------------------------------- DDIM
+def _ddim_step_args(x, e_c, step_idx, noise, draw, same_shape):
+    """The checks ddim_step, ddim_step_ex and ddim_step_rows share: x [B, C, H, W] fp32 on the device; e_c, noise and every given tensor
+    of same_shape ((tensor, name) pairs) of x's shape; a given noise excludes the in-kernel draw; step_idx (when given) int32.
+    -> (B, C, H, W)."""
+    _chk(x, name="x")
+    _chk(e_c, name="e_c")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, C, H, W], got {tuple(x.shape)}")
+    shp = tuple(x.shape)
+    for t, nm in (((e_c, "e_c"), (noise, "noise")) + same_shape):
+        if t is not None:
+            _chk(t, name=nm)
+            if tuple(t.shape) != shp:
+                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {shp}")
+    if draw and noise is not None:
+        raise ValueError("a given noise tensor and the in-kernel draw exclude each other")
+    if step_idx is not None:
+        _chk(step_idx, torch.int32, "step_idx")
+    return shp
+
+
 def ddim_step(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], coefs: torch.Tensor, x_prev: torch.Tensor,
               pred_x0: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
               step_idx: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, rescale_phi: float = 0.7) -> torch.Tensor:
-    _chk(x, name="x")
-    _chk(e_c, name="e_c")
-    B, Cc, H, W = x.shape
+    """One DDIM update with the rescaled classifier-free combine (stedm_ddim_step). x_prev may be x."""
+    B, Cc, H, W = _ddim_step_args(x, e_c, step_idx, noise, False, ((e_u, "e_u"), (x_prev, "x_prev"), (pred_x0, "pred_x0")))
     check(lib().stedm_ddim_step(x.data_ptr(), e_c.data_ptr(), _ptr(e_u), _ptr(noise), coefs.data_ptr(), _ptr(step_idx),
                                 float(cfg_scale), float(rescale_phi), x_prev.data_ptr(), _ptr(pred_x0), B, Cc, H, W, _stream()),
           "stedm_ddim_step")
     return x_prev
-
 
 
 def ddim_step_ex(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor], coefs: torch.Tensor, x_prev: torch.Tensor,
@@ -1077,25 +1096,13 @@ def ddim_step_ex(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tensor]
     """ddim_step with the reference's temperature and noise dropout (stedm_ddim_step_ex): noise = ((sigma z) temperature) keep / (1 - p),
     x_prev = (sqrt(a_prev) x0 + dir) + noise. z: `noise`, or with draw=True row first_id + b of ops.philox_normal(seed, stream
     1 + n_iters - 1 - step_idx[0]) drawn in the kernel. The keep bits come from (seed, first_id + b, iteration); see include/stedm_hip.h.
-    eps_out: the guided eps (may be e_c); noise_out: the noise term (both [B, C, H, W] fp32)."""
-    _chk(x, name="x")
-    _chk(e_c, name="e_c")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [B, C, H, W], got {tuple(x.shape)}")
-    B, Cc, H, W = x.shape
-    for t, nm in ((e_u, "e_u"), (noise, "noise"), (x_prev, "x_prev"), (pred_x0, "pred_x0"), (eps_out, "eps_out"), (noise_out, "noise_out")):
-        if t is not None:
-            _chk(t, name=nm)
-            if tuple(t.shape) != tuple(x.shape):
-                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {tuple(x.shape)}")
-    if draw and noise is not None:
-        raise ValueError("a given noise tensor and the in-kernel draw exclude each other")
+    eps_out: the guided eps (may be e_c); noise_out: the noise term (both [B, C, H, W] fp32). x_prev may be x."""
+    B, Cc, H, W = _ddim_step_args(x, e_c, step_idx, noise, draw, ((e_u, "e_u"), (x_prev, "x_prev"), (pred_x0, "pred_x0"),
+                                                                  (eps_out, "eps_out"), (noise_out, "noise_out")))
     if not 0.0 <= float(noise_dropout) < 1.0:
         raise ValueError(f"noise_dropout {noise_dropout} outside [0, 1)")
     if (draw or noise_dropout > 0) and (step_idx is None or int(n_iters) <= 0):
         raise ValueError("the in-kernel draw and the noise dropout need step_idx (device int32) and n_iters > 0")
-    if step_idx is not None:
-        _chk(step_idx, torch.int32, "step_idx")
     check(lib().stedm_ddim_step_ex(x.data_ptr(), e_c.data_ptr(), _ptr(e_u), _ptr(noise), coefs.data_ptr(), _ptr(step_idx), int(n_iters),
                                    float(cfg_scale), float(rescale_phi), 1 if draw else 0, float(temperature), float(noise_dropout),
                                    int(first_id), int(seed) & 0xFFFFFFFFFFFFFFFF, x_prev.data_ptr(), _ptr(pred_x0), _ptr(eps_out),
@@ -1111,25 +1118,12 @@ def ddim_step_rows(x: torch.Tensor, e_c: torch.Tensor, e_u: Optional[torch.Tenso
     a captured launch replays with what the tensor then holds. Row b with scales[b] == 1 takes the unguided branch (e = e_c) and does
     not read e_u. z: `noise`, or with draw=True row first_id + b of ops.philox_normal(seed, stream 1 + n_iters - 1 - step_idx[0]) drawn in
     the kernel; neither: no noise term. Any W and H (a sample spans ceil(W / 16) workgroups); x_prev may be x."""
-    _chk(x, name="x")
-    _chk(e_c, name="e_c")
-    if x.dim() != 4:
-        raise ValueError(f"x must be [B, C, H, W], got {tuple(x.shape)}")
-    B, Cc, H, W = x.shape
-    for t, nm in ((e_c, "e_c"), (e_u, "e_u"), (noise, "noise"), (x_prev, "x_prev"), (pred_x0, "pred_x0")):
-        if t is not None:
-            _chk(t, name=nm)
-            if tuple(t.shape) != tuple(x.shape):
-                raise ValueError(f"{nm} {tuple(t.shape)} must have x's shape {tuple(x.shape)}")
+    B, Cc, H, W = _ddim_step_args(x, e_c, step_idx, noise, draw, ((e_u, "e_u"), (x_prev, "x_prev"), (pred_x0, "pred_x0")))
     _chk(scales, name="scales")
     if tuple(scales.shape) != (B,):
         raise ValueError(f"scales {tuple(scales.shape)} must be [{B}]")
-    if draw and noise is not None:
-        raise ValueError("a given noise tensor and the in-kernel draw exclude each other")
     if draw and (step_idx is None or int(n_iters) <= 0):
         raise ValueError("the in-kernel draw needs step_idx (device int32) and n_iters > 0")
-    if step_idx is not None:
-        _chk(step_idx, torch.int32, "step_idx")
     check(lib().stedm_ddim_step_rows(x.data_ptr(), e_c.data_ptr(), _ptr(e_u), _ptr(noise), coefs.data_ptr(), _ptr(step_idx), int(n_iters),
                                      scales.data_ptr(), float(rescale_phi), 1 if draw else 0, int(first_id),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, x_prev.data_ptr(), _ptr(pred_x0), B, Cc, H, W, _stream()),

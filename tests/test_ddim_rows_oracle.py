@@ -184,9 +184,10 @@ def test_refusals_with_per_sample_scales_raise_before_any_op(recorded):
 
 # ------------------------------------------------------------------------------------------------ the built kernel
 def test_ddim_step_rows_variants_have_no_register_spills():
-    """The code-object notes of sampler.o (the way tests/test_abi.py reads them): every stedm_ddim_step_rows variant - the register forms
-    up to the 24 elements a thread holds at the native 3 x 128 x 128 latent, the looped form, each with and without the in-kernel draw -
-    keeps `.vgpr_spill_count` and `.sgpr_spill_count` 0."""
+    """The code-object notes of sampler.o (the way tests/test_abi.py reads them): every instantiation of ddim_step_kernel - for
+    stedm_ddim_step_rows (DdimRowsForm) the register forms up to the 24 elements a thread holds at the native 3 x 128 x 128 latent and the
+    looped form, each with and without the in-kernel draw; and every form of the scalar entries - keeps `.vgpr_spill_count` and
+    `.sgpr_spill_count` 0."""
     from stedm_amd import build
     build.build(verbose=False)
     objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
@@ -205,11 +206,12 @@ def test_ddim_step_rows_variants_have_no_register_spills():
         if m:
             kname = m.group(1)
         m = re.match(r"\s+\.(vgpr|sgpr)_spill_count:\s+(\d+)", ln)
-        if m and kname and "ddim_step_rows" in kname:
+        if m and kname and "ddim_step_kernel" in kname:
             seen.add(kname)
             assert int(m.group(2)) == 0, f"{kname} spills {m.group(2)} {m.group(1)}s"
-    assert len(seen) >= 1, "no ddim_step_rows kernel found in the code object"
-    assert any("ILi24E" in k for k in seen) and any("ILi0E" in k for k in seen), sorted(seen)
+    rows = {k for k in seen if "DdimRowsForm" in k}
+    assert len(rows) == 12 and len(seen - rows) == 16, sorted(seen)          # R in {0, 2, 4, 8, 16, 24} x DRAW; R in {0, 4, 8, 16} x DRAW x EXT
+    assert any("Li24E" in k for k in rows) and any("Li0E" in k for k in rows), sorted(rows)
 
 
 # ------------------------------------------------------------------------------------------------ sample_test_images plumbing
