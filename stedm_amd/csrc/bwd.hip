@@ -6,6 +6,7 @@
 // No atomics: every reduction has a fixed order, gradients are bitwise reproducible.
 #include "common.hpp"
 #include "sgemm.hpp"
+#include "wfrag.hpp"
 
 using namespace stedm;
 
@@ -1179,17 +1180,15 @@ __global__ void __launch_bounds__(256) adamw_ema_pack_kernel(const FusedOptDesc*
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int oi = 0; oi < d.nout; ++oi) {
     const FusedPackOut po = d.o[oi];
-    const int fr = po.m16 ? 16 : 32, fc = po.m16 ? 32 : 16;                 // fragment rows x channels
+    const int fr = po.m16 ? FragM16::FR : FragM32::FR, fc = po.m16 ? FragM16::KC : FragM32::KC;      // fragment rows x channels (wfrag.hpp)
     const int Rn = po.transposed ? CIW : ROWS, Rc = po.transposed ? ROWS : CIW;   // the piece in the pack's (row n, channel c) coordinates
     const int n_base = po.transposed ? ci0 : co0, c_base = po.transposed ? co0 : ci0;
     const int nch = (po.transposed ? cout : cin) / fc;                       // channel chunks of the pack
     const int nfn = Rn / fr, nfrag = nfn * (Rc / fc) * taps;
-    const int g = lane >> 4;
     for (int f = wave; f < nfrag; f += 4) {
       const int tap = f % taps, ff = f / taps, fn = ff % nfn, fcx = ff / nfn;
-      int nl, cl;
-      if (!po.m16) { nl = fn * 32 + (lane & 31); cl = fcx * 16 + (lane >> 5) * 8; }
-      else { nl = fn * 16 + (lane & 15); cl = fcx * 32 + 8 * (taps == 9 ? 2 * (g & 1) + (g >> 1) : g); }
+      const int nl = fn * fr + (po.m16 ? FragM16::lane_row(lane) : FragM32::lane_row(lane));
+      const int cl = fcx * fc + (po.m16 ? FragM16::lane_c(lane, taps) : FragM32::lane_c(lane, taps));
       const int ts = po.flip ? taps - 1 - tap : tap;        // source tap
       const float* src = po.transposed ? ftile + cl * pitch + nl * taps + ts : ftile + nl * pitch + cl * taps + ts;
       const int es = po.transposed ? pitch : taps;
@@ -1197,8 +1196,7 @@ __global__ void __launch_bounds__(256) adamw_ema_pack_kernel(const FusedOptDesc*
 #pragma unroll
       for (int e = 0; e < 8; ++e) x[e] = src[e * es];
       const int n = n_base + nl, c = c_base + cl;
-      const long at = po.m16 ? ((((long)(n >> 7) * nch + (c >> 5)) * taps + tap) * 8 + ((n >> 4) & 7)) * 512 + ((n & 15) + 16 * g) * 8
-                             : ((((long)(n >> 7) * nch + (c >> 4)) * taps + tap) * 4 + ((n >> 5) & 3)) * 512 + ((n & 31) + 32 * ((c >> 3) & 1)) * 8;
+      const long at = po.m16 ? frag_at<FragM16>(n, c, tap, nch, taps) : frag_at<FragM32>(n, c, tap, nch, taps);
       if (po.f16) {
         typedef _Float16 H8 __attribute__((ext_vector_type(8)));
         H8 o;

@@ -1,4 +1,4 @@
-// Error plumbing, weight packing, transposes, graph helpers, embedding path, im2col. The sampler kernels are in sampler.hip.
+// Error plumbing, transposes, graph helpers, embedding path, im2col. The sampler kernels are in sampler.hip, the 16-bit packs in pack.hip.
 #include <stdarg.h>
 
 #include "common.hpp"
@@ -40,472 +40,6 @@ extern "C" int stedm_device_cus(void) {
     return -1;
   }
   return p.multiProcessorCount;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Weight packing: OIHW fp32 -> [cout][tap][cin] 16-bit hi (+ lo = round(w - float(hi))).
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void pack_conv_weight_kernel(const float* __restrict__ w, T* __restrict__ hi, T* __restrict__ lo, int cout,
-                                        int cin, int taps, long sn, long sc, int flip) {
-  const long total = (long)cout * taps * cin;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ci = (int)(i % cin);
-    const long r = i / cin;
-    const int tap = (int)(r % taps);
-    const int co = (int)(r / taps);
-    const float v = w[(long)co * sn + (long)ci * sc + (flip ? taps - 1 - tap : tap)];
-    const T h = (T)v;
-    hi[i] = h;
-    if (lo) lo[i] = (T)(v - (float)h);
-  }
-}
-
-extern "C" int stedm_pack_conv_weight(const float* w, void* w_hi, void* w_lo, int cout, int cin, int ks, int mm_dtype,
-                                      void* stream) {
-  STEDM_CHECK_ARG(w && w_hi, "pack_conv_weight: null pointer");
-  STEDM_CHECK_ARG(ks == 1 || ks == 3, "pack_conv_weight: ks must be 1 or 3 (got %d)", ks);
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight: bad mm_dtype %d", mm_dtype);
-  const long total = (long)cout * cin * ks * ks;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  if (mm_dtype == STEDM_F16)
-    pack_conv_weight_kernel<_Float16><<<grid, 256, 0, as_stream(stream)>>>(w, (_Float16*)w_hi, (_Float16*)w_lo, cout, cin,
-                                                                         ks * ks, (long)cin * ks * ks, ks * ks, 0);
-  else
-    pack_conv_weight_kernel<__bf16><<<grid, 256, 0, as_stream(stream)>>>(w, (__bf16*)w_hi, (__bf16*)w_lo, cout, cin,
-                                                                       ks * ks, (long)cin * ks * ks, ks * ks, 0);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename T>
-__global__ void pack_conv_weight_up_kernel(const float* __restrict__ w, T* __restrict__ hi, T* __restrict__ lo, int cout, int cin) {
-  const long total = (long)4 * cout * 4 * cin;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ci = (int)(i % cin);
-    long r = i / cin;
-    const int tap = (int)(r % 4); r /= 4;
-    const int co = (int)(r % cout);
-    const int par = (int)(r / cout);
-    const int py = par >> 1, px = par & 1, a = tap >> 1, b = tap & 1;
-    // 3x3 taps that land on low-res neighbour (a, b) for output parity (py, px)
-    const int dy0 = py == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2), dy1 = py == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2);
-    const int dx0 = px == 0 ? (b == 0 ? 0 : 1) : (b == 0 ? 0 : 2), dx1 = px == 0 ? (b == 0 ? 0 : 2) : (b == 0 ? 1 : 2);
-    float v = 0.f;
-    for (int dy = dy0; dy <= dy1; ++dy)
-      for (int dx = dx0; dx <= dx1; ++dx) v += w[((long)co * cin + ci) * 9 + dy * 3 + dx];
-    const T h = (T)v;
-    hi[i] = h;
-    if (lo) lo[i] = (T)(v - (float)h);
-  }
-}
-
-extern "C" int stedm_pack_conv_weight_up(const float* w, void* w_hi, void* w_lo, int cout, int cin, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(w && w_hi, "pack_conv_weight_up: null pointer");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_up: bad mm_dtype %d", mm_dtype);
-  const long total = (long)16 * cout * cin;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  if (mm_dtype == STEDM_F16)
-    pack_conv_weight_up_kernel<_Float16><<<grid, 256, 0, as_stream(stream)>>>(w, (_Float16*)w_hi, (_Float16*)w_lo, cout, cin);
-  else
-    pack_conv_weight_up_kernel<__bf16><<<grid, 256, 0, as_stream(stream)>>>(w, (__bf16*)w_hi, (__bf16*)w_lo, cout, cin);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-// Fragment-order packing for the register-streamed 3x3 kernel (conv_rs.inc):
-//   out[tn][chunk][tap][q][lane][e] = W[n = tn*128 + (q>>1)*64 + (q&1)*32 + (lane&31)][ci = chunk*16 + (lane>>5)*8 + e][tap]
-// (rows beyond cout are zero). One wave-wide 16-B load = one MFMA B fragment, 1 KiB contiguous.
-// One block = one (128-row tile tn, 16-channel chunk, 64-row half): the 64 x 16 x taps source values go through LDS so that both the
-// gather from the source (runs along its contiguous index: (ci, tap) for an OIHW filter, (n, tap) for the transposed forms) and the
-// 16-B fragment stores are coalesced.
-// M16: the fragment order of the 16x16x32 MFMA kind (stedm_pack_conv_weight_frag16): blocks of 32 rows x 32 channels,
-//   out[tn][chunk32][tap][c][lane][e] = W[n = tn*128 + c*16 + (lane&15)][ci = chunk*32 + kofs(lane>>4) + e][tap], kofs(g) = 16 (g&1) + 8 (g>>1) for a
-//   3x3 (plane, piece), 8 g for a 1x1.
-constexpr int kPackTileFloats = 64 * (16 * 9 + 1);     // the largest tile of the four (taps, M16) forms: 64 rows x (16 x 9 + 1)
-
-// block `bid` of one tensor's pack; `traw`: kPackTileFloats floats of LDS
-template <typename T, int taps, bool M16>
-__device__ __forceinline__ void pack_frag_block(const float* __restrict__ w, T* __restrict__ out, const int cout, const int cin, const long sn,
-                                                const long sc, const int flip, const int bid, float* traw, T* __restrict__ out_lo = nullptr) {
-  typedef T V8 __attribute__((ext_vector_type(8)));
-  constexpr int NR = M16 ? 32 : 64, KC = M16 ? 32 : 16, NSUB = 128 / NR;     // rows and channels per block, blocks per 128-row tile
-  constexpr int PITCH = KC * taps + 1;
-  static_assert(NR * PITCH <= kPackTileFloats, "pack tile");
-  float (*tile)[PITCH] = reinterpret_cast<float (*)[PITCH]>(traw);
-  const int nch = cin / KC;
-  const int half = bid % NSUB;
-  const int chunk = (bid / NSUB) % nch, tn = (bid / NSUB) / nch;
-  const int n0 = tn * 128 + half * NR, ci0 = chunk * KC;
-  const int per = NR * KC * taps;
-  const bool n_fast = sn <= sc;       // which source index is contiguous
-  // 16-B loads along the contiguous source run when the layout allows it (rows inside the matrix, 16-B aligned runs): the pack is a
-  // pure stream, its speed is the bytes in flight
-  const bool vec = n0 + NR <= cout && (n_fast ? (sn == taps && (sc * 4) % 16 == 0) : (sc == taps && (sn * 4) % 16 == 0)) &&
-                   ((reinterpret_cast<uintptr_t>(w) & 15) == 0) && ((n_fast ? NR : KC) * taps) % 4 == 0;
-  if (vec) {
-    const int run = (n_fast ? NR : KC) * taps;          // contiguous floats per outer index (ci for n_fast, n otherwise)
-    const int nouter = n_fast ? KC : NR;
-    for (int v4 = threadIdx.x; v4 < nouter * (run / 4); v4 += 256) {
-      const int o = v4 / (run / 4), r0 = (v4 - o * (run / 4)) * 4;
-      const float* src = n_fast ? w + (long)n0 * sn + (long)(ci0 + o) * sc + r0 : w + (long)(n0 + o) * sn + (long)ci0 * sc + r0;
-      const float4 f = *reinterpret_cast<const float4*>(src);
-      const float fv[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = r0 + j, a = r / taps, ts = r - a * taps;       // a = n_local (n_fast) or ci_local; ts = source tap
-        const int tap = flip ? taps - 1 - ts : ts;
-        if (n_fast) tile[a][o * taps + tap] = fv[j];
-        else tile[o][a * taps + tap] = fv[j];
-      }
-    }
-  } else
-  for (int idx = threadIdx.x; idx < per; idx += 256) {
-    int row, cil, tap;
-    if (n_fast) { cil = idx / (NR * taps); const int r = idx - cil * NR * taps; row = r / taps; tap = r - row * taps; }
-    else { row = idx / (KC * taps); const int r = idx - row * KC * taps; cil = r / taps; tap = r - cil * taps; }
-    const int n = n0 + row;
-    tile[row][cil * taps + tap] = n < cout ? w[(long)n * sn + (long)(ci0 + cil) * sc + (flip ? taps - 1 - tap : tap)] : 0.f;
-  }
-  __syncthreads();
-  // stores: (tap, fragment of the block, lane) -> one 16-B vector of 8 consecutive channels
-  for (int v = threadIdx.x; v < taps * 2 * 64; v += 256) {
-    const int lane = v & 63, ql = (v >> 6) & 1, tap = v >> 7;
-    int row, c8;
-    if (M16) { const int g = lane >> 4; row = ql * 16 + (lane & 15); c8 = taps == 9 ? (g & 1) * 16 + (g >> 1) * 8 : g * 8; }
-    else { row = ql * 32 + (lane & 31); c8 = (lane >> 5) * 8; }
-    V8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (T)tile[row][(c8 + e) * taps + tap];
-    const int q = half * 2 + ql;
-    const long at = ((((long)tn * nch + chunk) * taps + tap) * (M16 ? 8 : 4) + q) * 512 + lane * 8;
-    *reinterpret_cast<V8*>(out + at) = o;
-    if (out_lo) {     // 3-product mode: the second stream holds w - hi
-      V8 l;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) l[e] = (T)(tile[row][(c8 + e) * taps + tap] - (float)o[e]);
-      *reinterpret_cast<V8*>(out_lo + at) = l;
-    }
-  }
-}
-
-template <typename T, int taps, bool M16 = false>
-__global__ void __launch_bounds__(256) pack_conv_weight_frag_kernel(const float* __restrict__ w, T* __restrict__ out, int cout, int cin, long total,
-                                                                    long sn, long sc, int flip, T* __restrict__ out_lo = nullptr) {
-  __shared__ float traw[kPackTileFloats];
-  pack_frag_block<T, taps, M16>(w, out, cout, cin, sn, sc, flip, blockIdx.x, traw, out_lo);
-}
-
-// Many tensors in ONE launch (the training step re-packs every convolution's weights after each optimizer step: ~130 packs of a few
-// microseconds each were launch-bound). descs[i].blk0 = first block of tensor i (ascending); a block finds its tensor by binary search.
-struct PackDesc {
-  const float* w;
-  void* out;
-  long sn, sc;
-  int cout, cin, taps, flip, m16, blk0;
-};
-static_assert(sizeof(PackDesc) == 56, "PackDesc layout is part of the ABI (stedm_pack_frag_multi)");
-
-template <typename T>
-__global__ void __launch_bounds__(256) pack_frag_multi_kernel(const PackDesc* __restrict__ descs, const int nd) {
-  __shared__ float traw[kPackTileFloats];
-  int lo = 0, hi = nd - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (descs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const PackDesc d = descs[lo];
-  const int bid = blockIdx.x - d.blk0;
-  T* out = reinterpret_cast<T*>(d.out);
-  if (d.m16) {
-    if (d.taps == 9) pack_frag_block<T, 9, true>(d.w, out, d.cout, d.cin, d.sn, d.sc, d.flip, bid, traw);
-    else pack_frag_block<T, 1, true>(d.w, out, d.cout, d.cin, d.sn, d.sc, d.flip, bid, traw);
-  } else {
-    if (d.taps == 9) pack_frag_block<T, 9, false>(d.w, out, d.cout, d.cin, d.sn, d.sc, d.flip, bid, traw);
-    else pack_frag_block<T, 1, false>(d.w, out, d.cout, d.cin, d.sn, d.sc, d.flip, bid, traw);
-  }
-}
-
-extern "C" int stedm_pack_frag_multi(const void* descs, int nd, int total_blocks, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(descs && nd > 0 && total_blocks > 0, "pack_frag_multi: bad args");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_frag_multi: bad mm_dtype %d", mm_dtype);
-  if (mm_dtype == STEDM_F16) pack_frag_multi_kernel<_Float16><<<total_blocks, 256, 0, as_stream(stream)>>>(reinterpret_cast<const PackDesc*>(descs), nd);
-  else pack_frag_multi_kernel<__bf16><<<total_blocks, 256, 0, as_stream(stream)>>>(reinterpret_cast<const PackDesc*>(descs), nd);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-static void launch_pack_frag(const float* w, void* out, int cout, int cin, int taps, long total, long sn, long sc, int flip, int mm_dtype, int grid,
-                             hipStream_t st) {
-  if (mm_dtype == STEDM_F16) {
-    if (taps == 9) pack_conv_weight_frag_kernel<_Float16, 9><<<grid, 256, 0, st>>>(w, (_Float16*)out, cout, cin, total, sn, sc, flip);
-    else pack_conv_weight_frag_kernel<_Float16, 1><<<grid, 256, 0, st>>>(w, (_Float16*)out, cout, cin, total, sn, sc, flip);
-  } else {
-    if (taps == 9) pack_conv_weight_frag_kernel<__bf16, 9><<<grid, 256, 0, st>>>(w, (__bf16*)out, cout, cin, total, sn, sc, flip);
-    else pack_conv_weight_frag_kernel<__bf16, 1><<<grid, 256, 0, st>>>(w, (__bf16*)out, cout, cin, total, sn, sc, flip);
-  }
-}
-
-extern "C" int stedm_pack_conv_weight_frag(const float* w, void* out, int cout, int cin, int ks, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(w && out && cin % 16 == 0 && (ks == 1 || ks == 3), "pack_conv_weight_frag: bad args (cin %% 16, ks 1 or 3)");
-  const int taps = ks * ks;
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_frag: bad mm_dtype %d", mm_dtype);
-  const long total = (long)((cout + 127) / 128) * (cin / 16) * taps * 4 * 64 * 8;
-  const int grid = ((cout + 127) / 128) * (cin / 16) * 2;
-  launch_pack_frag(w, out, cout, cin, taps, total, (long)cin * taps, taps, 0, mm_dtype, grid, as_stream(stream));
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-// Same packs from an arbitrarily strided source: element (n, ci, tap) = w[n*sn + ci*sc + (flip ? taps-1-tap : tap)]. The backward pass
-// packs the dgrad filter (n = forward cin, ci = forward cout, taps reversed) straight from the OIHW parameter, and dY^T of the
-// wgrad GEMM (n = channel, ci = pixel) straight from the NHWC gradient. Any of w_hi / w_lo / w_frag may be NULL.
-extern "C" int stedm_pack_conv_weight_strided(const float* w, long sn, long sc, int flip, void* w_hi, void* w_lo, void* w_frag, int cout, int cin, int ks,
-                                              int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(w && (w_hi || w_frag) && (ks == 1 || ks == 3), "pack_conv_weight_strided: bad args");
-  STEDM_CHECK_ARG(!w_frag || cin % 16 == 0, "pack_conv_weight_strided: fragment order needs cin %% 16 == 0");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_strided: bad mm_dtype %d", mm_dtype);
-  const int taps = ks * ks;
-  hipStream_t st = as_stream(stream);
-  if (w_hi) {
-    const long total = (long)cout * cin * taps;
-    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    if (mm_dtype == STEDM_F16) pack_conv_weight_kernel<_Float16><<<grid, 256, 0, st>>>(w, (_Float16*)w_hi, (_Float16*)w_lo, cout, cin, taps, sn, sc, flip);
-    else pack_conv_weight_kernel<__bf16><<<grid, 256, 0, st>>>(w, (__bf16*)w_hi, (__bf16*)w_lo, cout, cin, taps, sn, sc, flip);
-  }
-  if (w_frag) {
-    const long total = (long)((cout + 127) / 128) * (cin / 16) * taps * 4 * 64 * 8;
-    const int grid = ((cout + 127) / 128) * (cin / 16) * 2;
-    launch_pack_frag(w, w_frag, cout, cin, taps, total, sn, sc, flip, mm_dtype, grid, st);
-  }
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-// Sub-pixel upsample weights (see pack_conv_weight_up_kernel) in fragment order: [4 parities][tn][cin/16][4 taps][4][64][8]
-template <typename T>
-__global__ void pack_conv_weight_up_frag_kernel(const float* __restrict__ w, T* __restrict__ out, int cout, int cin, long per_parity) {
-  const int nch = cin / 16;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < 4 * per_parity; i += (long)gridDim.x * blockDim.x) {
-    const int par = (int)(i / per_parity);
-    const long ii = i - par * per_parity;
-    const int e = (int)(ii & 7);
-    const int lane = (int)((ii >> 3) & 63);
-    const int q = (int)((ii >> 9) & 3);
-    long r = ii >> 11;
-    const int tap = (int)(r & 3); r >>= 2;
-    const int chunk = (int)(r % nch);
-    const int tn = (int)(r / nch);
-    const int n = tn * 128 + (q >> 1) * 64 + (q & 1) * 32 + (lane & 31);
-    const int ci = chunk * 16 + (lane >> 5) * 8 + e;
-    const int py = par >> 1, px = par & 1, a = tap >> 1, b = tap & 1;
-    const int dy0 = py == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2), dy1 = py == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2);
-    const int dx0 = px == 0 ? (b == 0 ? 0 : 1) : (b == 0 ? 0 : 2), dx1 = px == 0 ? (b == 0 ? 0 : 2) : (b == 0 ? 1 : 2);
-    float v = 0.f;
-    if (n < cout)
-      for (int dy = dy0; dy <= dy1; ++dy)
-        for (int dx = dx0; dx <= dx1; ++dx) v += w[((long)n * cin + ci) * 9 + dy * 3 + dx];
-    out[i] = (T)v;
-  }
-}
-
-extern "C" int stedm_pack_conv_weight_up_frag(const float* w, void* out, int cout, int cin, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(w && out && cin % 32 == 0, "pack_conv_weight_up_frag: bad args (cin %% 32)");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_up_frag: bad mm_dtype %d", mm_dtype);
-  const long per = (long)((cout + 127) / 128) * (cin / 16) * 4 * 4 * 64 * 8;
-  const int grid = (int)((4 * per + 255) / 256 < 8192 ? (4 * per + 255) / 256 : 8192);
-  if (mm_dtype == STEDM_F16) pack_conv_weight_up_frag_kernel<_Float16><<<grid, 256, 0, as_stream(stream)>>>(w, (_Float16*)out, cout, cin, per);
-  else pack_conv_weight_up_frag_kernel<__bf16><<<grid, 256, 0, as_stream(stream)>>>(w, (__bf16*)out, cout, cin, per);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int stedm_pack_conv_weight_frag16(const float* w, long sn, long sc, int flip, void* out, int cout, int cin, int ks, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(w && out && cin % 32 == 0 && cout > 0 && (ks == 1 || ks == 3), "pack_conv_weight_frag16: bad args (cin %% 32, ks 1 or 3)");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_frag16: bad mm_dtype %d", mm_dtype);
-  const int taps = ks * ks;
-  const long total = (long)((cout + 127) / 128) * (cin / 32) * taps * 8 * 64 * 8;
-  const int grid = ((cout + 127) / 128) * (cin / 32) * 4;
-  hipStream_t st = as_stream(stream);
-  if (mm_dtype == STEDM_F16) {
-    if (taps == 9) pack_conv_weight_frag_kernel<_Float16, 9, true><<<grid, 256, 0, st>>>(w, (_Float16*)out, cout, cin, total, sn, sc, flip);
-    else pack_conv_weight_frag_kernel<_Float16, 1, true><<<grid, 256, 0, st>>>(w, (_Float16*)out, cout, cin, total, sn, sc, flip);
-  } else {
-    if (taps == 9) pack_conv_weight_frag_kernel<__bf16, 9, true><<<grid, 256, 0, st>>>(w, (__bf16*)out, cout, cin, total, sn, sc, flip);
-    else pack_conv_weight_frag_kernel<__bf16, 1, true><<<grid, 256, 0, st>>>(w, (__bf16*)out, cout, cin, total, sn, sc, flip);
-  }
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-// hi and lo fragment streams of the 3-product mode: out = [2][total] elements, total = ceil(cout / 128) * (cin / 32) * 9 * 8 * 512
-extern "C" int stedm_pack_conv_weight_frag16_hl(const float* w, long sn, long sc, int flip, void* out, int cout, int cin, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(w && out && cin % 32 == 0 && cout > 0, "pack_conv_weight_frag16_hl: bad args (cin %% 32)");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_frag16_hl: bad mm_dtype %d", mm_dtype);
-  const long total = (long)((cout + 127) / 128) * (cin / 32) * 9 * 8 * 64 * 8;
-  const int grid = ((cout + 127) / 128) * (cin / 32) * 4;
-  hipStream_t st = as_stream(stream);
-  if (mm_dtype == STEDM_F16)
-    pack_conv_weight_frag_kernel<_Float16, 9, true><<<grid, 256, 0, st>>>(w, (_Float16*)out, cout, cin, total, sn, sc, flip, (_Float16*)out + total);
-  else
-    pack_conv_weight_frag_kernel<__bf16, 9, true><<<grid, 256, 0, st>>>(w, (__bf16*)out, cout, cin, total, sn, sc, flip, (__bf16*)out + total);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-// ... of a 1x1 filter (skip_connection, qkv, proj_out in the 3-product modes): out = [2][ceil(cout / 128)][cin / 32][1][8][512]
-extern "C" int stedm_pack_conv_weight_frag16_hl1(const float* w, long sn, long sc, int flip, void* out, int cout, int cin, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(w && out && cin % 32 == 0 && cout > 0, "pack_conv_weight_frag16_hl1: bad args (cin %% 32)");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_frag16_hl1: bad mm_dtype %d", mm_dtype);
-  const long total = (long)((cout + 127) / 128) * (cin / 32) * 8 * 64 * 8;
-  const int grid = ((cout + 127) / 128) * (cin / 32) * 4;
-  hipStream_t st = as_stream(stream);
-  if (mm_dtype == STEDM_F16)
-    pack_conv_weight_frag_kernel<_Float16, 1, true><<<grid, 256, 0, st>>>(w, (_Float16*)out, cout, cin, total, sn, sc, flip, (_Float16*)out + total);
-  else
-    pack_conv_weight_frag_kernel<__bf16, 1, true><<<grid, 256, 0, st>>>(w, (__bf16*)out, cout, cin, total, sn, sc, flip, (__bf16*)out + total);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-// STEDM_CONV_S2D weights: the stride-2 3x3 as a 2x2 conv over the 4 parity blocks of the space-to-depth planes, fragment order
-template <typename T>
-__global__ void pack_conv_weight_s2d_frag_kernel(const float* __restrict__ w, T* __restrict__ out, int cout, int cin, long total, int pad_br) {
-  const int nch = 4 * cin / 16;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int e = (int)(i & 7);
-    const int lane = (int)((i >> 3) & 63);
-    const int q = (int)((i >> 9) & 3);
-    long r = i >> 11;
-    const int tap = (int)(r & 3); r >>= 2;
-    const int chunk = (int)(r % nch);
-    const int tn = (int)(r / nch);
-    const int n = tn * 128 + (q >> 1) * 64 + (q & 1) * 32 + (lane & 31);
-    const int cc = chunk * 16 + (lane >> 5) * 8 + e;          // channel of the planes: parity block * cin + c
-    const int par = cc / cin, c = cc - par * cin;
-    const int py = par >> 1, px = par & 1, a = tap >> 1, b = tap & 1;
-    // symmetric pad 1: plane rows (y-1, y) hold image rows 2y-2 .. 2y+1, the filter covers 2y-1 .. 2y+1;
-    // bottom/right pad (pad_br): plane rows (y, y+1) hold image rows 2y .. 2y+3, the filter covers 2y .. 2y+2
-    const int dy = pad_br ? (a == 0 ? py : (py == 0 ? 2 : -1)) : (a == 0 ? (py == 1 ? 0 : -1) : (py == 0 ? 1 : 2));
-    const int dx = pad_br ? (b == 0 ? px : (px == 0 ? 2 : -1)) : (b == 0 ? (px == 1 ? 0 : -1) : (px == 0 ? 1 : 2));
-    out[i] = (n < cout && dy >= 0 && dx >= 0) ? (T)w[((long)n * cin + c) * 9 + dy * 3 + dx] : (T)0.f;
-  }
-}
-
-extern "C" int stedm_pack_conv_weight_s2d_frag(const float* w, void* out, int cout, int cin, int mm_dtype, int pad_br, void* stream) {
-  STEDM_CHECK_ARG(w && out && cin % 8 == 0, "pack_conv_weight_s2d_frag: bad args (cin %% 8)");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_s2d_frag: bad mm_dtype %d", mm_dtype);
-  const long total = (long)((cout + 127) / 128) * (4 * cin / 16) * 4 * 4 * 64 * 8;
-  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  if (mm_dtype == STEDM_F16) pack_conv_weight_s2d_frag_kernel<_Float16><<<grid, 256, 0, as_stream(stream)>>>(w, (_Float16*)out, cout, cin, total, pad_br);
-  else pack_conv_weight_s2d_frag_kernel<__bf16><<<grid, 256, 0, as_stream(stream)>>>(w, (__bf16*)out, cout, cin, total, pad_br);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-// The same two derived filters for the 3-product modes on the 16x16x32 MFMA kind (conv_rs.inc RS_SUBM): fragment order of
-// stedm_pack_conv_weight_frag16 with 4 taps — out[parity][tn][chunk32][tap][c][lane][e] = W'[n = tn*128 + 16 c + (lane & 15)][ci = 32 chunk +
-// 16 (g & 1) + 8 (g >> 1) + e][tap], g = lane >> 4 — as a hi stream followed by a lo stream (value - hi, rounded).
-// UP: the four parity filters with pre-summed taps (pack_conv_weight_up_frag_kernel); else: the space-to-depth filter over 4 * cin channels.
-template <typename T, bool UP>
-__global__ void pack_conv_weight_sub_frag16_hl_kernel(const float* __restrict__ w, T* __restrict__ out, int cout, int cin, long per_parity, long total,
-                                                      int pad_br) {
-  const int nch = (UP ? cin : 4 * cin) / 32;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int par = UP ? (int)(i / per_parity) : 0;
-    const long ii = i - par * per_parity;
-    const int e = (int)(ii & 7);
-    const int lane = (int)((ii >> 3) & 63);
-    const int c = (int)((ii >> 9) & 7);
-    long r = ii >> 12;
-    const int tap = (int)(r & 3); r >>= 2;
-    const int chunk = (int)(r % nch);
-    const int tn = (int)(r / nch);
-    const int g = lane >> 4;
-    const int n = tn * 128 + c * 16 + (lane & 15);
-    const int cc = chunk * 32 + 16 * (g & 1) + 8 * (g >> 1) + e;
-    const int a = tap >> 1, b = tap & 1;
-    float v = 0.f;
-    if (n < cout) {
-      if (UP) {
-        const int py = par >> 1, px = par & 1;
-        const int dy0 = py == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2), dy1 = py == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2);
-        const int dx0 = px == 0 ? (b == 0 ? 0 : 1) : (b == 0 ? 0 : 2), dx1 = px == 0 ? (b == 0 ? 0 : 2) : (b == 0 ? 1 : 2);
-        for (int dy = dy0; dy <= dy1; ++dy)
-          for (int dx = dx0; dx <= dx1; ++dx) v += w[((long)n * cin + cc) * 9 + dy * 3 + dx];
-      } else {
-        const int pb = cc / cin, ci = cc - pb * cin;          // parity block of the space-to-depth planes, channel inside it
-        const int py = pb >> 1, px = pb & 1;
-        const int dy = pad_br ? (a == 0 ? py : (py == 0 ? 2 : -1)) : (a == 0 ? (py == 1 ? 0 : -1) : (py == 0 ? 1 : 2));
-        const int dx = pad_br ? (b == 0 ? px : (px == 0 ? 2 : -1)) : (b == 0 ? (px == 1 ? 0 : -1) : (px == 0 ? 1 : 2));
-        if (dy >= 0 && dx >= 0) v = w[((long)n * cin + ci) * 9 + dy * 3 + dx];
-      }
-    }
-    const T hv = (T)v;
-    out[i] = hv;
-    out[total + i] = (T)(v - (float)hv);
-  }
-}
-
-extern "C" int stedm_pack_conv_weight_up_frag16_hl(const float* w, void* out, int cout, int cin, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(w && out && cin % 32 == 0 && cout > 0, "pack_conv_weight_up_frag16_hl: bad args (cin %% 32)");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_up_frag16_hl: bad mm_dtype %d", mm_dtype);
-  const long per = (long)((cout + 127) / 128) * (cin / 32) * 4 * 8 * 64 * 8, total = 4 * per;
-  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  if (mm_dtype == STEDM_F16) pack_conv_weight_sub_frag16_hl_kernel<_Float16, true><<<grid, 256, 0, as_stream(stream)>>>(w, (_Float16*)out, cout, cin, per, total, 0);
-  else pack_conv_weight_sub_frag16_hl_kernel<__bf16, true><<<grid, 256, 0, as_stream(stream)>>>(w, (__bf16*)out, cout, cin, per, total, 0);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int stedm_pack_conv_weight_s2d_frag16_hl(const float* w, void* out, int cout, int cin, int mm_dtype, int pad_br, void* stream) {
-  STEDM_CHECK_ARG(w && out && cin % 8 == 0 && cout > 0, "pack_conv_weight_s2d_frag16_hl: bad args (cin %% 8)");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "pack_conv_weight_s2d_frag16_hl: bad mm_dtype %d", mm_dtype);
-  const long total = (long)((cout + 127) / 128) * (4 * cin / 32) * 4 * 8 * 64 * 8;
-  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  if (mm_dtype == STEDM_F16) pack_conv_weight_sub_frag16_hl_kernel<_Float16, false><<<grid, 256, 0, as_stream(stream)>>>(w, (_Float16*)out, cout, cin, total, total, pad_br);
-  else pack_conv_weight_sub_frag16_hl_kernel<__bf16, false><<<grid, 256, 0, as_stream(stream)>>>(w, (__bf16*)out, cout, cin, total, total, pad_br);
-  STEDM_LAUNCH_CHECK();
-  return 0;
-}
-
-// NHWC fp32 -> space-to-depth 16-bit planes [B][H/2][W/2][4C]; thread = one channel quad of one input pixel
-template <typename T>
-__global__ void __launch_bounds__(256) space_to_depth16_kernel(const float* __restrict__ x, T* __restrict__ hi, T* __restrict__ lo, int C, int H, int W,
-                                                               long total_q, unsigned* ovf) {
-  typedef T V4 __attribute__((ext_vector_type(4)));
-  const int Q = C >> 2;
-  unsigned bad = 0u;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total_q; i += (long)gridDim.x * blockDim.x) {
-    const int q = (int)(i % Q);
-    long pix = i / Q;
-    const int xx = (int)(pix % W); pix /= W;
-    const int yy = (int)(pix % H);
-    const long b = pix / H;
-    const float4 v = *reinterpret_cast<const float4*>(x + i * 4);
-    const long o = ((((b * (H >> 1) + (yy >> 1)) * (W >> 1) + (xx >> 1)) * 4 + ((yy & 1) * 2 + (xx & 1))) * (long)C >> 2) + q;
-    V4 h4;
-    h4[0] = (T)v.x; h4[1] = (T)v.y; h4[2] = (T)v.z; h4[3] = (T)v.w;
-    reinterpret_cast<V4*>(hi)[o] = h4;
-    bad |= f16_over_v4<T>(h4);
-    if (lo) {
-      V4 l4;
-      l4[0] = (T)(v.x - (float)h4[0]); l4[1] = (T)(v.y - (float)h4[1]); l4[2] = (T)(v.z - (float)h4[2]); l4[3] = (T)(v.w - (float)h4[3]);
-      reinterpret_cast<V4*>(lo)[o] = l4;
-    }
-  }
-  f16_guard_commit(ovf, bad, STEDM_F16G_S2D);
-}
-
-extern "C" int stedm_space_to_depth16(const float* x, int C, int B, int H, int W, void* out_hi, void* out_lo, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(x && out_hi && C > 0 && C % 4 == 0 && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "space_to_depth16: bad args (C %% 4, even H/W)");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "space_to_depth16: bad mm_dtype %d", mm_dtype);
-  const long total_q = (long)B * H * W * (C / 4);
-  const int grid = (int)((total_q + 255) / 256 < 16384 ? (total_q + 255) / 256 : 16384);
-  if (mm_dtype == STEDM_F16) space_to_depth16_kernel<_Float16><<<grid, 256, 0, as_stream(stream)>>>(x, (_Float16*)out_hi, (_Float16*)out_lo, C, H, W, total_q, f16_guard_flag());
-  else space_to_depth16_kernel<__bf16><<<grid, 256, 0, as_stream(stream)>>>(x, (__bf16*)out_hi, (__bf16*)out_lo, C, H, W, total_q, nullptr);
-  STEDM_LAUNCH_CHECK();
-  return 0;
 }
 
 __global__ void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int rows, int cols) {

@@ -126,113 +126,117 @@ def coop_check(where: str = "") -> None:
 
 
 # ------------------------------------------------------------------------------------------- weights
-def pack_conv_weight(w: torch.Tensor, prec: Precision) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """OIHW (or [O][I][1] Conv1d) fp32 -> ([O][taps][I] 16-bit hi, lo or None)."""
+# output shape of each pack from (tn = ceil(cout / 128), cout, cin, taps); the layouts are stated in csrc/wfrag.hpp
+_PACK_SHAPE = {
+    "planes": lambda tn, cout, cin, taps: (cout, taps, cin),
+    "up_planes": lambda tn, cout, cin, taps: (4 * cout, 4, cin),
+    "frag": lambda tn, cout, cin, taps: (tn, cin // 16, taps, 4, 64, 8),
+    "frag16": lambda tn, cout, cin, taps: (tn, cin // 32, taps, 8, 64, 8),
+    "frag16_hl": lambda tn, cout, cin, taps: (2, tn, cin // 32, taps, 8, 64, 8),
+    "up_frag": lambda tn, cout, cin, taps: (4, tn, cin // 16, 4, 4, 64, 8),
+    "up_frag16_hl": lambda tn, cout, cin, taps: (2, 4, tn, cin // 32, 4, 8, 64, 8),
+    "s2d_frag": lambda tn, cout, cin, taps: (tn, 4 * cin // 16, 4, 4, 64, 8),
+    "s2d_frag16_hl": lambda tn, cout, cin, taps: (2, tn, 4 * cin // 32, 4, 8, 64, 8),
+}
+
+
+def pack_blocks(cout: int, cin: int, m16: bool) -> int:
+    """blocks one tensor takes in a stedm_pack_frag_multi table (32 rows x 32 channels in the 16x16x32 order, 64 x 16 in the other)"""
+    return ((cout + 127) // 128) * ((cin // 32) * 4 if m16 else (cin // 16) * 2)
+
+
+def _conv_weight(w: torch.Tensor):
+    """OIHW (or [O][I][1] Conv1d) parameter -> (detached contiguous fp32 [O][I][ks][ks] on the GPU, cout, cin, ks)"""
     if w.dim() == 3:
         w = w.unsqueeze(-1)
     w = w.detach().contiguous()
     _chk(w, name="conv weight")
     cout, cin, ks, ks2 = w.shape
     assert ks == ks2
-    hi = torch.empty((cout, ks * ks, cin), dtype=torch.int16, device=w.device)
-    lo = torch.empty_like(hi) if prec.npass == 3 else None
-    check(lib().stedm_pack_conv_weight(w.data_ptr(), hi.data_ptr(), _ptr(lo), cout, cin, ks, prec.mm_dtype, _stream()),
-          "stedm_pack_conv_weight")
-    return hi, lo
+    return w, cout, cin, ks
+
+
+def _pack_empty(kind: str, w: torch.Tensor, cout: int, cin: int, taps: int) -> torch.Tensor:
+    return torch.empty(_PACK_SHAPE[kind]((cout + 127) // 128, cout, cin, taps), dtype=torch.int16, device=w.device)
+
+
+def _pack(entry: str, kind: str, w: torch.Tensor, cout: int, cin: int, taps: int, args, lo: bool = False):
+    """allocate the `kind` output (and a lo twin) and make the checked call lib().<entry>(*args(out pointer, lo pointer or None))"""
+    out = _pack_empty(kind, w, cout, cin, taps)
+    out_lo = torch.empty_like(out) if lo else None
+    check(getattr(lib(), entry)(*args(out.data_ptr(), _ptr(out_lo))), entry)
+    return out, out_lo
+
+
+def pack_conv_weight(w: torch.Tensor, prec: Precision) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """OIHW (or [O][I][1] Conv1d) fp32 -> ([O][taps][I] 16-bit hi, lo or None)."""
+    w, cout, cin, ks = _conv_weight(w)
+    return _pack("stedm_pack_conv_weight", "planes", w, cout, cin, ks * ks,
+                 lambda hi, lo: (w.data_ptr(), hi, lo, cout, cin, ks, prec.mm_dtype, _stream()), lo=prec.npass == 3)
 
 
 def pack_conv_weight_up(w: torch.Tensor, prec: Precision) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """OIHW 3x3 fp32 -> sub-pixel upsample planes [4*O][4][I] (parity-major), see stedm_pack_conv_weight_up."""
-    w = w.detach().contiguous()
-    _chk(w, name="conv weight")
-    cout, cin, ks, _ = w.shape
+    w, cout, cin, ks = _conv_weight(w)
     assert ks == 3
-    hi = torch.empty((4 * cout, 4, cin), dtype=torch.int16, device=w.device)
-    lo = torch.empty_like(hi) if prec.npass == 3 else None
-    check(lib().stedm_pack_conv_weight_up(w.data_ptr(), hi.data_ptr(), _ptr(lo), cout, cin, prec.mm_dtype, _stream()),
-          "stedm_pack_conv_weight_up")
-    return hi, lo
+    return _pack("stedm_pack_conv_weight_up", "up_planes", w, cout, cin, 4,
+                 lambda hi, lo: (w.data_ptr(), hi, lo, cout, cin, prec.mm_dtype, _stream()), lo=prec.npass == 3)
 
 
 def pack_conv_weight_frag(w: torch.Tensor, prec: Precision) -> torch.Tensor:
     """OIHW 3x3 / 1x1 fp32 -> MFMA-fragment-order 16-bit weights (see stedm_pack_conv_weight_frag)."""
-    w = w.detach().contiguous()
-    _chk(w, name="conv weight")
-    cout, cin, ks, _ = w.shape
+    w, cout, cin, ks = _conv_weight(w)
     assert ks in (1, 3) and cin % 16 == 0
-    out = torch.empty(((cout + 127) // 128, cin // 16, ks * ks, 4, 64, 8), dtype=torch.int16, device=w.device)
-    check(lib().stedm_pack_conv_weight_frag(w.data_ptr(), out.data_ptr(), cout, cin, ks, prec.mm_dtype, _stream()), "stedm_pack_conv_weight_frag")
-    return out
+    return _pack("stedm_pack_conv_weight_frag", "frag", w, cout, cin, ks * ks,
+                 lambda out, _: (w.data_ptr(), out, cout, cin, ks, prec.mm_dtype, _stream()))[0]
 
 
 def pack_conv_weight_frag16(w: torch.Tensor, prec: Precision, sn: Optional[int] = None, sc: Optional[int] = None, flip: bool = False,
                             cout: Optional[int] = None, cin: Optional[int] = None, ks: Optional[int] = None) -> torch.Tensor:
     """3x3 / 1x1 fp32 filter -> fragment order of the 16x16x32 MFMA kind (stedm_pack_conv_weight_frag16). Default: a plain OIHW filter;
     sn / sc / flip / cout / cin / ks describe a strided source like pack_conv_weight_strided (the dgrad filter of the training step)."""
-    w = w.detach()
     if sn is None:
-        w = w.contiguous()
-        cout, cin, ks, _ = w.shape
+        w, cout, cin, ks = _conv_weight(w)
         assert ks in (1, 3)
         sn, sc = cin * ks * ks, ks * ks
-    _chk(w, name="conv weight")
+    else:
+        w = w.detach()
+        _chk(w, name="conv weight")
     assert cin % 32 == 0
     if prec.npass == 3:      # 3-product mode: [2] = the hi stream, then the lo stream
-        out = torch.empty((2, (cout + 127) // 128, cin // 32, ks * ks, 8, 64, 8), dtype=torch.int16, device=w.device)
-        fn = lib().stedm_pack_conv_weight_frag16_hl if ks == 3 else lib().stedm_pack_conv_weight_frag16_hl1
-        check(fn(w.data_ptr(), sn, sc, int(flip), out.data_ptr(), cout, cin, prec.mm_dtype, _stream()), "stedm_pack_conv_weight_frag16_hl")
-        return out
-    out = torch.empty(((cout + 127) // 128, cin // 32, ks * ks, 8, 64, 8), dtype=torch.int16, device=w.device)
-    check(lib().stedm_pack_conv_weight_frag16(w.data_ptr(), sn, sc, int(flip), out.data_ptr(), cout, cin, ks, prec.mm_dtype, _stream()),
-          "stedm_pack_conv_weight_frag16")
-    return out
+        return _pack("stedm_pack_conv_weight_frag16_hl" if ks == 3 else "stedm_pack_conv_weight_frag16_hl1", "frag16_hl", w, cout, cin, ks * ks,
+                     lambda out, _: (w.data_ptr(), sn, sc, int(flip), out, cout, cin, prec.mm_dtype, _stream()))[0]
+    return _pack("stedm_pack_conv_weight_frag16", "frag16", w, cout, cin, ks * ks,
+                 lambda out, _: (w.data_ptr(), sn, sc, int(flip), out, cout, cin, ks, prec.mm_dtype, _stream()))[0]
+
+
+def _pack_derived(entry: str, kind: str, w: torch.Tensor, prec: Precision, cin_mod: int, *pad_br) -> torch.Tensor:
+    """the 2x2 filters derived from an OIHW 3x3 (sub-pixel upsample, space-to-depth downsample), fragment order"""
+    w, cout, cin, ks = _conv_weight(w)
+    assert ks == 3 and cin % cin_mod == 0
+    return _pack(entry, kind, w, cout, cin, 4, lambda out, _: (w.data_ptr(), out, cout, cin, prec.mm_dtype, *pad_br, _stream()))[0]
 
 
 def pack_conv_weight_up_frag(w: torch.Tensor, prec: Precision) -> torch.Tensor:
     """OIHW 3x3 fp32 -> fragment-order weights of the sub-pixel upsample form (4 parities x 4 pre-summed taps)."""
-    w = w.detach().contiguous()
-    _chk(w, name="conv weight")
-    cout, cin, ks, _ = w.shape
-    assert ks == 3 and cin % 32 == 0
-    out = torch.empty((4, (cout + 127) // 128, cin // 16, 4, 4, 64, 8), dtype=torch.int16, device=w.device)
-    check(lib().stedm_pack_conv_weight_up_frag(w.data_ptr(), out.data_ptr(), cout, cin, prec.mm_dtype, _stream()), "stedm_pack_conv_weight_up_frag")
-    return out
+    return _pack_derived("stedm_pack_conv_weight_up_frag", "up_frag", w, prec, 32)
 
 
 def pack_conv_weight_s2d_frag(w: torch.Tensor, prec: Precision, pad_br: bool = False) -> torch.Tensor:
     """OIHW 3x3 fp32 (stride-2 Downsample.op) -> fragment-order weights of the equivalent 2x2 conv over space-to-depth planes.
     pad_br: the conv pads bottom/right only (the VQ encoder's Downsample, model.py:59-76) instead of 1 on every side."""
-    w = w.detach().contiguous()
-    _chk(w, name="conv weight")
-    cout, cin, ks, _ = w.shape
-    assert ks == 3 and cin % 8 == 0
-    out = torch.empty(((cout + 127) // 128, 4 * cin // 16, 4, 4, 64, 8), dtype=torch.int16, device=w.device)
-    check(lib().stedm_pack_conv_weight_s2d_frag(w.data_ptr(), out.data_ptr(), cout, cin, prec.mm_dtype, int(pad_br), _stream()), "stedm_pack_conv_weight_s2d_frag")
-    return out
+    return _pack_derived("stedm_pack_conv_weight_s2d_frag", "s2d_frag", w, prec, 8, int(pad_br))
 
 
 def pack_conv_weight_up_frag16_hl(w: torch.Tensor, prec: Precision) -> torch.Tensor:
     """The sub-pixel upsample filters as hi + lo fragment streams of the 16x16x32 kind (stedm_pack_conv_weight_up_frag16_hl): the 3-product
     modes read both, the single-product modes the hi stream (RS_SUBM, conv_rs.inc)."""
-    w = w.detach().contiguous()
-    _chk(w, name="conv weight")
-    cout, cin, ks, _ = w.shape
-    assert ks == 3 and cin % 32 == 0
-    out = torch.empty((2, 4, (cout + 127) // 128, cin // 32, 4, 8, 64, 8), dtype=torch.int16, device=w.device)
-    check(lib().stedm_pack_conv_weight_up_frag16_hl(w.data_ptr(), out.data_ptr(), cout, cin, prec.mm_dtype, _stream()), "stedm_pack_conv_weight_up_frag16_hl")
-    return out
+    return _pack_derived("stedm_pack_conv_weight_up_frag16_hl", "up_frag16_hl", w, prec, 32)
 
 
 def pack_conv_weight_s2d_frag16_hl(w: torch.Tensor, prec: Precision, pad_br: bool = False) -> torch.Tensor:
     """The space-to-depth Downsample filter as hi + lo fragment streams of the 16x16x32 kind (3-product modes: both; single-product: hi)."""
-    w = w.detach().contiguous()
-    _chk(w, name="conv weight")
-    cout, cin, ks, _ = w.shape
-    assert ks == 3 and cin % 8 == 0
-    out = torch.empty((2, (cout + 127) // 128, 4 * cin // 32, 4, 8, 64, 8), dtype=torch.int16, device=w.device)
-    check(lib().stedm_pack_conv_weight_s2d_frag16_hl(w.data_ptr(), out.data_ptr(), cout, cin, prec.mm_dtype, int(pad_br), _stream()),
-          "stedm_pack_conv_weight_s2d_frag16_hl")
-    return out
+    return _pack_derived("stedm_pack_conv_weight_s2d_frag16_hl", "s2d_frag16_hl", w, prec, 8, int(pad_br))
 
 
 def space_to_depth16(x: torch.Tensor, out_hi: torch.Tensor, out_lo: Optional[torch.Tensor], prec: Precision) -> None:
@@ -397,19 +401,12 @@ class PackPlan:
 
     def frag(self, w: torch.Tensor, sn: int, sc: int, flip: bool, cout: int, cin: int, ks: int, m16: bool) -> torch.Tensor:
         """Pack now (single-tensor launch) and remember the problem. w: fp32 tensor whose element (n, ci, tap) is flat[n*sn + ci*sc + tap']."""
-        _chk(w, name="w")
-        taps = ks * ks
         if m16:
-            assert cin % 32 == 0
-            out = torch.empty(((cout + 127) // 128, cin // 32, taps, 8, 64, 8), dtype=torch.int16, device=w.device)
-            check(lib().stedm_pack_conv_weight_frag16(w.data_ptr(), sn, sc, int(flip), out.data_ptr(), cout, cin, ks, self.prec.mm_dtype, _stream()),
-                  "stedm_pack_conv_weight_frag16")
+            assert self.prec.npass == 1        # stedm_pack_frag_multi writes one stream: no hi + lo form of this order here
+            out = pack_conv_weight_frag16(w, self.prec, sn, sc, flip, cout, cin, ks)
         else:
-            assert cin % 16 == 0
-            out = torch.empty(((cout + 127) // 128, cin // 16, taps, 4, 64, 8), dtype=torch.int16, device=w.device)
-            check(lib().stedm_pack_conv_weight_strided(w.data_ptr(), sn, sc, int(flip), None, None, out.data_ptr(), cout, cin, ks, self.prec.mm_dtype,
-                                                       _stream()), "stedm_pack_conv_weight_strided")
-        self.items.append((w, sn, sc, int(flip), cout, cin, taps, int(m16), out))
+            out = pack_conv_weight_strided(w, sn, sc, flip, cout, cin, ks, self.prec, want_hi=False, want_frag=True)[2]
+        self.items.append((w, sn, sc, int(flip), cout, cin, ks * ks, int(m16), out))
         self._table = None
         self._rest = None
         self._fresh = None
@@ -426,7 +423,7 @@ class PackPlan:
         for i in idxs:
             (w, sn, sc, flip, cout, cin, taps, m16, out) = self.items[i]
             rec.append(struct.pack("<QQqqiiiiii", w.data_ptr(), out.data_ptr(), sn, sc, cout, cin, taps, flip, m16, blk))
-            blk += ((cout + 127) // 128) * ((cin // 32) * 4 if m16 else (cin // 16) * 2)
+            blk += pack_blocks(cout, cin, m16)
         if not rec:
             return None, 0, 0
         return torch.frombuffer(bytearray(b"".join(rec)), dtype=torch.uint8).to(self.items[0][0].device), blk, len(rec)
@@ -1444,10 +1441,9 @@ def pack_conv_weight_strided(w: torch.Tensor, sn: int, sc: int, flip: bool, cout
                              want_frag: bool = False):
     """(hi, lo, frag) packs of the filter whose element (n, ci, tap) is w.flatten()[n*sn + ci*sc + tap'] (see stedm_pack_conv_weight_strided)."""
     _chk(w, name="w")
-    taps = ks * ks
-    hi = torch.empty((cout, taps, cin), dtype=torch.int16, device=w.device) if want_hi else None
+    hi = _pack_empty("planes", w, cout, cin, ks * ks) if want_hi else None
     lo = torch.empty_like(hi) if (want_hi and prec.npass == 3) else None
-    frag = torch.empty(((cout + 127) // 128, cin // 16, taps, 4, 64, 8), dtype=torch.int16, device=w.device) if want_frag else None
+    frag = _pack_empty("frag", w, cout, cin, ks * ks) if want_frag else None
     check(lib().stedm_pack_conv_weight_strided(w.data_ptr(), sn, sc, int(flip), _ptr(hi), _ptr(lo), _ptr(frag), cout, cin, ks, prec.mm_dtype, _stream()),
           "stedm_pack_conv_weight_strided")
     return hi, lo, frag

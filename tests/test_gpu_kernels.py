@@ -1310,20 +1310,6 @@ def test_conv_up_subpixel_epilogue_chan_stats(dev, prec, B, H, W, c, cout):
     assert torch.allclose(cs.sum(1)[..., 1].double(), (flat * flat).sum(1), rtol=1e-4, atol=5e-3)
 
 
-def test_pack_conv_weight_frag_layout(dev):
-    from stedm_amd import ops
-    prec = ops.Precision.parse("f16")
-    cout, cin = 160, 48
-    w = prng.normal(3, "wf.w", (cout, cin, 3, 3))
-    got = ops.pack_conv_weight_frag(w.to(dev), prec).cpu().view(torch.float16).float()      # [tn][chunk][tap][q][lane][8]
-    tn, ch, tap, q, lane, e = torch.meshgrid(*[torch.arange(n) for n in got.shape], indexing="ij")
-    n = tn * 128 + (q // 2) * 64 + (q % 2) * 32 + (lane % 32)
-    ci = ch * 16 + (lane // 32) * 8 + e
-    wp = torch.cat([w, torch.zeros(256 - cout, cin, 3, 3)]).reshape(256, cin, 9)
-    want = wp[n, ci, tap].half().float()
-    assert torch.equal(got, want)
-
-
 @pytest.mark.parametrize("prec,tol", PRECS[:2])
 @pytest.mark.parametrize("B,H,W,c,mode", [(2, 8, 8, 64, "up"), (16, 16, 16, 128, "up"), (3, 4, 4, 32, "up"), (1, 32, 32, 32, "up"),
                                           (2, 16, 16, 64, "down"), (8, 32, 32, 128, "down"), (3, 8, 8, 32, "down")])
