@@ -5,6 +5,7 @@
 // (GroupNorm+SiLU backward, attention backward, reductions, loss, optimizer) is HBM-bound fp32 work in this file.
 // No atomics: every reduction has a fixed order, gradients are bitwise reproducible.
 #include "common.hpp"
+#include "gn_fold.hpp"
 #include "sgemm.hpp"
 #include "wfrag.hpp"
 
@@ -37,34 +38,10 @@ __device__ __forceinline__ float silu_grad(float y) {
 
 // ------------------------------------------------------------------------------------------------ GroupNorm statistics
 // chan partials of the (virtual concat) input -> mr[B][groups][2] = {mean, rstd}
-__global__ void __launch_bounds__(256) gn_fold_kernel(const float* __restrict__ cs1, int nslab1, int c1, const float* __restrict__ cs2, int nslab2,
-                                                      int c2, int groups, int HW, float eps, float* __restrict__ mr) {
+// (one block per sample folds all its groups, as a pixel-run block of the forward's apply kernels does: the same bits, gn_fold.hpp)
+__global__ void __launch_bounds__(256) gn_fold_kernel(GnPartials p) {
   __shared__ double dsu[256], dsq[256];
-  const int b = blockIdx.x, C = c1 + c2, cpg = C / groups;
-  const int L = 256 / groups, g = threadIdx.x / L, l = threadIdx.x % L;
-  double su = 0.0, sq = 0.0;
-  if (g < groups) {
-    const int nmax = nslab1 > nslab2 ? nslab1 : nslab2;
-    for (int e = l; e < cpg * nmax; e += L) {
-      const int k = e / cpg, c = g * cpg + (e - k * cpg);
-      if (c < c1) {
-        if (k < nslab1) { const float* p = cs1 + (((long)b * nslab1 + k) * c1 + c) * 2; su += (double)p[0]; sq += (double)p[1]; }
-      } else if (k < nslab2) {
-        const float* p = cs2 + (((long)b * nslab2 + k) * c2 + (c - c1)) * 2; su += (double)p[0]; sq += (double)p[1];
-      }
-    }
-  }
-  dsu[threadIdx.x] = su; dsq[threadIdx.x] = sq;
-  __syncthreads();
-  if (threadIdx.x < groups) {
-    double s = 0.0, q = 0.0;
-    for (int i = 0; i < L; ++i) { s += dsu[threadIdx.x * L + i]; q += dsq[threadIdx.x * L + i]; }
-    const double n = (double)cpg * HW, mean = s / n;
-    double var = q / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    mr[((long)b * groups + threadIdx.x) * 2] = (float)mean;
-    mr[((long)b * groups + threadIdx.x) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  }
+  gn_fold_block<false>(p, blockIdx.x, blockIdx.x, 0, p.groups, true, dsu, dsq, nullptr, nullptr);
 }
 
 struct GnBwdArgs {
@@ -1279,7 +1256,7 @@ extern "C" int stedm_spatial_rescale_wgrad(const float* x, const float* d_out, f
 extern "C" int stedm_gn_fold(const float* cs1, int nslab1, int c1, const float* cs2, int nslab2, int c2, int groups, int B, int HW, float eps, float* mean_rstd,
                              void* stream) {
   STEDM_CHECK_ARG(cs1 && mean_rstd && groups > 0 && groups <= 64 && (c1 + c2) % groups == 0 && (cs2 != nullptr) == (c2 > 0), "gn_fold: bad args");
-  gn_fold_kernel<<<B, 256, 0, as_stream(stream)>>>(cs1, nslab1, c1, cs2, nslab2, c2, groups, HW, eps, mean_rstd);
+  gn_fold_kernel<<<B, 256, 0, as_stream(stream)>>>(GnPartials{cs1, nslab1, c1, cs2, nslab2, c2, groups, HW, eps, mean_rstd});
   STEDM_LAUNCH_CHECK();
   return 0;
 }

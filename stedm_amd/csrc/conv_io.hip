@@ -218,7 +218,7 @@ __global__ void __launch_bounds__(256) conv_out_kernel(const float* __restrict__
       const int g = ch / cpg;
       double su = 0.0, sq = 0.0;
       for (int cc = g * cpg; cc < (g + 1) * cpg; ++cc) { su += dsum[cc * 2]; sq += dsum[cc * 2 + 1]; }      // fixed order
-      const double inv_n = 1.0 / ((double)cpg * HW);
+      const double inv_n = 1.0 / ((double)cpg * HW);      // gn_mean_rstd (gn_fold.hpp) is the statement of record of these five lines
       const double mean = su * inv_n;
       double var = sq * inv_n - mean * mean;
       var = var > 0.0 ? var : 0.0;

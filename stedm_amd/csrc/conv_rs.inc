@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "conv_igemm_dma.inc"
+#include "gn_fold.hpp"
 
 // timing experiments only (STEDM_CONV_DBG & 1024): per-block phase stamps of the constant 100 MHz clock (tools/conv_phases.py)
 static __device__ unsigned long long g_conv_stamps[2048 * 8];
@@ -1376,8 +1377,8 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
         if (tid < ng) {
           double s_ = 0.0, q_ = 0.0;
           if (coop) {
-            // the sample's `coop` x cpg partial sums of this group in the order stedm_gn_apply16c folds the same statistics (entry e = slab * cpg +
-            // channel; lane l of L = 256 / groups takes e = l, l + L, ...; the lanes' doubles are added in lane order): same mean / rstd bits
+            // the sample's `coop` x cpg partial sums of this group in the order gn_fold_block (gn_fold.hpp) states for the apply kernels, which
+            // fold the same statistics with L = 256 / groups lanes per group: same mean / rstd bits
             const int L = 256 / a.gn_groups, n_e = cpg * coop;
             for (int l = 0; l < L; ++l) {
               double su = 0.0, sq = 0.0;
@@ -1389,12 +1390,7 @@ __global__ void __launch_bounds__((16 / WM + 2) * 64) conv_rs_kernel(const ConvP
             }
           } else
           for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { s_ += (double)sCh[c * 2]; q_ += (double)sCh[c * 2 + 1]; }
-          const double inv_n = 1.0 / ((double)cpg * (coop ? p.HWout : rows_per));
-          const double mean = s_ * inv_n;
-          double var = q_ * inv_n - mean * mean;
-          var = var > 0.0 ? var : 0.0;
-          sGm[tid * 2] = (float)mean;
-          sGm[tid * 2 + 1] = (float)(1.0 / sqrt(var + (double)a.gn_eps));
+          gn_mean_rstd(s_, q_, 1.0 / ((double)cpg * (coop ? p.HWout : rows_per)), a.gn_eps, sGm[tid * 2], sGm[tid * 2 + 1]);
           if (a.gn_mr && sM[row0] >= 0) { float* d = a.gn_mr + ((long)sMb[row0] * a.gn_groups + n0 / cpg + tid) * 2; d[0] = sGm[tid * 2]; d[1] = sGm[tid * 2 + 1]; }
         }
         __syncthreads();
@@ -1528,12 +1524,7 @@ static __global__ void __launch_bounds__(256) conv_splitk_reduce_kernel(const st
     if (t < ng) {
       double s_ = 0.0, q_ = 0.0;
       for (int c = t * cpg; c < (t + 1) * cpg; ++c) { s_ += (double)gsum[(c >> 2) * 8 + (c & 3)]; q_ += (double)gsum[(c >> 2) * 8 + 4 + (c & 3)]; }
-      const double inv_n = 1.0 / ((double)cpg * HW);
-      const double mean = s_ * inv_n;
-      double var = q_ * inv_n - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      gmr[t * 2] = (float)mean;
-      gmr[t * 2 + 1] = (float)(1.0 / sqrt(var + (double)a.gn_eps));
+      gn_mean_rstd(s_, q_, 1.0 / ((double)cpg * HW), a.gn_eps, gmr[t * 2], gmr[t * 2 + 1]);
       if (a.gn_mr) { float* d = a.gn_mr + ((long)b * a.gn_groups + (qb0 * 4) / cpg + t) * 2; d[0] = gmr[t * 2]; d[1] = gmr[t * 2 + 1]; }
     }
     __syncthreads();

@@ -1,11 +1,10 @@
 // GroupNorm statistics -> per-(sample, channel) scale/shift, over the virtual concat [x1 | x2].
 // One block per (sample, group): two passes over its cpg x HW slice (second pass hits L1/L2),
 // so the variance is the centred, biased form nn.GroupNorm computes (util.py:214-216).
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.hpp"
+#include "gn_fold.hpp"
 using namespace stedm;
 
 struct GnArgs {
@@ -221,11 +220,7 @@ __global__ void __launch_bounds__(256) gn_apply16_kernel(GnApplyArgs a, int slab
       su += a.stats[(((long)b * nslab_stats + k) * a.groups + threadIdx.x) * 2];
       sq += a.stats[(((long)b * nslab_stats + k) * a.groups + threadIdx.x) * 2 + 1];
     }
-    const double mean = su * inv_n;
-    double var = sq * inv_n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    lmean[threadIdx.x] = (float)mean;
-    lrstd[threadIdx.x] = (float)(1.0 / sqrt(var + (double)a.eps));
+    gn_mean_rstd(su, sq, inv_n, a.eps, lmean[threadIdx.x], lrstd[threadIdx.x]);
   }
   __syncthreads();
   const float* p1 = a.x1 + (long)b * a.HW * a.c1;
@@ -256,17 +251,12 @@ __global__ void __launch_bounds__(256) gn_apply16_kernel(GnApplyArgs a, int slab
       }
     }
     if (a.act == 1) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
-    V4 hi;
-    hi[0] = (T)v.x; hi[1] = (T)v.y; hi[2] = (T)v.z; hi[3] = (T)v.w;
+    V4 lo;
+    const V4 hi = split16<T>(v, ol != nullptr, lo);
     const long o = (long)pix * Q + q;
     oh[o] = hi;
     bad |= f16_over_v4<T>(hi);
-    if (ol) {
-      V4 lo;
-      lo[0] = (T)(v.x - (float)hi[0]); lo[1] = (T)(v.y - (float)hi[1]);
-      lo[2] = (T)(v.z - (float)hi[2]); lo[3] = (T)(v.w - (float)hi[3]);
-      ol[o] = lo;
-    }
+    if (ol) ol[o] = lo;
     pix += dpix; q += dq;
     if (q >= Q) { q -= Q; ++pix; }
   }
@@ -329,13 +319,11 @@ __global__ void __launch_bounds__(256) gn_chan_stats_kernel(const float* __restr
       const float4 v = *reinterpret_cast<const float4*>(px + (long)pix * C);
       if constexpr (CAST) {
         const long o = ((long)b * HW + pix) * C + (qb0 + tq) * 4;
-        V4 h4; h4[0] = (T)v.x; h4[1] = (T)v.y; h4[2] = (T)v.z; h4[3] = (T)v.w;
+        V4 l4;
+        const V4 h4 = split16<T>(v, o_lo != nullptr, l4);
         *reinterpret_cast<V4*>(o_hi + o) = h4;
         bad |= f16_over_v4<T>(h4);
-        if (o_lo) {
-          V4 l4; l4[0] = (T)(v.x - (float)h4[0]); l4[1] = (T)(v.y - (float)h4[1]); l4[2] = (T)(v.z - (float)h4[2]); l4[3] = (T)(v.w - (float)h4[3]);
-          *reinterpret_cast<V4*>(o_lo + o) = l4;
-        }
+        if (o_lo) *reinterpret_cast<V4*>(o_lo + o) = l4;
       }
       s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
       q[0] += v.x * v.x; q[1] += v.y * v.y; q[2] += v.z * v.z; q[3] += v.w * v.w;
@@ -415,13 +403,10 @@ struct GnApplyCArgs {
   void* raw_lo;
   float* mr;     // optional [B][groups][2]: the {mean, rstd} this pass folds anyway, kept for the training backward
   unsigned* ovf; // fp16 range guard flag (common.hpp) or nullptr
-  const void* x16;  // v8 kernel, X16 form: the x1 channels arrive as the 16-bit values a convolution's epilogue already wrote into channels
+  const void* x16;  // octet kernel: the x1 channels arrive as the 16-bit values a convolution's epilogue already wrote into channels
                     // [0, c1) of the raw plane [B][HW][c1 + c2] (= raw_hi): x1 is not read and that part of the raw plane not rewritten
+  __device__ GnPartials partials() const { return GnPartials{cs1, nslab1, c1, cs2, nslab2, c2, groups, HW, eps, mr}; }
 };
-
-// A value beyond the fp16 range (65 504) in a run of pixels makes that run's sum of squares exceed 65 504^2 = 4.29e9: a block whose channel
-// partials all stay below the threshold cannot overflow and skips the per-element test of its stream (NaN / inf partials fail the `<` too).
-#define STEDM_F16_SQ_SAFE 4.0e9f
 
 // y = act(GroupNorm([x1|x2])) from channel partials -> 16-bit planes; optionally also the plain conversion of [x1|x2]
 // (raw planes: the operand of the ResBlock's 1x1 skip convolution) from the same read of the fp32 tensors.
@@ -462,48 +447,11 @@ __global__ void __launch_bounds__(256) gn_apply16c_kernel(GnApplyCArgs a, int sl
     }
   };
   load_batch(threadIdx.x);
-  bool maybe_over = false;       // block-uniform: some channel partial of this block's groups admits |x| > 65504 (fp16 guard, raw planes)
-  bool norm_over = false;        // block-uniform: some channel's gamma / beta admits a normalised value beyond the fp16 range
+  // every block folds all groups of its sample (gn_fold.hpp); the first one writes the side output. Block-uniform guard switches:
+  const bool guard = a.ovf != nullptr && __is_same(T, _Float16);
+  const bool maybe_over = gn_fold_block(a.partials(), b, b2, 0, a.groups, sl == 0, dsu, dsq, lmean, lrstd) && guard;   // raw planes
+  const bool norm_over = gn_norm_over(a.gamma, a.beta, C, cpg, a.HW, guard);                                            // normalised planes
   unsigned bad_raw = 0u, bad_norm = 0u;
-  {
-    const int L = 256 / a.groups;                 // lanes per group (groups <= 64)
-    const int g = threadIdx.x / L, l = threadIdx.x % L;
-    double su = 0.0, sq = 0.0;
-    int big = 0;
-    if (g < a.groups) {
-      const int nmax = a.nslab1 > a.nslab2 ? a.nslab1 : a.nslab2;
-      const int n = cpg * nmax;
-      for (int e = l; e < n; e += L) {            // entry = (slab k, channel cc of the group); tensors may be partitioned differently
-        const int k = e / cpg, c = g * cpg + (e - k * cpg);
-        if (c < a.c1) {
-          if (k < a.nslab1) { const float* p = a.cs1 + (((long)b * a.nslab1 + k) * a.c1 + c) * 2; su += (double)p[0]; sq += (double)p[1]; big |= !(p[1] < STEDM_F16_SQ_SAFE); }
-        } else if (k < a.nslab2) {
-          const float* p = a.cs2 + (((long)b2 * a.nslab2 + k) * a.c2 + (c - a.c1)) * 2; su += (double)p[0]; sq += (double)p[1]; big |= !(p[1] < STEDM_F16_SQ_SAFE);
-        }
-      }
-    }
-    dsu[threadIdx.x] = su; dsq[threadIdx.x] = sq;
-    maybe_over = __syncthreads_or(big) != 0 && a.ovf != nullptr && __is_same(T, _Float16);
-    if (g < a.groups && l == 0) {
-      double s = 0.0, q = 0.0;
-      for (int i = 0; i < L; ++i) { s += dsu[threadIdx.x + i]; q += dsq[threadIdx.x + i]; }   // fixed order
-      const double inv_n = 1.0 / ((double)cpg * a.HW);
-      const double mean = s * inv_n;
-      double var = q * inv_n - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      lmean[g] = (float)mean;
-      lrstd[g] = (float)(1.0 / sqrt(var + (double)a.eps));
-      if (a.mr && sl == 0) { a.mr[((long)b * a.groups + g) * 2] = lmean[g]; a.mr[((long)b * a.groups + g) * 2 + 1] = lrstd[g]; }
-    }
-    // the normalised planes have their own switch: |x^| <= sqrt(n) whatever the raw values are, so a plane value can only leave the fp16
-    // range through gamma / beta (sqrt(n) |gamma| + |beta| > 65504) - small raw values do not rule that out
-    int nb = 0;
-    if (a.ovf != nullptr && __is_same(T, _Float16)) {
-      const float rn = sqrtf((float)cpg * (float)a.HW);
-      for (int c = threadIdx.x; c < C; c += 256) nb |= !(rn * fabsf(a.gamma[c]) + fabsf(a.beta[c]) < 65504.f);
-    }
-    norm_over = __syncthreads_or(nb) != 0;
-  }
   for (int i = threadIdx.x; i < total; i += 256 * U) {
     if (i != (int)threadIdx.x) load_batch(i);
 #pragma unroll
@@ -513,16 +461,11 @@ __global__ void __launch_bounds__(256) gn_apply16c_kernel(GnApplyCArgs a, int sl
         float4 w = v[k];
         const long o = (long)pixs[k] * Q + qs[k];
         if (rh) {
-          V4 hi;
-          hi[0] = (T)w.x; hi[1] = (T)w.y; hi[2] = (T)w.z; hi[3] = (T)w.w;
+          V4 lo;
+          const V4 hi = split16<T>(w, rl != nullptr, lo);
           rh[o] = hi;
           if (maybe_over) bad_raw |= f16_over_v4<T>(hi);
-          if (rl) {
-            V4 lo;
-            lo[0] = (T)(w.x - (float)hi[0]); lo[1] = (T)(w.y - (float)hi[1]);
-            lo[2] = (T)(w.z - (float)hi[2]); lo[3] = (T)(w.w - (float)hi[3]);
-            rl[o] = lo;
-          }
+          if (rl) rl[o] = lo;
         }
         const float4 gm = *reinterpret_cast<const float4*>(a.gamma + c);
         const float4 bt = *reinterpret_cast<const float4*>(a.beta + c);
@@ -537,16 +480,11 @@ __global__ void __launch_bounds__(256) gn_apply16c_kernel(GnApplyCArgs a, int sl
           w.z = (w.z - mf) * rstd * gm.z + bt.z; w.w = (w.w - mf) * rstd * gm.w + bt.w;
         }
         if (a.act == 1) { w.x = silu_f(w.x); w.y = silu_f(w.y); w.z = silu_f(w.z); w.w = silu_f(w.w); }
-        V4 hi;
-        hi[0] = (T)w.x; hi[1] = (T)w.y; hi[2] = (T)w.z; hi[3] = (T)w.w;
+        V4 lo;
+        const V4 hi = split16<T>(w, ol != nullptr, lo);
         oh[o] = hi;
         if (norm_over) bad_norm |= f16_over_v4<T>(hi);
-        if (ol) {
-          V4 lo;
-          lo[0] = (T)(w.x - (float)hi[0]); lo[1] = (T)(w.y - (float)hi[1]);
-          lo[2] = (T)(w.z - (float)hi[2]); lo[3] = (T)(w.w - (float)hi[3]);
-          ol[o] = lo;
-        }
+        if (ol) ol[o] = lo;
       }
       pixs[k] += dpix; qs[k] += dq;
       if (qs[k] >= Q) { qs[k] -= Q; ++pixs[k]; }
@@ -566,7 +504,7 @@ __global__ void __launch_bounds__(256) gn_apply16c_kernel(GnApplyCArgs a, int sl
 // cb > 0: the block takes a CHANNEL run of cb channels (whole groups, a multiple of 8) of every pixel of its sample instead of a pixel run
 // of all channels: it folds the statistics and builds the table of its own groups only (the samples of the 8 x 8 level are 64 pixels of
 // 1024 - 2048 channels: six pixel-run blocks per sample each built the whole table for 11 pixels of streaming).
-template <typename T, bool X16 = false>
+template <typename T>
 __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int slab, int cb) {
   typedef T V4 __attribute__((ext_vector_type(4)));
   __shared__ double dsu[256], dsq[256];
@@ -576,9 +514,8 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
   const int C = a.c1 + a.c2, Qall = C >> 2;
   const int cpg = C / a.groups;
   const int b2 = a.bmod > 0 ? b % a.bmod : b;
-  const float* p1 = X16 ? nullptr : a.x1 + (long)b * a.HW * a.c1;
+  const float* p1 = a.x1 + (long)b * a.HW * a.c1;
   const float* p2 = a.x2 ? a.x2 + (long)b2 * a.HW * a.c2 : nullptr;
-  const T* p16 = X16 ? reinterpret_cast<const T*>(a.x16) + (long)b * a.HW * C : nullptr;      // rows of C channels: the raw plane itself
   const int c_lo = cb > 0 ? sl * cb : 0, c_n = cb > 0 ? cb : C;       // this block's channels
   const int Q = c_n >> 2, q_lo = c_lo >> 2;                           // quads per pixel of this block, first quad
   const int px0 = cb > 0 ? 0 : sl * slab, px1 = cb > 0 ? a.HW : min(a.HW, px0 + slab);
@@ -606,73 +543,21 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
     for (int k = 0; k < U; ++k) {
       const bool ok = it * 256 * U + (int)threadIdx.x + k * 256 < total;
       const int px = ok ? lpx[k] : px0, c = (q_lo + (ok ? lqs[k] : 0)) * 4;
-      if (X16 && c < a.c1) {           // 8 B of the producer's 16-bit values
-        const V4 h4 = *reinterpret_cast<const V4*>(p16 + (long)px * C + c);
-        dst[k] = make_float4((float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]);
-      } else {
-        const float* src = (!X16 && c < a.c1) ? p1 + (long)px * a.c1 + c : p2 + (long)px * a.c2 + (c - a.c1);
-        dst[k] = *reinterpret_cast<const float4*>(src);
-      }
+      const float* src = c < a.c1 ? p1 + (long)px * a.c1 + c : p2 + (long)px * a.c2 + (c - a.c1);
+      dst[k] = *reinterpret_cast<const float4*>(src);
       lpx[k] += dpix; lqs[k] += dq;
       if (lqs[k] >= Q) { lqs[k] -= Q; ++lpx[k]; }
     }
   };
   load_adv(v, 0);
   load_adv(vn, 1);
-  bool maybe_over = false;       // block-uniform: some channel partial of this block's groups admits |x| > 65504 (fp16 guard, raw planes)
-  bool norm_over = false;        // block-uniform: some channel's gamma / beta admits a normalised value beyond the fp16 range
+  // the fold of this block's groups (gn_fold.hpp). Pixel-run blocks all fold every group of their sample: the first writes the side output;
+  // channel-run blocks own their groups. Block-uniform guard switches:
+  const bool guard = a.ovf != nullptr && __is_same(T, _Float16);
+  const bool maybe_over = gn_fold_block(a.partials(), b, b2, c_lo / cpg, c_n / cpg, cb > 0 || sl == 0, dsu, dsq, lmean, lrstd) && guard;   // raw planes
+  const bool norm_over = gn_build_table(tab, lmean, lrstd, a.gamma, a.beta, C, cpg, a.HW, c_lo, c_n, guard);                              // normalised planes
   unsigned bad_raw = 0u, bad_norm = 0u;
-  {
-    const int g_lo = c_lo / cpg, ng = c_n / cpg;  // this block's groups
-    const int L = 256 / ng;                       // lanes per group (groups <= 64)
-    const int gl = threadIdx.x / L, l = threadIdx.x % L, g = g_lo + gl;
-    double su = 0.0, sq = 0.0;
-    int big = 0;
-    if (gl < ng) {
-      const int nmax = a.nslab1 > a.nslab2 ? a.nslab1 : a.nslab2;
-      const int n = cpg * nmax;
-      for (int e = l; e < n; e += L) {            // entry = (slab k, channel cc of the group); tensors may be partitioned differently
-        const int k = e / cpg, c = g * cpg + (e - k * cpg);
-        if (c < a.c1) {
-          if (k < a.nslab1) { const float* p = a.cs1 + (((long)b * a.nslab1 + k) * a.c1 + c) * 2; su += (double)p[0]; sq += (double)p[1]; big |= !(p[1] < STEDM_F16_SQ_SAFE); }
-        } else if (k < a.nslab2) {
-          const float* p = a.cs2 + (((long)b2 * a.nslab2 + k) * a.c2 + (c - a.c1)) * 2; su += (double)p[0]; sq += (double)p[1]; big |= !(p[1] < STEDM_F16_SQ_SAFE);
-        }
-      }
-    }
-    dsu[threadIdx.x] = su; dsq[threadIdx.x] = sq;
-    maybe_over = __syncthreads_or(big) != 0 && a.ovf != nullptr && __is_same(T, _Float16);
-    if (gl < ng && l == 0) {
-      double s = 0.0, q = 0.0;
-      for (int i = 0; i < L; ++i) { s += dsu[threadIdx.x + i]; q += dsq[threadIdx.x + i]; }   // fixed order
-      const double inv_n = 1.0 / ((double)cpg * a.HW);
-      const double mean = s * inv_n;
-      double var = q * inv_n - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      lmean[g] = (float)mean;
-      lrstd[g] = (float)(1.0 / sqrt(var + (double)a.eps));
-      // (pixel-run blocks all fold every group of their sample: the first writes; channel-run blocks own their groups)
-      if (a.mr && (cb > 0 || sl == 0)) { a.mr[((long)b * a.groups + g) * 2] = lmean[g]; a.mr[((long)b * a.groups + g) * 2 + 1] = lrstd[g]; }
-    }
-    __syncthreads();
-    int nb = 0;
-    const bool guard = a.ovf != nullptr && __is_same(T, _Float16);
-    const float rn = sqrtf((float)cpg * (float)a.HW);          // |x^| <= sqrt(n): the normalised planes' own switch (see gn_apply16c_kernel)
-    for (int c = c_lo + threadIdx.x; c < c_lo + c_n; c += 256) {
-      const int gc = c / cpg;
-      const float gmc = a.gamma[c], btc = a.beta[c];
-      tab[c] = lmean[gc];
-      tab[C + c] = lrstd[gc] * gmc;
-      tab[2 * C + c] = btc;
-      if (guard) nb |= !(rn * fabsf(gmc) + fabsf(btc) < 65504.f);
-    }
-    norm_over = __syncthreads_or(nb) != 0;
-  }
   const bool odd = threadIdx.x & 1;
-  auto pack4 = [](float x0, float x1, float x2, float x3) {
-    V4 h; h[0] = (T)x0; h[1] = (T)x1; h[2] = (T)x2; h[3] = (T)x3;
-    return *reinterpret_cast<uint2*>(&h);
-  };
   // lane pair exchange: the even lane keeps cursor 0's quad and receives its partner's; the odd lane keeps cursor 1's. Returns the
   // 16 B this lane stores: {even lane's quad, odd lane's quad} of the cursor it owns.
   auto pair16 = [&](uint2 q0, uint2 q1) {
@@ -697,13 +582,11 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
       float4 w = v[k];
       const bool live = k == 0 ? live0 : live1;
       if (TAIL && !live) { w = make_float4(0.f, 0.f, 0.f, 0.f); }
+      V4 lo;
       if (rh) {
-        rq[k] = pack4(w.x, w.y, w.z, w.w);
+        rq[k] = __builtin_bit_cast(uint2, split16<T>(w, rl != nullptr, lo));
         if (maybe_over) bad_raw |= f16_over4<T>(rq[k]);
-        if (rl) {
-          V4 hq = *reinterpret_cast<V4*>(&rq[k]);
-          rlq[k] = pack4(w.x - (float)hq[0], w.y - (float)hq[1], w.z - (float)hq[2], w.w - (float)hq[3]);
-        }
+        if (rl) rlq[k] = __builtin_bit_cast(uint2, lo);
       }
       const int cc = live ? c : c_lo;
       const float4 mn = *reinterpret_cast<const float4*>(tab + cc);
@@ -711,12 +594,9 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
       const float4 bt = *reinterpret_cast<const float4*>(tab + 2 * C + cc);
       w.x = (w.x - mn.x) * sc.x + bt.x; w.y = (w.y - mn.y) * sc.y + bt.y; w.z = (w.z - mn.z) * sc.z + bt.z; w.w = (w.w - mn.w) * sc.w + bt.w;
       if (a.act == 1) { w.x = silu_f(w.x); w.y = silu_f(w.y); w.z = silu_f(w.z); w.w = silu_f(w.w); }
-      oq[k] = pack4(w.x, w.y, w.z, w.w);
+      oq[k] = __builtin_bit_cast(uint2, split16<T>(w, ol != nullptr, lo));
       if (norm_over) bad_norm |= f16_over4<T>(oq[k]);
-      if (ol) {
-        V4 hq = *reinterpret_cast<V4*>(&oq[k]);
-        olq[k] = pack4(w.x - (float)hq[0], w.y - (float)hq[1], w.z - (float)hq[2], w.w - (float)hq[3]);
-      }
+      if (ol) olq[k] = __builtin_bit_cast(uint2, lo);
     }
     // my cursor: 0 on even lanes, 1 on odd lanes; the 16-B destination starts at the EVEN lane's quad of that cursor
     const int mk = odd ? 1 : 0;
@@ -725,10 +605,8 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
     const uint4 so = pair16(oq[0], oq[1]);
     if (!TAIL || mlive) *reinterpret_cast<uint4*>(oh + o) = so;
     if (ol) { const uint4 t4 = pair16(olq[0], olq[1]); if (!TAIL || mlive) *reinterpret_cast<uint4*>(ol + o) = t4; }
-    // (X16: the x1 part of the raw plane is the source itself; c1 % 8 == 0 keeps a lane pair on one side of the seam)
-    const bool rawst = !X16 || (q_lo + (qs[mk] & ~1)) * 4 >= a.c1;
-    if (rh) { const uint4 t4 = pair16(rq[0], rq[1]); if ((!TAIL || mlive) && rawst) *reinterpret_cast<uint4*>(rh + o) = t4; }
-    if (rl) { const uint4 t4 = pair16(rlq[0], rlq[1]); if ((!TAIL || mlive) && rawst) *reinterpret_cast<uint4*>(rl + o) = t4; }
+    if (rh) { const uint4 t4 = pair16(rq[0], rq[1]); if (!TAIL || mlive) *reinterpret_cast<uint4*>(rh + o) = t4; }
+    if (rl) { const uint4 t4 = pair16(rlq[0], rlq[1]); if (!TAIL || mlive) *reinterpret_cast<uint4*>(rl + o) = t4; }
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       pixs[k] += dpix; qs[k] += dq;
@@ -742,17 +620,19 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
   if (norm_over) f16_guard_commit(a.ovf, bad_norm, STEDM_F16G_NORM);
 }
 
-// Round 5: the pass on OCTETS (8 channels per thread and iteration), single-product modes. A lane's unit is 8 contiguous channels of one
-// pixel: 16 B of 16-bit source (the h half of a decoder concat in its X16 form) or 32 B of fp32 source in, ONE 16-B store of the normalised
-// plane out (plus one of the raw plane for fp32-source channels when asked) - no lane exchange, half the table reads and address
+// The pass on OCTETS (8 channels per thread and iteration) for the X16 form (stedm_gn_apply16c_x16), single-product modes. A lane's unit is 8
+// contiguous channels of one pixel: 16 B of 16-bit source (channels [0, c1), the h half of a decoder concat) or 32 B of fp32 source (x2) in,
+// ONE 16-B store of the normalised plane out (plus one of the raw plane for the fp32-source channels) - no lane exchange, half the table reads and address
 // arithmetic per byte of gn_apply16c_v8_kernel. (The quad kernel with 8-B loads for the 16-bit half ran the nine decoder concats at
 // 3.1 TB/s of 1.64 GB where the fp32 form had run 5.2 TB/s of 2.41 GB: the pass is bound by requests in flight, not by bytes.)
 // Same block partition as the quad kernel (pixel runs of all channels, or channel runs of whole groups: cb), same statistics fold.
 // PAIR (C and c1 multiples of 16): the fp32 half is loaded with a 16-B lane stride - lanes 2k / 2k + 1 own octets e / e + 1 = quads 4 of one
 // 64-B run; load 0 takes quads (0, 1) of the run, load 1 quads (2, 3), and the pair trades one quad each way (4 DPP moves) - instead of two
 // 16-B loads at a 32-B lane stride, which request every cache line twice (3.4 TB/s on that half against 5.2 for coalesced loads).
-template <typename T, bool X16, bool PAIR>
-__global__ void __launch_bounds__(256) gn_apply16c_o8_kernel(GnApplyCArgs a, int slab, int cb) {
+// (Waves per SIMD stated: the unpaired form fits the 64 registers of 8 waves, the exchange of the paired one costs a step. Left to itself
+// the compiler lands the unpaired form anywhere from 62 to 68 registers as unrelated code around it changes.)
+template <typename T, bool PAIR>
+__global__ void __launch_bounds__(256, PAIR ? 7 : 8) gn_apply16c_o8_kernel(GnApplyCArgs a, int slab, int cb) {
   typedef T V8 __attribute__((ext_vector_type(8)));
   __shared__ double dsu[256], dsq[256];
   __shared__ float lmean[64], lrstd[64];
@@ -761,9 +641,8 @@ __global__ void __launch_bounds__(256) gn_apply16c_o8_kernel(GnApplyCArgs a, int
   const int C = a.c1 + a.c2, Oall = C >> 3;
   const int cpg = C / a.groups;
   const int b2 = a.bmod > 0 ? b % a.bmod : b;
-  const float* p1 = X16 ? nullptr : a.x1 + (long)b * a.HW * a.c1;
   const float* p2 = a.x2 ? a.x2 + (long)b2 * a.HW * a.c2 : nullptr;
-  const T* p16 = X16 ? reinterpret_cast<const T*>(a.x16) + (long)b * a.HW * C : nullptr;      // rows of C channels: the raw plane itself
+  const T* p16 = reinterpret_cast<const T*>(a.x16) + (long)b * a.HW * C;      // rows of C channels: the raw plane itself
   const int c_lo = cb > 0 ? sl * cb : 0, c_n = cb > 0 ? cb : C;       // this block's channels
   const int O = c_n >> 3, o_lo = c_lo >> 3;                           // octets per pixel of this block, first octet
   const int px0 = cb > 0 ? 0 : sl * slab, px1 = cb > 0 ? a.HW : min(a.HW, px0 + slab);
@@ -781,8 +660,8 @@ __global__ void __launch_bounds__(256) gn_apply16c_o8_kernel(GnApplyCArgs a, int
     const bool ok = it * 256 + (int)threadIdx.x < total;
     const int px = ok ? lpx : px0, c = (o_lo + (ok ? loc : 0)) * 8;
     // one address pair, selected without a branch: the loads themselves are unconditional
-    const bool h16 = X16 && c < a.c1;
-    const float* f32 = (!X16 && c < a.c1) ? p1 + (long)px * a.c1 + c : p2 + (long)px * a.c2 + (c - a.c1);
+    const bool h16 = c < a.c1;
+    const float* f32 = p2 + (long)px * a.c2 + (c - a.c1);
     // (PAIR: the even lane of a pair starts at its own octet, the odd lane 16 B before its own: together 32 contiguous bytes per load)
     const char* s0 = h16 ? reinterpret_cast<const char*>(p16 + (long)px * C + c)
                          : reinterpret_cast<const char*>(f32) - ((PAIR && ok && (threadIdx.x & 1)) ? 16 : 0);
@@ -794,53 +673,11 @@ __global__ void __launch_bounds__(256) gn_apply16c_o8_kernel(GnApplyCArgs a, int
   };
   load_adv(va, 0);
   load_adv(vb, 1);
-  bool maybe_over = false, norm_over = false;       // block-uniform fp16 guard switches (raw planes / normalised planes), as in the quad kernel
+  // fold, table and the block-uniform guard switches (raw planes / normalised planes), as in the quad-pair kernel
+  const bool guard = a.ovf != nullptr && __is_same(T, _Float16);
+  const bool maybe_over = gn_fold_block(a.partials(), b, b2, c_lo / cpg, c_n / cpg, cb > 0 || sl == 0, dsu, dsq, lmean, lrstd) && guard;
+  const bool norm_over = gn_build_table(tab, lmean, lrstd, a.gamma, a.beta, C, cpg, a.HW, c_lo, c_n, guard);
   unsigned bad_raw = 0u, bad_norm = 0u;
-  {
-    const int g_lo = c_lo / cpg, ng = c_n / cpg;  // this block's groups
-    const int L = 256 / ng;                       // lanes per group (groups <= 64)
-    const int gl = threadIdx.x / L, l = threadIdx.x % L, g = g_lo + gl;
-    double su = 0.0, sq = 0.0;
-    int big = 0;
-    if (gl < ng) {
-      const int nmax = a.nslab1 > a.nslab2 ? a.nslab1 : a.nslab2;
-      const int n = cpg * nmax;
-      for (int e = l; e < n; e += L) {            // entry = (slab k, channel cc of the group); tensors may be partitioned differently
-        const int k = e / cpg, c = g * cpg + (e - k * cpg);
-        if (c < a.c1) {
-          if (k < a.nslab1) { const float* p = a.cs1 + (((long)b * a.nslab1 + k) * a.c1 + c) * 2; su += (double)p[0]; sq += (double)p[1]; big |= !(p[1] < STEDM_F16_SQ_SAFE); }
-        } else if (k < a.nslab2) {
-          const float* p = a.cs2 + (((long)b2 * a.nslab2 + k) * a.c2 + (c - a.c1)) * 2; su += (double)p[0]; sq += (double)p[1]; big |= !(p[1] < STEDM_F16_SQ_SAFE);
-        }
-      }
-    }
-    dsu[threadIdx.x] = su; dsq[threadIdx.x] = sq;
-    maybe_over = __syncthreads_or(big) != 0 && a.ovf != nullptr && __is_same(T, _Float16);
-    if (gl < ng && l == 0) {
-      double s_ = 0.0, q_ = 0.0;
-      for (int i = 0; i < L; ++i) { s_ += dsu[threadIdx.x + i]; q_ += dsq[threadIdx.x + i]; }   // fixed order
-      const double inv_n = 1.0 / ((double)cpg * a.HW);
-      const double mean = s_ * inv_n;
-      double var = q_ * inv_n - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      lmean[g] = (float)mean;
-      lrstd[g] = (float)(1.0 / sqrt(var + (double)a.eps));
-      if (a.mr && (cb > 0 || sl == 0)) { a.mr[((long)b * a.groups + g) * 2] = lmean[g]; a.mr[((long)b * a.groups + g) * 2 + 1] = lrstd[g]; }
-    }
-    __syncthreads();
-    int nb = 0;
-    const bool guard = a.ovf != nullptr && __is_same(T, _Float16);
-    const float rn = sqrtf((float)cpg * (float)a.HW);
-    for (int c = c_lo + threadIdx.x; c < c_lo + c_n; c += 256) {
-      const int gc = c / cpg;
-      const float gmc = a.gamma[c], btc = a.beta[c];
-      tab[c] = lmean[gc];
-      tab[C + c] = lrstd[gc] * gmc;
-      tab[2 * C + c] = btc;
-      if (guard) nb |= !(rn * fabsf(gmc) + fabsf(btc) < 65504.f);
-    }
-    norm_over = __syncthreads_or(nb) != 0;
-  }
   auto pack8 = [](const float (&x)[8]) {
     V8 h;
 #pragma unroll
@@ -854,7 +691,7 @@ __global__ void __launch_bounds__(256) gn_apply16c_o8_kernel(GnApplyCArgs a, int
     const bool live = !TAIL || it * 256 + (int)threadIdx.x < total;
     const int c = (o_lo + (live ? oc : 0)) * 8;
     float w[8];
-    const bool from16 = X16 && c < a.c1;
+    const bool from16 = c < a.c1;
     if (from16) {
       const V8 h8 = __builtin_bit_cast(V8, va[0]);
 #pragma unroll
@@ -871,7 +708,7 @@ __global__ void __launch_bounds__(256) gn_apply16c_o8_kernel(GnApplyCArgs a, int
       w[0] = va[0].x; w[1] = va[0].y; w[2] = va[0].z; w[3] = va[0].w; w[4] = va[1].x; w[5] = va[1].y; w[6] = va[1].z; w[7] = va[1].w;
     }
     const long o = (long)pix * Oall + o_lo + oc;
-    if (rh && !from16) {          // (X16: the 16-bit half of the raw plane is the source itself)
+    if (rh && !from16) {          // (the 16-bit half of the raw plane is the source itself)
       const uint4 rq = pack8(w);
       if (maybe_over) bad_raw |= over8(rq);
       if (live) rh[o] = rq;
@@ -896,54 +733,6 @@ __global__ void __launch_bounds__(256) gn_apply16c_o8_kernel(GnApplyCArgs a, int
   if (nfull * 256 < total) body(std::true_type{}, nfull);
   if (maybe_over) f16_guard_commit(a.ovf, bad_raw, STEDM_F16G_RAW);
   if (norm_over) f16_guard_commit(a.ovf, bad_norm, STEDM_F16G_NORM);
-}
-
-extern "C" int stedm_gn_apply16c_mr(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
-                                    const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
-                                    void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, int mm_dtype, void* stream);
-
-static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream);
-
-// The same pass when the x1 half of the concat already sits in the raw plane as 16-bit values (written there by the producing convolution's
-// epilogue: stedm_conv_args.out16_hi + out16_stride, no fp32 tensor of it exists): reads 2 B instead of 4 for those channels and writes
-// their normalised plane only. raw_hi [B][HW][c1 + c2] holds x1 in channels [0, c1) on entry and receives the plain conversion of x2 in
-// [c1, c1 + c2). cs1: the channel statistics the producer's epilogue left (of the fp32 values before their rounding). Single-product modes.
-extern "C" int stedm_gn_apply16c_x16(int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
-                                     const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
-                                     void* out_hi, void* raw_hi, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(cs1 && out_hi && raw_hi && gamma && beta, "gn_apply16c_x16: null pointer");
-  STEDM_CHECK_ARG((x2 != nullptr) == (c2 > 0) && (x2 == nullptr || cs2 != nullptr), "gn_apply16c_x16: x2/c2/cs2 mismatch");
-  const int C = c1 + c2;
-  STEDM_CHECK_ARG(C % 8 == 0 && c1 % 8 == 0 && c1 > 0 && (size_t)3 * C * sizeof(float) <= 48 * 1024, "gn_apply16c_x16: need c1, c1 + c2 multiples of 8, C <= 4096");
-  STEDM_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0, "gn_apply16c_x16: need groups <= 64 and C %% groups == 0");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_apply16c_x16: bad mm_dtype");
-  STEDM_CHECK_ARG(nslab1 > 0 && (x2 == nullptr || nslab2 > 0), "gn_apply16c_x16: nslab1 / nslab2 must be the slot counts of cs1 / cs2");
-  GnApplyCArgs a{nullptr, x2, cs1, cs2, c1, c2, x2_bmod, groups, HW, act, nslab1, x2 ? nslab2 : 0, gamma, beta, eps, out_hi, nullptr, raw_hi, nullptr, nullptr,
-                 mm_dtype == STEDM_F16 ? f16_guard_flag() : nullptr, raw_hi};
-  return gn_apply16c_launch(a, B, mm_dtype, stream);
-}
-
-extern "C" int stedm_gn_apply16c(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
-                                 const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
-                                 void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, int mm_dtype, void* stream) {
-  return stedm_gn_apply16c_mr(x1, c1, cs1, nslab1, x2, c2, cs2, nslab2, x2_bmod, gamma, beta, eps, groups, act, B, HW, out_hi, out_lo, raw_hi, raw_lo,
-                              nullptr, mm_dtype, stream);
-}
-
-extern "C" int stedm_gn_apply16c_mr(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
-                                    const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
-                                    void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(x1 && cs1 && out_hi && gamma && beta, "gn_apply16c: null pointer");
-  STEDM_CHECK_ARG((x2 != nullptr) == (c2 > 0) && (x2 == nullptr || cs2 != nullptr), "gn_apply16c: x2/c2/cs2 mismatch");
-  const int C = c1 + c2;
-  STEDM_CHECK_ARG(C % 4 == 0 && c1 % 4 == 0 && C / 4 <= 1024, "gn_apply16c: channels must be multiples of 4, C <= 4096");
-  STEDM_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0, "gn_apply16c: need groups <= 64 and C %% groups == 0");
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_apply16c: bad mm_dtype");
-  STEDM_CHECK_ARG(raw_hi || !raw_lo, "gn_apply16c: raw_lo without raw_hi");
-  STEDM_CHECK_ARG(nslab1 > 0 && (x2 == nullptr || nslab2 > 0), "gn_apply16c: nslab1 / nslab2 must be the slot counts of cs1 / cs2");
-  GnApplyCArgs a{x1, x2, cs1, cs2, c1, c2, x2_bmod, groups, HW, act, nslab1, x2 ? nslab2 : 0, gamma, beta, eps, out_hi, out_lo, raw_hi, raw_lo, mean_rstd,
-                 mm_dtype == STEDM_F16 ? f16_guard_flag() : nullptr, nullptr};
-  return gn_apply16c_launch(a, B, mm_dtype, stream);
 }
 
 static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream) {
@@ -979,26 +768,15 @@ static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream)
       if (cb > 0 && (C % cb != 0 || c1 % cb != 0 || cb % unit != 0 || cb / cpg > 64)) cb = 0;
     }
     if (cb > 0) grid = dim3(B, C / cb);
-    static const int o8_mode = getenv("STEDM_GN_O8") ? atoi(getenv("STEDM_GN_O8")) : 1;      // A/B timing only: 0 quad kernel everywhere, 1 octets for the X16 form, 2 octets wherever they apply
-    const bool o8_ok = !a.out_lo && !a.raw_lo && (cb == 0 || cb % 8 == 0);
-    if (o8_ok && ((a.x16 && o8_mode >= 1) || o8_mode >= 2)) {
-      static const bool no_pair = getenv("STEDM_GN_NOPAIR") != nullptr;      // A/B timing only
-      const bool pair = C % 16 == 0 && c1 % 16 == 0 && (cb == 0 || cb % 16 == 0) && !no_pair;
-#define GN_O8(TT, XX, PP) gn_apply16c_o8_kernel<TT, XX, PP><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb)
+    if (a.x16) {      // the octet kernel (single-product planes only: the entry has no lo planes; cb is a multiple of 8)
+      const bool pair = C % 16 == 0 && c1 % 16 == 0 && (cb == 0 || cb % 16 == 0);
       if (mm_dtype == STEDM_F16) {
-        if (a.x16) { if (pair) GN_O8(_Float16, true, true); else GN_O8(_Float16, true, false); }
-        else { if (pair) GN_O8(_Float16, false, true); else GN_O8(_Float16, false, false); }
+        if (pair) gn_apply16c_o8_kernel<_Float16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
+        else gn_apply16c_o8_kernel<_Float16, false><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
       } else {
-        if (a.x16) { if (pair) GN_O8(__bf16, true, true); else GN_O8(__bf16, true, false); }
-        else { if (pair) GN_O8(__bf16, false, true); else GN_O8(__bf16, false, false); }
+        if (pair) gn_apply16c_o8_kernel<__bf16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
+        else gn_apply16c_o8_kernel<__bf16, false><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
       }
-#undef GN_O8
-      STEDM_LAUNCH_CHECK();
-      return 0;
-    }
-    if (a.x16) {
-      if (mm_dtype == STEDM_F16) gn_apply16c_v8_kernel<_Float16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
-      else gn_apply16c_v8_kernel<__bf16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
     } else if (mm_dtype == STEDM_F16) gn_apply16c_v8_kernel<_Float16><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
     else gn_apply16c_v8_kernel<__bf16><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
     STEDM_LAUNCH_CHECK();
@@ -1011,4 +789,46 @@ static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream)
     gn_apply16c_kernel<__bf16><<<grid, 256, 0, as_stream(stream)>>>(a, slab);
   STEDM_LAUNCH_CHECK();
   return 0;
+}
+
+// The same pass when the x1 half of the concat already sits in the raw plane as 16-bit values (written there by the producing convolution's
+// epilogue: stedm_conv_args.out16_hi + out16_stride, no fp32 tensor of it exists): reads 2 B instead of 4 for those channels and writes
+// their normalised plane only. raw_hi [B][HW][c1 + c2] holds x1 in channels [0, c1) on entry and receives the plain conversion of x2 in
+// [c1, c1 + c2). cs1: the channel statistics the producer's epilogue left (of the fp32 values before their rounding). Single-product modes.
+extern "C" int stedm_gn_apply16c_x16(int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
+                                     const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                                     void* out_hi, void* raw_hi, int mm_dtype, void* stream) {
+  STEDM_CHECK_ARG(cs1 && out_hi && raw_hi && gamma && beta, "gn_apply16c_x16: null pointer");
+  STEDM_CHECK_ARG((x2 != nullptr) == (c2 > 0) && (x2 == nullptr || cs2 != nullptr), "gn_apply16c_x16: x2/c2/cs2 mismatch");
+  const int C = c1 + c2;
+  STEDM_CHECK_ARG(C % 8 == 0 && c1 % 8 == 0 && c1 > 0 && (size_t)3 * C * sizeof(float) <= 48 * 1024, "gn_apply16c_x16: need c1, c1 + c2 multiples of 8, C <= 4096");
+  STEDM_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0, "gn_apply16c_x16: need groups <= 64 and C %% groups == 0");
+  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_apply16c_x16: bad mm_dtype");
+  STEDM_CHECK_ARG(nslab1 > 0 && (x2 == nullptr || nslab2 > 0), "gn_apply16c_x16: nslab1 / nslab2 must be the slot counts of cs1 / cs2");
+  GnApplyCArgs a{nullptr, x2, cs1, cs2, c1, c2, x2_bmod, groups, HW, act, nslab1, x2 ? nslab2 : 0, gamma, beta, eps, out_hi, nullptr, raw_hi, nullptr, nullptr,
+                 mm_dtype == STEDM_F16 ? f16_guard_flag() : nullptr, raw_hi};
+  return gn_apply16c_launch(a, B, mm_dtype, stream);
+}
+
+extern "C" int stedm_gn_apply16c_mr(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
+                                    const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                                    void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, int mm_dtype, void* stream) {
+  STEDM_CHECK_ARG(x1 && cs1 && out_hi && gamma && beta, "gn_apply16c: null pointer");
+  STEDM_CHECK_ARG((x2 != nullptr) == (c2 > 0) && (x2 == nullptr || cs2 != nullptr), "gn_apply16c: x2/c2/cs2 mismatch");
+  const int C = c1 + c2;
+  STEDM_CHECK_ARG(C % 4 == 0 && c1 % 4 == 0 && C / 4 <= 1024, "gn_apply16c: channels must be multiples of 4, C <= 4096");
+  STEDM_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0, "gn_apply16c: need groups <= 64 and C %% groups == 0");
+  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_apply16c: bad mm_dtype");
+  STEDM_CHECK_ARG(raw_hi || !raw_lo, "gn_apply16c: raw_lo without raw_hi");
+  STEDM_CHECK_ARG(nslab1 > 0 && (x2 == nullptr || nslab2 > 0), "gn_apply16c: nslab1 / nslab2 must be the slot counts of cs1 / cs2");
+  GnApplyCArgs a{x1, x2, cs1, cs2, c1, c2, x2_bmod, groups, HW, act, nslab1, x2 ? nslab2 : 0, gamma, beta, eps, out_hi, out_lo, raw_hi, raw_lo, mean_rstd,
+                 mm_dtype == STEDM_F16 ? f16_guard_flag() : nullptr, nullptr};
+  return gn_apply16c_launch(a, B, mm_dtype, stream);
+}
+
+extern "C" int stedm_gn_apply16c(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
+                                 const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                                 void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, int mm_dtype, void* stream) {
+  return stedm_gn_apply16c_mr(x1, c1, cs1, nslab1, x2, c2, cs2, nslab2, x2_bmod, gamma, beta, eps, groups, act, B, HW, out_hi, out_lo, raw_hi, raw_lo,
+                              nullptr, mm_dtype, stream);
 }

@@ -190,9 +190,10 @@ def gn_stats_k(C, HW):
     return (slab + npl - 1) // npl
 
 
-def apply16c_geometry(B, HW, c1, c2, groups, hilo, x16, o8_mode=1):
+def apply16c_geometry(B, HW, c1, c2, groups, hilo, x16):
     """(kernel, slab, cb, pair) of gn_apply16c_launch: kernel in {quad, v8, o8}; slab = pixels per pixel-run block; cb = channels per
-    channel-run block (0: pixel runs)"""
+    channel-run block (0: pixel runs). The X16 entry (single-product only, c1 and C multiples of 8 by its argument check) takes the octet
+    kernel, every other 8-wide shape the quad-pair kernel."""
     C = c1 + c2
     want = (128 * 256 + C - 1) // C
     per_sample = max((HW + want - 1) // want, (768 + B - 1) // B)
@@ -212,8 +213,8 @@ def apply16c_geometry(B, HW, c1, c2, groups, hilo, x16, o8_mode=1):
                 cb = t
         if cb and (C % cb or c1 % cb or cb % unit or cb // cpg > 64):
             cb = 0
-    o8_ok = not hilo and (cb == 0 or cb % 8 == 0)
-    if o8_ok and ((x16 and o8_mode >= 1) or o8_mode >= 2):
+    if x16:
+        assert not hilo and cb % 8 == 0
         return "o8", slab, cb, C % 16 == 0 and c1 % 16 == 0 and (cb == 0 or cb % 16 == 0)
     return "v8", slab, cb, False
 
@@ -712,11 +713,11 @@ FWD = [
     ("v8_pixel_notail", 3, 32, 32, 384, 128, 0, 32, "f32", 1, 1),
     # the same with C = 640: 4 x 160 = 640 quads = one full iteration + a tail of 128
     ("v8_pixel_full_tail", 3, 32, 32, 512, 128, 0, 32, "f32", 4, 1),
-    # hi + lo planes: o8_ok is false, the 8-wide kernel whatever STEDM_GN_O8 says; HW = 256, B * C / t >= 768 for no run t -> 1-pixel runs
+    # hi + lo planes through the 8-wide kernel (lane pairs exchange four quads); HW = 256, B * C / t >= 768 for no run t -> 1-pixel runs
     ("v8_hilo", 2, 16, 16, 512, 128, 0, 32, "hilo", 4, 1),
     # one group: L = 256 fold lanes, cpg = 16
     ("v8_g1", 2, 8, 8, 8, 8, 0, 1, "hilo", 1, 1),
-    # cpg = 5 (the table is per channel: no quad / group alignment needed); C = 40 is no multiple of 16: the non-PAIR octet form under STEDM_GN_O8 = 2
+    # cpg = 5 (the table is per channel: no quad / group alignment needed); C = 40, c1 = 24: multiples of 8, not of 16
     ("v8_cpg5", 2, 8, 8, 24, 16, 0, 8, "f32", 1, 1),
     # HW = 64 <= 256, C = 512, cpg = 16: t = 128 gives 200 * 4 = 800 >= 768 blocks -> cb = 128: four channel-run blocks of 8 groups per sample
     ("v8_chan", 200, 8, 8, 256, 256, 0, 32, "f32", 1, 1),
@@ -913,13 +914,13 @@ def x16_words(x1, dtype):
     return flat(x1).to(dtype).contiguous().view(torch.int16)
 
 
-def emu_forward(case, x1, x2, gamma, beta, eps, act, dtype, defects=(), o8_mode=1):
+def emu_forward(case, x1, x2, gamma, beta, eps, act, dtype, defects=()):
     """gn_chan_stats (x2) -> fold -> the apply kernel of the case's form, all emulated: the outputs a GPU run of the case produces"""
     B, HW, c1, c2, bmod, groups, form, ns1, ns2 = case_dims(case)
     cs1 = emu_chan_stats(x1, ns1, defects)
     cs2 = emu_chan_stats(x2, ns2, defects) if c2 else None
     mr = emu_fold(cs1, cs2, bmod, groups, HW, eps, defects)
-    geom = apply16c_geometry(B, HW, c1, c2, groups, form == "hilo", form == "x16", o8_mode)
+    geom = apply16c_geometry(B, HW, c1, c2, groups, form == "hilo", form == "x16")
     raw16 = None
     if form == "x16":
         raw16 = torch.full((B, HW, c1 + c2), FILL16, dtype=torch.int16)

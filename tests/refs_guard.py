@@ -22,7 +22,7 @@ OVER = 65520.0
 RAW, NORM, CONV_OUT16, S2D, CAST, CONV_SRC = 1, 2, 4, 8, 16, 32
 
 # the block-uniform switch of stedm_gn_apply16c's raw planes: the per-element test runs only when a channel partial's sum of squares
-# reaches this value (gn.hip: STEDM_F16_SQ_SAFE)
+# reaches this value (gn_fold.hpp: STEDM_F16_SQ_SAFE)
 SQ_SAFE = 4.0e9
 # a value whose fp32 square passes SQ_SAFE while its fp16 cast is finite: the switch is on and nothing may be flagged
 SWITCH_ON_FINITE = 63300.0

@@ -17,39 +17,38 @@ the kernel must store exactly that value in any summation order. The GroupNorm p
 
 Site -> case, from the source line of each f16_guard_commit and the rule that sends the case there:
 
-  gn.hip:273   gn_apply16_kernel, CAST (gamma == NULL)          test_cast_plain_conversion[apply16-*]
-  gn.hip:273   gn_apply16_kernel, NORM (gamma given)            test_norm_gn_apply16
-  gn.hip:347   gn_chan_stats_kernel<CAST>                       test_cast_plain_conversion[chan_stats16-*]
-  gn.hip:555/6 gn_apply16c_kernel (quad): c1 % 8 != 0           test_gn_apply16c_raw / _norm [quad]
-  gn.hip:741/2 gn_apply16c_v8_kernel: C % 8 == 0, c1 % 8 == 0, 3 C floats <= 48 KiB; pixel runs (cb == 0: B * C / t < 768 for every
+  gn.hip:263   gn_apply16_kernel, CAST (gamma == NULL)          test_cast_plain_conversion[apply16-*]
+  gn.hip:263   gn_apply16_kernel, NORM (gamma given)            test_norm_gn_apply16
+  gn.hip:335   gn_chan_stats_kernel<CAST>                       test_cast_plain_conversion[chan_stats16-*]
+  gn.hip:493/4 gn_apply16c_kernel (quad): c1 % 8 != 0           test_gn_apply16c_raw / _norm [quad]
+  gn.hip:619/20 gn_apply16c_v8_kernel: C % 8 == 0, c1 % 8 == 0, 3 C floats <= 48 KiB; pixel runs (cb == 0: B * C / t < 768 for every
                admissible run t) [v8_pixel]; channel runs (HW <= 256, B * C / 128 >= 768: cb = 128) [v8_chan, v8_chan_bmod]; the hi + lo
-               planes keep this kernel (o8_ok needs out_lo == raw_lo == NULL) [v8_hilo]
-  gn.hip:741/2 gn_apply16c_v8_kernel<X16>: not reached by default (STEDM_GN_O8 = 0 is an A/B timing switch); same body as above
-  gn.hip:897/8 gn_apply16c_o8_kernel<X16>: stedm_gn_apply16c_x16; PAIR when C, c1 (and cb) are multiples of 16 [x16_pair_chan,
-               x16_pair_pixel], else not [x16_unpaired]. (The fp32-source octet form needs STEDM_GN_O8 = 2, an A/B timing switch.)
+               planes take this kernel too [v8_hilo]
+  gn.hip:734/5 gn_apply16c_o8_kernel: stedm_gn_apply16c_x16; PAIR when C, c1 (and cb) are multiples of 16 [x16_pair_chan,
+               x16_pair_pixel], else not [x16_unpaired]
   pack.hip:355 space_to_depth16_kernel                          test_s2d
   conv_igemm.hip:267  fp32-source loader (src1, no src16)       test_conv_src
   conv_igemm_dma.inc:363   128-row 1x1 LDS kernel (no fragment pack)          test_conv_out16[lds_1x1-side]
   conv_igemm_dma9.inc:288  128-row 3x3 LDS kernel (no fragment pack)          test_conv_out16[lds_3x3_partial_tile-side]
-  conv_rs.inc:1429  generic row loop (fp32 output + side output)              test_conv_out16[rs3x3_ragged-side]
+  conv_rs.inc:1425  generic row loop (fp32 output + side output)              test_conv_out16[rs3x3_ragged-side]
                     ... its scalar tail (cout % 4 != 0)                        test_conv_out16[rs3x3_tail-side]
                     fast path (out == NULL, statistics)                        test_conv_out16[rs3x3_ragged-only]
                     ... into a wider plane (out16_stride)                      test_conv_out16[rs3x3_ragged-wide]
                     sub-pixel scatter (CONV_UP_SUBPIXEL rows, 4 parities)      test_conv_out16[sub_full-side / -only]
-  conv_rs.inc:1151  lean 8-channel loop (out == NULL, no res / emb / stats)   test_conv_out16_flat[lean_tiled], [lean_npers] under
+  conv_rs.inc:1152  lean 8-channel loop (out == NULL, no res / emb / stats)   test_conv_out16_flat[lean_tiled], [lean_npers] under
                     STEDM_CONV_NO_NPERS
-  conv_rs.inc:932   N-persistent form, 16-bit store from the accumulators     test_conv_out16_flat[lean_npers]
-  conv_rs.inc:932   N-persistent form, q / k and v^T planes                   test_conv_out16_qkv[qkv_npers]
-  conv_rs.inc:1121  qkv epilogue of the tiled form (q / k rows, v transposed) test_conv_out16_qkv[qkv_tiled], [qkv_npers] under
+  conv_rs.inc:933   N-persistent form, 16-bit store from the accumulators     test_conv_out16_flat[lean_npers]
+  conv_rs.inc:933   N-persistent form, q / k and v^T planes                   test_conv_out16_qkv[qkv_npers]
+  conv_rs.inc:1122  qkv epilogue of the tiled form (q / k rows, v transposed) test_conv_out16_qkv[qkv_tiled], [qkv_npers] under
                     STEDM_CONV_NO_NPERS
-  conv_rs.inc:1507  split-K reduce pass                                        test_conv_out16[splitk3x3_b2-side / -only]
+  conv_rs.inc:1503  split-K reduce pass                                        test_conv_out16[splitk3x3_b2-side / -only]
                     ... as a call of its own (stedm_conv_finish)               test_conv_out16_finish
-  conv_rs.inc:1063  LayerNorm epilogue (ln_after)                              test_norm_layernorm_epilogue
-  conv_rs.inc:1430  riding GroupNorm, in-tile (gn_tile: the plain 3x3 kinds without a K split, i.e. tiles for 3/4 of the chip; HW divides
+  conv_rs.inc:1064  LayerNorm epilogue (ln_after)                              test_norm_layernorm_epilogue
+  conv_rs.inc:1426  riding GroupNorm, in-tile (gn_tile: the plain 3x3 kinds without a K split, i.e. tiles for 3/4 of the chip; HW divides
                     256; cout % 128 == 0; cpg % 4 == 0)                        test_norm_riding_groupnorm[in_tile]
                     ... cooperative across the tiles of a sample (gn_coop: HW = 2 .. 4 tiles, cout = 128, the words handed over)
                                                                                test_norm_riding_groupnorm[coop]
-  conv_rs.inc:1567  riding GroupNorm on the split-K reduce pass                test_norm_riding_groupnorm[splitk]
+  conv_rs.inc:1558  riding GroupNorm on the split-K reduce pass                test_norm_riding_groupnorm[splitk]
   composite         conv (split K, chan_stats, one element at OVER) -> gn_apply16c(raw=): RAW from the epilogue's partials
                                                                                test_composite_conv_statistics_switch_the_raw_test_on
 
@@ -308,7 +307,7 @@ GN16C = [
     # HW = 64 <= 256, C = 512, cpg = 16: t = 128 gives 200 * 4 = 800 >= 768 blocks -> cb = 128: four channel-run blocks of 8 groups per sample
     ("v8_chan", 200, 8, 8, 256, 256, 0, "f32"),
     ("v8_chan_bmod", 200, 8, 8, 256, 256, 100, "f32"),
-    # hi + lo planes: o8_ok is false, the 8-wide kernel whatever STEDM_GN_O8 says
+    # hi + lo planes through the 8-wide kernel
     ("v8_hilo", 2, 16, 16, 512, 128, 0, "hilo"),
     # stedm_gn_apply16c_x16 -> the octet kernel. C = 2048, c1 = 1024 multiples of 16, HW = 64, cpg = 64: t = 128 gives 48 * 16 = 768 -> cb = 128, PAIR
     ("x16_pair_chan", 48, 8, 8, 1024, 1024, 24, "x16"),

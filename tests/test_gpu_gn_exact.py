@@ -12,7 +12,7 @@ its words. tests/test_gn_refs_cpu.py holds fp32 emulations of the kernels to the
 Kernel instantiation -> case. The branch rules are RESTATED in Python (refs_gn.apply16c_geometry / gn_bwd_fused_cb / chan_stats_qbs) and the
 mapping is asserted against that restatement on the CPU tier (test_geometry_names_every_form), as the guard tests do: a change of a launch
 heuristic in gn.hip / bwd.hip has to be restated there, or cases silently move to other instantiations. Every stedm_gn_apply16c case runs
-single-product and hi + lo in both tiers (refs_gn.forms; hi + lo sends the shapes of the 8-wide kernel there under every switch value):
+single-product and hi + lo in both tiers (refs_gn.forms; both modes of an 8-wide shape run in the quad-pair kernel):
 
   gn_scale_shift_kernel<true>                cpg, c1, c2 multiples of 4                      test_scale_shift[vec4*]
   gn_scale_shift_kernel<false>               cpg = 6 / c1 = 6                                test_scale_shift[scalar*]
@@ -26,23 +26,17 @@ single-product and hi + lo in both tiers (refs_gn.forms; hi + lo sends the shape
   gn_apply16c_kernel<_Float16 / __bf16>      c1 % 8 != 0: quad_cpg2, quad_cpg6 (per-element group lookup), quad_cpg4_c1_4 (cpg % 4 == 0),
                                              quad_g64 (L = 4 lanes per group), quad_two_passes (1538 quads per block: the loop runs twice,
                                              second load_batch, cursor advance and wrap; the others have <= 1024 and run it once)
-  gn_apply16c_v8_kernel<T, false>            pixel runs: v8_pixel_tail_only (96 quads < 512), v8_pixel_notail (4 px x 128 quads = 512),
+  gn_apply16c_v8_kernel<T>                   pixel runs: v8_pixel_tail_only (96 quads < 512), v8_pixel_notail (4 px x 128 quads = 512),
                                              v8_pixel_full_tail (640 = 512 + 128), v8_hilo (hi + lo keeps this kernel), v8_g1, v8_cpg5;
                                              channel runs cb = 128: v8_chan, v8_chan_bmod (hi + lo)
-  gn_apply16c_o8_kernel<T, true, true>       stedm_gn_apply16c_x16, PAIR: x16_pair_chan (cb = 128, bmod, nslab1 = 4 nslab2), x16_pair_pixel
+  gn_apply16c_o8_kernel<T, true>             stedm_gn_apply16c_x16, PAIR: x16_pair_chan (cb = 128, bmod, nslab1 = 4 nslab2), x16_pair_pixel
                                              (tail only), x16_pixel_notail (4 px x 64 octets = 256), x16_c2_0, x16_straddle (1024 + 512,
                                              cpg 48: groups across the seam), x16_g64
-  gn_apply16c_o8_kernel<T, true, false>      c1 = 136: no multiple of 16: x16_unpaired
-  gn_apply16c_v8_kernel<T, true>             STEDM_GN_O8 = 0 (timing switch, read once per process): test_timing_switch_forms[0], in ONE child
-  gn_apply16c_o8_kernel<T, false, true / false>  STEDM_GN_O8 = 2: test_timing_switch_forms[2] (v8_pixel_notail, v8_pixel_tail_only PAIR; v8_cpg5 not)
+  gn_apply16c_o8_kernel<T, false>            c1 = 136: no multiple of 16: x16_unpaired
   gn_bwd_fused_kernel<T, 2 / 4 / 8>          fused_ppt2, fused_ppt4 / fused_ragged (10 x 10) / fused_g64, fused_ppt8 (ppt 7)
   gn_bwd_stats / _fold / _apply_kernel<T>    no admissible channel run: chain_c1536 (1024 + 512), chain_64x64 (ppt > 8), chain_ragged_cpg6
   gn_bwd_param_kernel                        every backward case; accumulate on and off
 """
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
@@ -54,7 +48,6 @@ torch.set_grad_enabled(False)
 
 NAN = float("nan")
 FILL16 = R.FILL16
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -325,36 +318,6 @@ def test_scale_shift(dev, case):
     r = (R.ratio((sc.double() - sc64).abs(), e_sc), R.ratio((sh.double() - sh64).abs(), e_sh))
     print(f"gn_scale_shift {name}: worst err/bound scale {r[0]:.3f} shift {r[1]:.3f}")
     assert max(r) < 1.0
-
-
-# ================================================================================================ the forms behind STEDM_GN_O8 (one child each)
-_CHILD = """
-import sys
-sys.path.insert(0, sys.argv[1])
-import torch
-from tests import refs_gn as R
-from tests import test_gpu_gn_exact as T
-dev = torch.device("cuda:0")
-for name in sys.argv[2:]:
-    case = R.FWD[R.FWD_IDS.index(name)]
-    for prec in ("f16", "bf16"):
-        T._exact_case(dev, case, prec)
-    print("GN_O8_CHILD_OK", name, flush=True)
-"""
-SWITCH = {"0": ["x16_pixel_notail", "x16_unpaired", "x16_g64"], "2": ["v8_pixel_notail", "v8_pixel_tail_only", "v8_cpg5"]}
-
-
-@pytest.mark.parametrize("mode", ["0", "2"])
-def test_timing_switch_forms(dev, mode):
-    """STEDM_GN_O8 is read once per process: one fresh child per value runs three exact-pattern cases through the instantiations the default
-    never launches - 0: gn_apply16c_v8_kernel<T, true> on the X16 cases; 2: gn_apply16c_o8_kernel<T, false, PAIR / no PAIR> on fp32 sources."""
-    for name in SWITCH[mode]:
-        c = R.FWD[R.FWD_IDS.index(name)]
-        k = R.apply16c_geometry(c[1], c[2] * c[3], c[4], c[5], c[7], False, c[8] == "x16", int(mode))[0]
-        assert k == ("v8" if mode == "0" else "o8")
-    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT] + SWITCH[mode], env=dict(os.environ, STEDM_GN_O8=mode), capture_output=True, text=True,
-                       timeout=180)
-    assert r.returncode == 0 and r.stdout.count("GN_O8_CHILD_OK") == 3, (r.stdout[-1500:], r.stderr[-3000:])
 
 
 # ================================================================================================ offset sweep
