@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 26
+#define STEDM_ABI_VERSION 27
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -152,6 +152,16 @@ int stedm_gn_apply16c(const float* x1, int c1, const float* cs1, int nslab1, con
 int stedm_gn_apply16c_mr(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
                          const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
                          void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, int mm_dtype, void* stream);
+/* The same pass for out_layers[0] of a use_scale_shift_norm ResBlock (openaimodel.py:199, 280-284): act(GroupNorm(x1) * (1 + scale) + shift),
+ * scale, shift = th.chunk(emb_out, 2, dim=1). Sample b reads scale[c] = film[b * film_bstride + film_off + c] and
+ * shift[c] = film[b * film_bstride + film_off + C + c]; film_bstride 0: one row for every sample. Rounding order, fp32:
+ * u = (x - mean) * (rstd * gamma) + beta, then z = u * (1 + scale) + shift. One source tensor (x2 NULL, c2 0), C % 8 == 0, C <= 2456: the
+ * 8-wide table kernel in the launch geometry of stedm_gn_apply16c; any other shape is an argument error. hi or hi + lo planes, f16 or
+ * bf16, raw planes and mean_rstd as in stedm_gn_apply16c_mr. The fp16 range guard's switch is taken on the sample's effective affine. */
+int stedm_gn_apply16c_film(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
+                           const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                           void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, const float* film, long film_bstride,
+                           int film_off, int mm_dtype, void* stream);
 /* The same pass when the h half of the concat already sits in the raw plane as 16-bit values, written there by the producing convolution
  * (stedm_conv_args.out16_hi + out16_stride; no fp32 tensor of it exists): raw_hi [B][HW][c1 + c2] holds x1 in channels [0, c1) on entry
  * and receives the plain conversion of x2 (fp32, [B or x2_bmod][HW][c2]) in [c1, c1 + c2); out_hi receives act(GroupNorm([x1|x2])).
@@ -627,6 +637,15 @@ int stedm_gn_bwd(const float* x1, int c1, const float* x2, int c2, const float* 
                  const float* beta, int groups, int act, const float* dA, const float* add, int B, int HW, float* ws,
                  float* dx1, int acc1, float* dx2, int acc2, void* dx16_hi, void* dx16_lo, int mm_dtype, float* dgamma,
                  float* dbeta, int acc_param, void* stream);
+/* stedm_gn_bwd for the FiLM form above (one source tensor): with z = u (1 + s) + sh, u = xhat gamma + beta and dy = dA act'(z), dx is the
+ * GroupNorm backward with gamma (1 + s_b) in place of gamma; d_film row b receives dscale[c] = gamma_c sum dy xhat + beta_c sum dy at
+ * d_film[b * d_film_bstride + d_film_off + c] and dshift[c] = sum dy at ... + C + c (the order of th.chunk); dgamma[c] (+)= sum_b (1 + s_bc)
+ * sum dy xhat, dbeta[c] (+)= sum_b (1 + s_bc) sum dy. film / film_bstride / film_off as in stedm_gn_apply16c_film, 16-byte aligned
+ * (multiples of 4 floats). Fixed summation order, no atomics. ws: stedm_gn_bwd_ws_floats(B, HW, C, groups) floats. */
+int stedm_gn_bwd_film(const float* x1, int c1, const float* mean_rstd, const float* gamma, const float* beta, int groups, int act,
+                      const float* film, long film_bstride, int film_off, const float* dA, const float* add, int B, int HW, float* ws,
+                      float* dx1, int acc1, void* dx16_hi, void* dx16_lo, int mm_dtype, float* dgamma, float* dbeta, int acc_param,
+                      float* d_film, long d_film_bstride, int d_film_off, void* stream);
 long stedm_gn_bwd_ws_floats(int B, int HW, int C, int groups);
 /* 16-bit NHWC planes [B][Hs][Ws][C] -> transposed im2col [(tap*C + c)][Ppad] over the conv's output grid (mode 0 stride 1,
  * 1 nearest-2x upsample + conv (openaimodel.py:129-131), 2 stride 2 pad 1 (:164-166)); pixels >= P are zero. */

@@ -53,11 +53,22 @@ struct GnBwdArgs {
   const float* add;   // optional [B][HW][C] added to dx (the residual / skip branch of the block)
   float* dx1; float* dx2; int acc1, acc2;
   void* o_hi; void* o_lo;   // optional 16-bit planes of dx (operand of the producer convolution's dgrad / wgrad)
+  const float* film; long film_bs; int film_off;   // FILM kernels (stedm_gn_bwd_film): sample b's row film + b * film_bs + film_off = {scale[C], shift[C]}
 };
+
+// FiLM form (use_scale_shift_norm, openaimodel.py:280-284): z = u (1 + s) + sh with u = xh gamma + beta, the two steps of the forward's
+// gn_film; dy = dA silu'(z); dx is the GroupNorm backward with the per-sample weight gamma (1 + s_b) in place of gamma. The FILM = false
+// instantiations compile to what they were.
+template <bool FILM>
+__device__ __forceinline__ float gn_bwd_arg(float xh, float ga, float be, float op, float sh) {
+  if constexpr (FILM) return (xh * ga + be) * op + sh;
+  else return xh * ga + be;
+}
 
 // grid (B, kGnBwdSlab-pixel slabs, blocks of 64 channel quads). 64-pixel slabs: with 256 the grid of a 16x16 x 512-channel tensor at batch 64
 // was 128 blocks (half the chip idle, 64 dependent pixel steps per thread)
 constexpr int kGnBwdSlab = 64;
+template <bool FILM = false>
 __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(GnBwdArgs a) {
   __shared__ float cpart[256 * 8];
   const int b = blockIdx.x, slab = blockIdx.y, nslab = gridDim.y;
@@ -68,12 +79,13 @@ __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(GnBwdArgs a) {
   const int px0 = min(a.HW, slab * kGnBwdSlab), px1 = min(a.HW, px0 + kGnBwdSlab);
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   if (tp < npl) {
-    float mean[4], rstd[4], ga[4], be[4];
+    float mean[4], rstd[4], ga[4], be[4], op[4] = {1.f, 1.f, 1.f, 1.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int g = (c + j) / cpg;
       mean[j] = a.mr[((long)b * a.groups + g) * 2]; rstd[j] = a.mr[((long)b * a.groups + g) * 2 + 1];
       ga[j] = a.gamma[c + j]; be[j] = a.beta[c + j];
+      if constexpr (FILM) { const float* fr = a.film + (long)b * a.film_bs + a.film_off; op[j] = 1.0f + fr[c + j]; sh[j] = fr[C + c + j]; }
     }
     const float* px = c < a.c1 ? a.x1 + (long)b * a.HW * a.c1 + c : a.x2 + (long)b * a.HW * a.c2 + (c - a.c1);
     const int ldx = c < a.c1 ? a.c1 : a.c2;
@@ -85,7 +97,7 @@ __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(GnBwdArgs a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float xh = (xs[j] - mean[j]) * rstd[j];
-        const float dy = a.act ? ds[j] * silu_grad(xh * ga[j] + be[j]) : ds[j];
+        const float dy = a.act ? ds[j] * silu_grad(gn_bwd_arg<FILM>(xh, ga[j], be[j], op[j], sh[j])) : ds[j];
         s1[j] += dy; s2[j] += dy * xh;
       }
     }
@@ -108,15 +120,18 @@ __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(GnBwdArgs a) {
 }
 
 // grid B: slab partials -> bc[B][C][2] (per-sample channel sums) and gm[B][groups][2]
+// film_row != NULL: the sums are weighted by the sample's gamma (1 + scale) (row of sample b at film_row + b * film_bs)
 __global__ void __launch_bounds__(256) gn_bwd_fold_kernel(const float* __restrict__ part, int nslab, int C, int groups, int HW,
-                                                          const float* __restrict__ gamma, float* __restrict__ bc, float* __restrict__ gm) {
+                                                          const float* __restrict__ gamma, float* __restrict__ bc, float* __restrict__ gm,
+                                                          const float* __restrict__ film_row = nullptr, long film_bs = 0) {
   extern __shared__ float sm[];   // [C][2] gamma-weighted sums
   const int b = blockIdx.x, cpg = C / groups;
   for (int c = threadIdx.x; c < C; c += 256) {
     float u = 0.f, w = 0.f;
     for (int k = 0; k < nslab; ++k) { const float* p = part + (((long)b * nslab + k) * C + c) * 2; u += p[0]; w += p[1]; }
     bc[((long)b * C + c) * 2] = u; bc[((long)b * C + c) * 2 + 1] = w;
-    sm[c * 2] = u * gamma[c]; sm[c * 2 + 1] = w * gamma[c];
+    const float gmc = film_row ? gamma[c] * (1.0f + film_row[(long)b * film_bs + c]) : gamma[c];
+    sm[c * 2] = u * gmc; sm[c * 2 + 1] = w * gmc;
   }
   __syncthreads();
   if (threadIdx.x < groups) {
@@ -157,8 +172,41 @@ __global__ void __launch_bounds__(256) gn_bwd_param_kernel(const float* __restri
   }
 }
 
+// The FiLM form of the parameter pass, from the same bc[b][c] = {U = sum dy, W = sum dy xhat} (z = (xhat gamma + beta)(1 + s) + sh):
+//   dshift[b][c] = U;  dscale[b][c] = gamma_c W + beta_c U;  dgamma[c] (+)= sum_b (1 + s_bc) W;  dbeta[c] (+)= sum_b (1 + s_bc) U
+// dscale / dshift go to row b of the embedding-gradient matrix dE (row stride de_ld): dE[b][de_off + c] and dE[b][de_off + C + c], the
+// order of th.chunk. Same grid and lane walk as gn_bwd_param_kernel: a lane takes samples bl, bl + 16, ... in order, the 16 lanes join
+// in lane order - no atomics, a fixed order.
+__global__ void __launch_bounds__(256) gn_bwd_film_param_kernel(const float* __restrict__ bc, int B, int C, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, const float* __restrict__ film, long film_bs,
+                                                                int film_off, float* __restrict__ dE, long de_ld, int de_off,
+                                                                float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
+  __shared__ float red[16][16][2];
+  const int cl = threadIdx.x & 15, bl = threadIdx.x >> 4, c = blockIdx.x * 16 + cl;
+  float u = 0.f, w = 0.f;
+  if (c < C) {
+    const float gmc = gamma[c], btc = beta[c];
+    for (int b = bl; b < B; b += 16) {
+      const float2 v = *reinterpret_cast<const float2*>(bc + ((long)b * C + c) * 2);
+      const float op = 1.0f + film[(long)b * film_bs + film_off + c];
+      dE[(long)b * de_ld + de_off + c] = gmc * v.y + btc * v.x;
+      dE[(long)b * de_ld + de_off + C + c] = v.x;
+      u += op * v.x; w += op * v.y;
+    }
+  }
+  red[bl][cl][0] = u; red[bl][cl][1] = w;
+  __syncthreads();
+  if (bl == 0 && c < C) {
+    float su = 0.f, sw = 0.f;
+#pragma unroll
+    for (int l = 0; l < 16; ++l) { su += red[l][cl][0]; sw += red[l][cl][1]; }   // fixed order
+    dbeta[c] = (accumulate ? dbeta[c] : 0.f) + su;
+    dgamma[c] = (accumulate ? dgamma[c] : 0.f) + sw;
+  }
+}
+
 // dx = rstd * (gamma*dy - m1 - xhat*m2) (+ add); grid (B, ceil(HW*Q / 1024)), one float4 per thread x 4
-template <typename T>
+template <typename T, bool FILM = false>
 __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(GnBwdArgs a) {
   typedef T V4 __attribute__((ext_vector_type(4)));
   const int b = blockIdx.x, C = a.c1 + a.c2, Q = C >> 2, cpg = C / a.groups;
@@ -191,11 +239,19 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(GnBwdArgs a) {
       }
     }
     float r[4];
+    float ops[4] = {1.f, 1.f, 1.f, 1.f}, shs[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (FILM) {
+      const float* fr = a.film + (long)b * a.film_bs + a.film_off;
+      const float4 s4 = *reinterpret_cast<const float4*>(fr + c), h4 = *reinterpret_cast<const float4*>(fr + C + c);
+      ops[0] = 1.0f + s4.x; ops[1] = 1.0f + s4.y; ops[2] = 1.0f + s4.z; ops[3] = 1.0f + s4.w;
+      shs[0] = h4.x; shs[1] = h4.y; shs[2] = h4.z; shs[3] = h4.w;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float xh = (xs[j] - mean[j]) * rstd[j];
-      const float dy = a.act ? ds[j] * silu_grad(xh * gas[j] + bes[j]) : ds[j];
-      r[j] = rstd[j] * (gas[j] * dy - m1[j] - xh * m2[j]);
+      const float dy = a.act ? ds[j] * silu_grad(gn_bwd_arg<FILM>(xh, gas[j], bes[j], ops[j], shs[j])) : ds[j];
+      if constexpr (FILM) r[j] = rstd[j] * ((gas[j] * ops[j]) * dy - m1[j] - xh * m2[j]);
+      else r[j] = rstd[j] * (gas[j] * dy - m1[j] - xh * m2[j]);
     }
     if (a.add) {
       const float4 av = *reinterpret_cast<const float4*>(a.add + o);
@@ -232,7 +288,7 @@ struct GnBwdFusedArgs {
   int cb;
 };
 
-template <typename T, int PPT>
+template <typename T, int PPT, bool FILM = false>
 __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
   typedef T V4 __attribute__((ext_vector_type(4)));
   __shared__ float red[512 * 8 + 2 * 288 + 2 * 72];  // [npl][qb][8] lane partials | [cb][2] gamma-weighted sums | [groups of the block][2]
@@ -246,7 +302,7 @@ __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
   const float* px = first ? a.x1 + (long)b * a.HW * a.c1 + c : a.x2 + (long)b * a.HW * a.c2 + (c - a.c1);
   const int ldx = first ? a.c1 : a.c2;
   const float* pd = a.dA + (long)b * a.HW * C + c;
-  float mean[4], rstd[4], ga[4], be[4];
+  float mean[4], rstd[4], ga[4], be[4], op[4] = {1.f, 1.f, 1.f, 1.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
   float xh[PPT][4], dy[PPT][4];
   float4 av[PPT];
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
@@ -266,6 +322,7 @@ __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
       const int g = (c + j) / cpg;
       mean[j] = a.mr[((long)b * a.groups + g) * 2]; rstd[j] = a.mr[((long)b * a.groups + g) * 2 + 1];
       ga[j] = a.gamma[c + j]; be[j] = a.beta[c + j];
+      if constexpr (FILM) { const float* fr = a.film + (long)b * a.film_bs + a.film_off; op[j] = 1.0f + fr[c + j]; sh[j] = fr[C + c + j]; }
     }
     if (a.add) {     // the residual branch's gradient is needed after the fold: in flight across it
 #pragma unroll
@@ -281,7 +338,7 @@ __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         xh[k][j] = (xi[j] - mean[j]) * rstd[j];
-        dy[k][j] = a.act ? di[j] * silu_grad(xh[k][j] * ga[j] + be[j]) : di[j];
+        dy[k][j] = a.act ? di[j] * silu_grad(gn_bwd_arg<FILM>(xh[k][j], ga[j], be[j], op[j], sh[j])) : di[j];
         if (live) { s1[j] += dy[k][j]; s2[j] += dy[k][j] * xh[k][j]; }
       }
     }
@@ -303,7 +360,8 @@ __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
     for (int j = 0; j < 4; ++j) {
       const int cc = c0 + t * 4 + j;
       fa.bc[((long)b * C + cc) * 2] = u[j]; fa.bc[((long)b * C + cc) * 2 + 1] = w[j];
-      const float gmm = a.gamma[cc];
+      float gmm = a.gamma[cc];
+      if constexpr (FILM) gmm *= 1.0f + a.film[(long)b * a.film_bs + a.film_off + cc];
       gsum[(t * 4 + j) * 2] = u[j] * gmm; gsum[(t * 4 + j) * 2 + 1] = w[j] * gmm;
     }
   }
@@ -327,7 +385,10 @@ __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
     if (pix >= a.HW) break;
     float r[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = rstd[j] * (ga[j] * dy[k][j] - m1[j] - xh[k][j] * m2[j]);
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (FILM) r[j] = rstd[j] * ((ga[j] * op[j]) * dy[k][j] - m1[j] - xh[k][j] * m2[j]);
+      else r[j] = rstd[j] * (ga[j] * dy[k][j] - m1[j] - xh[k][j] * m2[j]);
+    }
     r[0] += av[k].x; r[1] += av[k].y; r[2] += av[k].z; r[3] += av[k].w;
     const long o = ((long)b * a.HW + pix) * C + c;
     float* dst = pdx + (long)pix * ldx;
@@ -351,11 +412,11 @@ __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
   }
 }
 
-template <typename T>
+template <typename T, bool FILM = false>
 static void launch_gn_bwd_fused(const GnBwdFusedArgs& fa, int ppt, dim3 grid, hipStream_t st) {
-  if (ppt <= 2) gn_bwd_fused_kernel<T, 2><<<grid, 512, 0, st>>>(fa);
-  else if (ppt <= 4) gn_bwd_fused_kernel<T, 4><<<grid, 512, 0, st>>>(fa);
-  else gn_bwd_fused_kernel<T, 8><<<grid, 512, 0, st>>>(fa);
+  if (ppt <= 2) gn_bwd_fused_kernel<T, 2, FILM><<<grid, 512, 0, st>>>(fa);
+  else if (ppt <= 4) gn_bwd_fused_kernel<T, 4, FILM><<<grid, 512, 0, st>>>(fa);
+  else gn_bwd_fused_kernel<T, 8, FILM><<<grid, 512, 0, st>>>(fa);
 }
 
 // channel run of the one-pass kernel for this shape (0: use the three-kernel chain): whole groups, one side of the concat seam, rows of
@@ -1286,12 +1347,51 @@ extern "C" int stedm_gn_bwd(const float* x1, int c1, const float* x2, int c2, co
     STEDM_LAUNCH_CHECK();
     return 0;
   }
-  gn_bwd_stats_kernel<<<dim3(B, nslab, (Q + 63) / 64), 256, 0, st>>>(a);
+  gn_bwd_stats_kernel<false><<<dim3(B, nslab, (Q + 63) / 64), 256, 0, st>>>(a);
   gn_bwd_fold_kernel<<<B, 256, (size_t)C * 8, st>>>(part, nslab, C, groups, HW, gamma, bc, gm);
   gn_bwd_param_kernel<<<(C + 15) / 16, 256, 0, st>>>(bc, B, C, dgamma, dbeta, acc_param);
   const dim3 grid(B, (unsigned)(((long)HW * Q + 1023) / 1024));
   if (mm_dtype == STEDM_F16) gn_bwd_apply_kernel<_Float16><<<grid, 256, 0, st>>>(a);
   else gn_bwd_apply_kernel<__bf16><<<grid, 256, 0, st>>>(a);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+// stedm_gn_bwd with the per-sample affine of a use_scale_shift_norm block (one source tensor): the same kernel selection
+// (gn_bwd_fused_cb), the FILM instantiations, and gn_bwd_film_param_kernel in place of gn_bwd_param_kernel.
+extern "C" int stedm_gn_bwd_film(const float* x1, int c1, const float* mean_rstd, const float* gamma, const float* beta, int groups, int act,
+                                 const float* film, long film_bstride, int film_off, const float* dA, const float* add, int B, int HW, float* ws,
+                                 float* dx1, int acc1, void* dx16_hi, void* dx16_lo, int mm_dtype, float* dgamma, float* dbeta, int acc_param,
+                                 float* d_film, long d_film_bstride, int d_film_off, void* stream) {
+  const int C = c1;
+  STEDM_CHECK_ARG(x1 && mean_rstd && gamma && beta && film && dA && ws && dx1 && dgamma && dbeta && d_film, "gn_bwd_film: null pointer");
+  STEDM_CHECK_ARG(C > 0 && C % 4 == 0 && groups > 0 && groups <= 64 && C % groups == 0 && C * 8 <= 65536, "gn_bwd_film: channel constraints");
+  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_bwd_film: bad mm_dtype");
+  STEDM_CHECK_ARG(B > 0 && HW > 0 && film_off >= 0 && film_off % 4 == 0 && film_bstride % 4 == 0 && (film_bstride == 0 || film_bstride >= (long)film_off + 2 * C),
+                  "gn_bwd_film: a film row holds 2 C values from film_off, 16-byte aligned (film_bstride=%ld film_off=%d C=%d)", film_bstride, film_off, C);
+  STEDM_CHECK_ARG(((uintptr_t)film & 15) == 0, "gn_bwd_film: film must be 16-byte aligned");
+  STEDM_CHECK_ARG(d_film_off >= 0 && d_film_bstride >= (long)d_film_off + 2 * C, "gn_bwd_film: a d_film row receives 2 C values from d_film_off");
+  const int nslab = (HW + kGnBwdSlab - 1) / kGnBwdSlab, Q = C / 4;
+  float* part = ws;
+  float* bc = part + (long)B * nslab * C * 2;
+  float* gm = bc + (long)B * C * 2;
+  GnBwdArgs a{x1, nullptr, c1, 0, mean_rstd, gamma, beta, dA, groups, HW, act, part, gm, add, dx1, nullptr, acc1, 0, dx16_hi, dx16_lo, film, film_bstride, film_off};
+  hipStream_t st = as_stream(stream);
+  int ppt = 0;
+  const int cb = gn_bwd_fused_cb(c1, 0, groups, HW, &ppt);
+  if (cb > 0) {
+    GnBwdFusedArgs fa{a, bc, cb};
+    if (mm_dtype == STEDM_F16) launch_gn_bwd_fused<_Float16, true>(fa, ppt, dim3(B, C / cb), st);
+    else launch_gn_bwd_fused<__bf16, true>(fa, ppt, dim3(B, C / cb), st);
+  } else {
+    gn_bwd_stats_kernel<true><<<dim3(B, nslab, (Q + 63) / 64), 256, 0, st>>>(a);
+    gn_bwd_fold_kernel<<<B, 256, (size_t)C * 8, st>>>(part, nslab, C, groups, HW, gamma, bc, gm, film + film_off, film_bstride);
+    const dim3 grid(B, (unsigned)(((long)HW * Q + 1023) / 1024));
+    if (mm_dtype == STEDM_F16) gn_bwd_apply_kernel<_Float16, true><<<grid, 256, 0, st>>>(a);
+    else gn_bwd_apply_kernel<__bf16, true><<<grid, 256, 0, st>>>(a);
+  }
+  gn_bwd_film_param_kernel<<<(C + 15) / 16, 256, 0, st>>>(bc, B, C, gamma, beta, film, film_bstride, film_off, d_film, d_film_bstride, d_film_off, dgamma,
+                                                          dbeta, acc_param);
   STEDM_LAUNCH_CHECK();
   return 0;
 }

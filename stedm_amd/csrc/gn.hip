@@ -405,6 +405,9 @@ struct GnApplyCArgs {
   unsigned* ovf; // fp16 range guard flag (common.hpp) or nullptr
   const void* x16;  // octet kernel: the x1 channels arrive as the 16-bit values a convolution's epilogue already wrote into channels
                     // [0, c1) of the raw plane [B][HW][c1 + c2] (= raw_hi): x1 is not read and that part of the raw plane not rewritten
+  const float* film;   // FiLM form (stedm_gn_apply16c_film): sample b's row film + b * film_bs + film_off = {scale[C], shift[C]}; NULL otherwise
+  long film_bs;
+  int film_off;
   __device__ GnPartials partials() const { return GnPartials{cs1, nslab1, c1, cs2, nslab2, c2, groups, HW, eps, mr}; }
 };
 
@@ -504,12 +507,14 @@ __global__ void __launch_bounds__(256) gn_apply16c_kernel(GnApplyCArgs a, int sl
 // cb > 0: the block takes a CHANNEL run of cb channels (whole groups, a multiple of 8) of every pixel of its sample instead of a pixel run
 // of all channels: it folds the statistics and builds the table of its own groups only (the samples of the 8 x 8 level are 64 pixels of
 // 1024 - 2048 channels: six pixel-run blocks per sample each built the whole table for 11 pixels of streaming).
-template <typename T>
+// FILM: the per-sample modulation z = u (1 + scale) + shift between the affine and the activation (gn_fold.hpp: gn_film); the table gets
+// the two rows 1 + scale and shift of the block's sample. The plain instantiations compile to what they were.
+template <typename T, bool FILM = false>
 __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int slab, int cb) {
   typedef T V4 __attribute__((ext_vector_type(4)));
   __shared__ double dsu[256], dsq[256];
   __shared__ float lmean[64], lrstd[64];
-  extern __shared__ __attribute__((aligned(16))) float tab[];   // [3][C]: mean, rstd * gamma, beta per channel
+  extern __shared__ __attribute__((aligned(16))) float tab[];   // [3][C]: mean, rstd * gamma, beta per channel (FILM: [5][C], + 1 + scale, shift)
   const int b = blockIdx.x, sl = blockIdx.y;
   const int C = a.c1 + a.c2, Qall = C >> 2;
   const int cpg = C / a.groups;
@@ -555,7 +560,9 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
   // channel-run blocks own their groups. Block-uniform guard switches:
   const bool guard = a.ovf != nullptr && __is_same(T, _Float16);
   const bool maybe_over = gn_fold_block(a.partials(), b, b2, c_lo / cpg, c_n / cpg, cb > 0 || sl == 0, dsu, dsq, lmean, lrstd) && guard;   // raw planes
-  const bool norm_over = gn_build_table(tab, lmean, lrstd, a.gamma, a.beta, C, cpg, a.HW, c_lo, c_n, guard);                              // normalised planes
+  bool norm_over;                                                                                                                          // normalised planes
+  if constexpr (FILM) norm_over = gn_build_table_film(tab, lmean, lrstd, a.gamma, a.beta, a.film + (long)b * a.film_bs + a.film_off, C, cpg, a.HW, c_lo, c_n, guard);
+  else norm_over = gn_build_table(tab, lmean, lrstd, a.gamma, a.beta, C, cpg, a.HW, c_lo, c_n, guard);
   unsigned bad_raw = 0u, bad_norm = 0u;
   const bool odd = threadIdx.x & 1;
   // lane pair exchange: the even lane keeps cursor 0's quad and receives its partner's; the odd lane keeps cursor 1's. Returns the
@@ -592,7 +599,14 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
       const float4 mn = *reinterpret_cast<const float4*>(tab + cc);
       const float4 sc = *reinterpret_cast<const float4*>(tab + C + cc);
       const float4 bt = *reinterpret_cast<const float4*>(tab + 2 * C + cc);
-      w.x = (w.x - mn.x) * sc.x + bt.x; w.y = (w.y - mn.y) * sc.y + bt.y; w.z = (w.z - mn.z) * sc.z + bt.z; w.w = (w.w - mn.w) * sc.w + bt.w;
+      if constexpr (FILM) {
+        const float4 op = *reinterpret_cast<const float4*>(tab + 3 * C + cc);
+        const float4 sh = *reinterpret_cast<const float4*>(tab + 4 * C + cc);
+        w.x = gn_film(w.x, mn.x, sc.x, bt.x, op.x, sh.x); w.y = gn_film(w.y, mn.y, sc.y, bt.y, op.y, sh.y);
+        w.z = gn_film(w.z, mn.z, sc.z, bt.z, op.z, sh.z); w.w = gn_film(w.w, mn.w, sc.w, bt.w, op.w, sh.w);
+      } else {
+        w.x = (w.x - mn.x) * sc.x + bt.x; w.y = (w.y - mn.y) * sc.y + bt.y; w.z = (w.z - mn.z) * sc.z + bt.z; w.w = (w.w - mn.w) * sc.w + bt.w;
+      }
       if (a.act == 1) { w.x = silu_f(w.x); w.y = silu_f(w.y); w.z = silu_f(w.z); w.w = silu_f(w.w); }
       oq[k] = __builtin_bit_cast(uint2, split16<T>(w, ol != nullptr, lo));
       if (norm_over) bad_norm |= f16_over4<T>(oq[k]);
@@ -755,7 +769,7 @@ static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream)
   if (slab > HW) slab = HW;
   dim3 grid(B, (HW + slab - 1) / slab);
   if (C % 8 == 0 && c1 % 8 == 0 && (size_t)3 * C * sizeof(float) <= 48 * 1024) {
-    const size_t lds = (size_t)3 * C * sizeof(float);
+    const size_t lds = (size_t)(a.film ? 5 : 3) * C * sizeof(float);      // (the FiLM entry admits only widths whose 5 rows stay within 48 KiB)
     // Small samples cut by pixels would need several blocks per sample, each building the whole table: cut those by CHANNELS instead
     // (runs of whole groups, >= 512 B per pixel, on one side of the concat seam), so a block builds the table of its own groups only.
     int cb = 0;
@@ -768,7 +782,10 @@ static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream)
       if (cb > 0 && (C % cb != 0 || c1 % cb != 0 || cb % unit != 0 || cb / cpg > 64)) cb = 0;
     }
     if (cb > 0) grid = dim3(B, C / cb);
-    if (a.x16) {      // the octet kernel (single-product planes only: the entry has no lo planes; cb is a multiple of 8)
+    if (a.film) {     // the FiLM form of the quad-pair kernel (stedm_gn_apply16c_film: one fp32 source)
+      if (mm_dtype == STEDM_F16) gn_apply16c_v8_kernel<_Float16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
+      else gn_apply16c_v8_kernel<__bf16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
+    } else if (a.x16) {      // the octet kernel (single-product planes only: the entry has no lo planes; cb is a multiple of 8)
       const bool pair = C % 16 == 0 && c1 % 16 == 0 && (cb == 0 || cb % 16 == 0);
       if (mm_dtype == STEDM_F16) {
         if (pair) gn_apply16c_o8_kernel<_Float16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
@@ -783,6 +800,7 @@ static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream)
     return 0;
   }
   STEDM_CHECK_ARG(!a.x16, "gn_apply16c_x16: the 16-bit source form belongs to the vector kernel");
+  STEDM_CHECK_ARG(!a.film, "gn_apply16c_film: the FiLM form belongs to the 8-wide table kernel");
   if (mm_dtype == STEDM_F16)
     gn_apply16c_kernel<_Float16><<<grid, 256, 0, as_stream(stream)>>>(a, slab);
   else
@@ -831,4 +849,28 @@ extern "C" int stedm_gn_apply16c(const float* x1, int c1, const float* cs1, int 
                                  void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, int mm_dtype, void* stream) {
   return stedm_gn_apply16c_mr(x1, c1, cs1, nslab1, x2, c2, cs2, nslab2, x2_bmod, gamma, beta, eps, groups, act, B, HW, out_hi, out_lo, raw_hi, raw_lo,
                               nullptr, mm_dtype, stream);
+}
+
+// act(GroupNorm(x1) * (1 + scale) + shift) -> 16-bit planes: out_layers[0] of a use_scale_shift_norm ResBlock (openaimodel.py:280-284).
+// Sample b reads scale[c] = film[b * film_bstride + film_off + c] and shift[c] = film[b * film_bstride + film_off + C + c] (film_bstride 0:
+// one row for every sample). One source tensor (x2 == NULL), C % 8 == 0, the 8-wide table kernel only, in the geometry of
+// gn_apply16c_launch; any other shape is an argument error. The rounding order is gn_film's (gn_fold.hpp).
+extern "C" int stedm_gn_apply16c_film(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
+                                      const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                                      void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, const float* film, long film_bstride,
+                                      int film_off, int mm_dtype, void* stream) {
+  STEDM_CHECK_ARG(x1 && cs1 && out_hi && gamma && beta && film, "gn_apply16c_film: null pointer");
+  STEDM_CHECK_ARG(x2 == nullptr && c2 == 0 && cs2 == nullptr, "gn_apply16c_film: one source tensor only (x2 must be NULL)");
+  (void)nslab2; (void)x2_bmod;
+  const int C = c1;
+  STEDM_CHECK_ARG(C > 0 && C % 8 == 0 && (size_t)5 * C * sizeof(float) <= 48 * 1024, "gn_apply16c_film: need C %% 8 == 0 and C <= 2456 (C=%d)", C);
+  STEDM_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0, "gn_apply16c_film: need groups <= 64 and C %% groups == 0");
+  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_apply16c_film: bad mm_dtype");
+  STEDM_CHECK_ARG(raw_hi || !raw_lo, "gn_apply16c_film: raw_lo without raw_hi");
+  STEDM_CHECK_ARG(nslab1 > 0 && B > 0 && HW > 0, "gn_apply16c_film: nslab1 must be the slot count of cs1");
+  STEDM_CHECK_ARG(film_off >= 0 && (film_bstride == 0 || film_bstride >= (long)film_off + 2 * C),
+                  "gn_apply16c_film: a row holds 2 C values from film_off (film_bstride=%ld film_off=%d C=%d)", film_bstride, film_off, C);
+  GnApplyCArgs a{x1, nullptr, cs1, nullptr, c1, 0, 0, groups, HW, act, nslab1, 0, gamma, beta, eps, out_hi, out_lo, raw_hi, raw_lo, mean_rstd,
+                 mm_dtype == STEDM_F16 ? f16_guard_flag() : nullptr, nullptr, film, film_bstride, film_off};
+  return gn_apply16c_launch(a, B, mm_dtype, stream);
 }

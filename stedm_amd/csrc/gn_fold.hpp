@@ -1,6 +1,6 @@
 // GroupNorm statistics from channel partials, stated once: the {sum, sumsq} -> {mean, rstd} formula, the block fold of the partials
 // of a virtual concat [x1 | x2] with its summation order, the per-channel table of the 8-wide apply kernels with the fp16 guard's
-// switch for the normalised planes, and the 16-bit hi / lo split. gn.hip (the apply kernels), bwd.hip (gn_fold_kernel) and the
+// switch for the normalised planes, the FiLM modulation of scale-shift-norm blocks (gn_film) and the 16-bit hi / lo split. gn.hip (the apply kernels), bwd.hip (gn_fold_kernel) and the
 // convolution epilogues that normalise their own output (conv_io.hip, conv_rs.inc) must agree bit for bit; they do so by calling this.
 #pragma once
 #include "common.hpp"
@@ -102,6 +102,38 @@ __device__ __forceinline__ bool gn_build_table(float* tab, const float* lmean, c
     tab[C + c] = lrstd[gc] * gmc;
     tab[2 * C + c] = btc;
     if (guard) nb |= gn_norm_admits_over(rn, gmc, btc);
+  }
+  return __syncthreads_or(nb) != 0;
+}
+
+// FiLM (scale-shift norm, openaimodel.py:280-284): the GroupNorm output is modulated per (sample, channel) by the embedding row
+// film[b][film_off + c] = scale, film[b][film_off + C + c] = shift (th.chunk(emb_out, 2, dim=1): scale half first). THE ORDER, in fp32:
+//   u = (x - mean) * (rstd * gamma) + beta        (the table rows and the order of the plain 8-wide kernels)
+//   z = u * (1 + scale) + shift                   (1 + scale rounded to fp32 once, when the table is built)
+// No folded affine: u keeps the bits the plain kernel would give, and the backward recomputes z from the same two steps.
+__device__ __forceinline__ float gn_film(float x, float mean, float rg, float beta, float one_scale, float shift) {
+  const float u = (x - mean) * rg + beta;
+  return u * one_scale + shift;
+}
+
+// gn_build_table for a FiLM block of sample b: tab[5][C], rows 0 .. 2 as above, tab[3 C + c] = 1 + scale, tab[4 C + c] = shift. The guard's
+// switch is evaluated on the sample's effective affine gamma (1 + scale), beta (1 + scale) + shift: a plane value can leave the fp16
+// range through scale / shift alone. film_row: the sample's row, already offset (film + b * film_bstride + film_off).
+__device__ __forceinline__ bool gn_build_table_film(float* tab, const float* lmean, const float* lrstd, const float* gamma, const float* beta,
+                                                    const float* film_row, int C, int cpg, int HW, int c_lo, int c_n, bool guard) {
+  __syncthreads();
+  int nb = 0;
+  const float rn = sqrtf((float)cpg * (float)HW);
+  for (int c = c_lo + threadIdx.x; c < c_lo + c_n; c += 256) {
+    const int gc = c / cpg;
+    const float gmc = gamma[c], btc = beta[c];
+    const float op = 1.0f + film_row[c], sh = film_row[C + c];
+    tab[c] = lmean[gc];
+    tab[C + c] = lrstd[gc] * gmc;
+    tab[2 * C + c] = btc;
+    tab[3 * C + c] = op;
+    tab[4 * C + c] = sh;
+    if (guard) nb |= gn_norm_admits_over(rn, gmc * op, btc * op + sh);
   }
   return __syncthreads_or(nb) != 0;
 }

@@ -347,6 +347,23 @@ def gn_apply16c(x1: torch.Tensor, cs1: torch.Tensor, x2: Optional[torch.Tensor],
                                      _ptr(mean_rstd), prec.mm_dtype, _stream()), "stedm_gn_apply16c_mr")
 
 
+def gn_apply16c_film(x1: torch.Tensor, cs1: torch.Tensor, out_hi: torch.Tensor, out_lo: Optional[torch.Tensor], prec: Precision, gamma: torch.Tensor,
+                     beta: torch.Tensor, film: torch.Tensor, film_off: int, film_bstride: int, eps: float = 1e-5, groups: int = 32, act: int = 0,
+                     raw: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None, mean_rstd: Optional[torch.Tensor] = None) -> None:
+    """act(GroupNorm(x1) * (1 + scale) + shift) -> 16-bit planes (stedm_gn_apply16c_film): sample b reads scale / shift at
+    film.view(-1)[b * film_bstride + film_off + (0 | C) + c]; film_bstride 0 shares one row."""
+    _chk(x1, name="x1"); _chk(film, name="film")
+    B, C = x1.shape[0], x1.shape[-1]
+    HW = x1.numel() // (B * C)
+    assert film_off >= 0 and film.numel() >= (B - 1) * film_bstride + film_off + 2 * C, "film rows out of range"
+    if mean_rstd is not None:
+        assert mean_rstd.dtype == torch.float32 and mean_rstd.is_contiguous() and tuple(mean_rstd.shape) == (B, groups, 2)
+    check(lib().stedm_gn_apply16c_film(x1.data_ptr(), C, cs1.data_ptr(), cs1.shape[1], None, 0, None, 0, 0, gamma.data_ptr(), beta.data_ptr(),
+                                       float(eps), groups, act, B, HW, out_hi.data_ptr(), _ptr(out_lo),
+                                       None if raw is None else raw[0].data_ptr(), None if raw is None else _ptr(raw[1]), _ptr(mean_rstd),
+                                       film.data_ptr(), int(film_bstride), int(film_off), prec.mm_dtype, _stream()), "stedm_gn_apply16c_film")
+
+
 def gn_apply16c_x16(c1: int, cs1: torch.Tensor, x2: Optional[torch.Tensor], cs2: Optional[torch.Tensor], out_hi: torch.Tensor, raw_hi: torch.Tensor,
                     prec: Precision, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, groups: int = 32, act: int = 0, x2_bmod: int = 0) -> None:
     """act(GroupNorm([x1|x2])) where x1 (c1 channels) already sits as 16-bit values in channels [0, c1) of raw_hi [B,H,W,c1+c2] (written there by
@@ -1475,6 +1492,24 @@ def gn_bwd(x1, x2, mean_rstd, gamma, beta, groups: int, act: int, dA, add, ws, d
                              _ptr(add), B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1), _ptr(dx2), int(acc2),
                              None if dx16 is None else dx16[0].data_ptr(), None if dx16 is None else _ptr(dx16[1]), prec.mm_dtype,
                              dgamma.data_ptr(), dbeta.data_ptr(), int(acc_param), _stream()), "stedm_gn_bwd")
+
+
+def gn_bwd_film(x1, mean_rstd, gamma, beta, groups: int, act: int, film, film_off: int, film_bstride: int, dA, add, ws, dx1, acc1: bool, dx16,
+                prec: Precision, dgamma, dbeta, acc_param: bool, d_film, d_film_off: int) -> None:
+    """Backward of act(GroupNorm(x1) * (1 + scale) + shift): see stedm_gn_bwd_film. d_film [B, N]: row b receives dscale | dshift at
+    columns [d_film_off, d_film_off + 2 C); its row stride may exceed N (a column block of a wider matrix)."""
+    _chk(x1, name="x1"); _chk(dA, name="dA"); _chk(film, name="film")
+    B, C = x1.shape[0], x1.shape[-1]
+    HW = x1.numel() // (B * C)
+    assert dA.numel() == B * HW * C and ws.numel() >= gn_bwd_ws_floats(B, HW, C, groups)
+    assert film_off >= 0 and film.numel() >= (B - 1) * film_bstride + film_off + 2 * C, "film rows out of range"
+    assert d_film.dtype == torch.float32 and d_film.dim() == 2 and d_film.shape[0] == B and d_film.stride(1) == 1
+    assert 0 <= d_film_off and d_film_off + 2 * C <= d_film.shape[1], "d_film columns out of range"
+    check(lib().stedm_gn_bwd_film(x1.data_ptr(), C, mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, act, film.data_ptr(),
+                                  int(film_bstride), int(film_off), dA.data_ptr(), _ptr(add), B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1),
+                                  None if dx16 is None else dx16[0].data_ptr(), None if dx16 is None else _ptr(dx16[1]), prec.mm_dtype,
+                                  dgamma.data_ptr(), dbeta.data_ptr(), int(acc_param), d_film.data_ptr(), d_film.stride(0), int(d_film_off),
+                                  _stream()), "stedm_gn_bwd_film")
 
 
 def im2col_t16(src16: torch.Tensor, dst16: torch.Tensor, ks: int, mode: int) -> None:

@@ -137,6 +137,17 @@ class UNetTrainer:
                         norm.eps, norm.num_groups, act)
         return hi, lo
 
+    def _film16(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int):
+        """_norm16 for out_layers[0] of a scale-shift-norm block: SiLU(GroupNorm(h) * (1 + scale) + shift) in the backward's operand format"""
+        m = self.m
+        kept = m._saved16.get((id(norm), h.data_ptr()))
+        if kept is not None and self.bprec.npass == 1:
+            return kept
+        hi, lo = self._planes("a16", tuple(h.shape))
+        ops.gn_apply16c_film(h, m._chan_stats(h), hi, lo, self.bprec, norm.weight, norm.bias, film, film_off, film_bstride, norm.eps,
+                             norm.num_groups, 1)
+        return hi, lo
+
     def _grad_of(self, t: torch.Tensor) -> Tuple[torch.Tensor, bool]:
         """(gradient buffer of activation `t`, whether it already holds a contribution)"""
         key = t.data_ptr()
@@ -366,6 +377,22 @@ class UNetTrainer:
         ops.gn_bwd(x1, x2, mr, norm.weight, norm.bias, G, act, dA, add, ws, g1, a1, g2, a2, dx16, self.bprec, self._param_grad(norm.weight),
                    self._param_grad(norm.bias), False)
 
+    def _gn_bwd_film(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int, dA, dx16, d_film, d_film_off: int):
+        """backward of SiLU(GroupNorm(h) * (1 + scale) + shift): dh, the GroupNorm's parameter gradients, and dscale | dshift into columns
+        [d_film_off, d_film_off + 2 C) of d_film (stedm_gn_bwd_film)"""
+        m = self.m
+        B, C = h.shape[0], h.shape[-1]
+        HW = h.numel() // (B * C)
+        G = norm.num_groups
+        mr = getattr(m, "_saved_mr", {}).get((id(norm), h.data_ptr()))
+        if mr is None:
+            mr = self._buf(f"mr.{B}x{G}", (B, G, 2))
+            ops.gn_fold(m._chan_stats(h), None, G, HW, norm.eps, mr)
+        ws = self._buf("gnws", (ops.gn_bwd_ws_floats(B, HW, C, G),))
+        g1, a1 = self._grad_of(h)
+        ops.gn_bwd_film(h, mr, norm.weight, norm.bias, G, 1, film, film_off, film_bstride, dA, None, ws, g1, a1, dx16, self.bprec,
+                        self._param_grad(norm.weight), self._param_grad(norm.bias), False, d_film, d_film_off)
+
     # ------------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, x: torch.Tensor, c_concat: Optional[torch.Tensor], t: torch.Tensor, context: torch.Tensor) -> torch.Tensor:
@@ -379,6 +406,7 @@ class UNetTrainer:
             raise
         self.tape = m._tape
         self.tape_emb = m._tape_emb
+        self.tape_film = m._tape_film
         m._tape = None
         if self.ema_decay is not None and getattr(self, "_ema", None) is None:
             self._build_ema()        # LitEma clones the parameters when it is built (ema.py:17-21): before anything updates them
@@ -508,11 +536,36 @@ class UNetTrainer:
         else:
             add = dout
         # conv2 and its GroupNorm + SiLU
-        h16 = self._norm16(rb.out_layers[0], 1, h)
+        film = rb.use_scale_shift_norm
+        if film:
+            # scale | shift of this block: its columns of the concatenated embedding projection, or the style projection (row stride = width)
+            fsrc = self.tape_film[1] if emb_off is None else self.tape_film[0]
+            foff, fbs = (0 if emb_off is None else emb_off), fsrc.shape[1]
+            h16 = self._film16(rb.out_layers[0], h, fsrc, foff, fbs)
+        else:
+            h16 = self._norm16(rb.out_layers[0], 1, h)
         self._wgrad(h16, dout16, dout, conv2.weight, 3, 0)
         dA2 = self._buf(f"dA.{B}x{H}x{W}x{co}", (B, H, W, co))
         self._dgrad(conv2, dout16, dA2)
         dh16 = self._planes("dh16", (B, H, W, co))
+        if film:
+            # the embedding modulates out_layers' GroupNorm (openaimodel.py:280-284): its gradient dscale | dshift comes out of that
+            # GroupNorm's backward; nothing adds onto h but conv1's bias, whose gradient is the batch sum of dh alone
+            if emb_off is None:
+                self.dEs = self._buf("dEs", (B, 2 * co))
+                dmat, doff = self.dEs, 0
+            else:
+                dmat, doff = self.dE, emb_off
+            self._gn_bwd_film(rb.out_layers[0], h, fsrc, foff, fbs, dA2, dh16, dmat, doff)
+            dh = self.G[h.data_ptr()]
+            self._bias_grad(dh, conv1.bias)
+            blk = dmat
+            if emb_off is not None:
+                blk = self._buf(f"dEblk.{B}x{2 * co}", (B, 2 * co))
+                blk.copy_(dmat[:, doff:doff + 2 * co])
+            self._colsum(blk, self._param_grad(rb.emb_layers[1].bias))       # emb_layers[1].bias: the column sums of its dE block
+            self._res_bwd_front(rb, x1, x2, dh, dh16, add, cin)
+            return
         self._gn_bwd(rb.out_layers[0], 1, h, None, dA2, None, dx16=dh16)
         dh = self.G[h.data_ptr()]
         # the embedding enters between conv1 and the second GroupNorm (openaimodel.py:276-287): its gradient is the per-sample
@@ -523,6 +576,11 @@ class UNetTrainer:
             self._bias_grad(dh, conv1.bias, self.dEs, co, also=eb)
         else:
             self._bias_grad(dh, conv1.bias, self.dE[:, emb_off:], self.dE.shape[1], also=eb)
+        self._res_bwd_front(rb, x1, x2, dh, dh16, add, cin)
+
+    def _res_bwd_front(self, rb: ResBlock, x1, x2, dh, dh16, add, cin):
+        B, H, W, _ = dh.shape
+        conv1 = rb.in_layers[2]
         # conv1 and the first GroupNorm + SiLU over the (virtual concat) input
         a16 = self._norm16(rb.in_layers[0], 1, x1, x2)
         self._wgrad(a16, dh16, dh, conv1.weight, 3, 0)

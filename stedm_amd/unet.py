@@ -72,20 +72,22 @@ class Downsample(nn.Module):
 
 
 class ResBlock(TimestepBlock):
-    """openaimodel.py:176-288 with the options the shipped configs use (no scale-shift norm, no up/down)."""
+    """openaimodel.py:176-288 without up / down. use_scale_shift_norm (:199, :280-284): emb_layers emits 2 * out_channels values and the block
+    computes h = out_norm(h) * (1 + scale) + shift in place of h + emb_out (AdaGN / FiLM)."""
 
     def __init__(self, channels, emb_channels, dropout, out_channels=None, use_conv=False, use_scale_shift_norm=False,
                  dims=2, use_checkpoint=False, up=False, down=False):
         super().__init__()
-        if use_scale_shift_norm or up or down or dims != 2 or use_conv:
-            raise NotImplementedError("ResBlock: use_scale_shift_norm / up / down / use_conv / dims != 2 are not "
+        if up or down or dims != 2 or use_conv:
+            raise NotImplementedError("ResBlock: up / down / use_conv / dims != 2 are not "
                                       "exercised by the reference configs and are not implemented in the HIP path")
         self.channels = channels
         self.emb_channels = emb_channels
         self.dropout = dropout
         self.out_channels = out_channels or channels
+        self.use_scale_shift_norm = bool(use_scale_shift_norm)
         self.in_layers = nn.Sequential(GroupNorm32(32, channels), nn.SiLU(), nn.Conv2d(channels, self.out_channels, 3, padding=1))
-        self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_channels, self.out_channels))
+        self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_channels, 2 * self.out_channels if use_scale_shift_norm else self.out_channels))
         self.out_layers = nn.Sequential(GroupNorm32(32, self.out_channels), nn.SiLU(), nn.Dropout(p=dropout),
                                         zero_module(nn.Conv2d(self.out_channels, self.out_channels, 3, padding=1)))
         if self.out_channels == channels:
@@ -168,6 +170,8 @@ class UNetModel(nn.Module):
         self.num_head_channels = num_head_channels
         self.num_heads_upsample = num_heads_upsample
         self.predict_codebook_ids = False
+        self.use_scale_shift_norm = bool(use_scale_shift_norm)
+        ssn = self.use_scale_shift_norm
         self.precision = Precision.parse(precision) if isinstance(precision, str) else precision
 
         ted = model_channels * 4
@@ -181,7 +185,8 @@ class UNetModel(nn.Module):
                     # the reference executes `layers.append()` here (openaimodel.py:580-590) -> TypeError
                     raise TypeError("list.append() takes exactly one argument (0 given) "
                                     "[reference openaimodel.py:580: ds in attention_resolutions is not constructible]")
-                self.input_blocks.append(TimestepEmbedSequential(ResBlock(ch, ted, dropout, out_channels=mult * model_channels)))
+                self.input_blocks.append(TimestepEmbedSequential(ResBlock(ch, ted, dropout, out_channels=mult * model_channels,
+                                                                                  use_scale_shift_norm=ssn)))
                 ch = mult * model_channels
                 input_block_chans.append(ch)
             if level != len(channel_mult) - 1:
@@ -198,16 +203,16 @@ class UNetModel(nn.Module):
         else:
             mid_attn = AttentionBlock(ch, num_heads=num_heads, num_head_channels=dim_head)
         self.middle_block = TimestepEmbedSequential(
-            ResBlock(ch, ted, dropout),
-            ResBlockStyle(ch, ted, dropout),
+            ResBlock(ch, ted, dropout, use_scale_shift_norm=ssn),
+            ResBlockStyle(ch, ted, dropout, use_scale_shift_norm=ssn),
             mid_attn,
-            ResBlock(ch, ted, dropout),
+            ResBlock(ch, ted, dropout, use_scale_shift_norm=ssn),
         )
         self.output_blocks = nn.ModuleList([])
         for level, mult in list(enumerate(channel_mult))[::-1]:
             for i in range(num_res_blocks + 1):
                 ich = input_block_chans.pop()
-                layers: List[nn.Module] = [ResBlock(ch + ich, ted, dropout, out_channels=model_channels * mult)]
+                layers: List[nn.Module] = [ResBlock(ch + ich, ted, dropout, out_channels=model_channels * mult, use_scale_shift_norm=ssn)]
                 ch = model_channels * mult
                 if ds in attention_resolutions:
                     raise TypeError("reference output block with ds in attention_resolutions is not runnable (openaimodel.py:689-698)")
@@ -292,6 +297,15 @@ class UNetModel(nn.Module):
                 if isinstance(layer, ResBlock):
                     out.append(layer)
         return out
+
+    def _emb_columns(self) -> Tuple[List[Tuple[ResBlock, int]], int]:
+        """([(block, first column)], columns) of the concatenated emb_layers projection: every timestep block takes the width of its own
+        emb_layers[1] - out_channels, or 2 * out_channels = [scale | shift] for a scale-shift-norm block."""
+        layout, off = [], 0
+        for rb in self._timestep_blocks():
+            layout.append((rb, off))
+            off += rb.emb_layers[1].out_features
+        return layout, off
 
     def _prepare(self) -> None:
         """(Re)pack weights when any parameter changed (cheap version fingerprint)."""
@@ -410,11 +424,7 @@ class UNetModel(nn.Module):
         c["te_b2"] = self.time_embed[2].bias.detach().float().contiguous()
         # all timestep emb_layers concatenated along N (SiLU -> Linear, openaimodel.py:231-237)
         tblocks = self._timestep_blocks()
-        self._emb_layout = []
-        off = 0
-        for rb in tblocks:
-            self._emb_layout.append((rb, off))
-            off += rb.out_channels
+        self._emb_layout, off = self._emb_columns()
         wcat = torch.cat([rb.emb_layers[1].weight.detach().float() for rb in tblocks], dim=0)  # [Ntot, ted]
         c["emb_w"] = wcat.contiguous()                          # [Ntot][ted]: K-major operand of the embedding path's backward
         c["emb_wt"] = ops.transpose(c["emb_w"])
@@ -507,6 +517,26 @@ class UNetModel(nn.Module):
                         norm.weight, norm.bias, norm.eps, norm.num_groups, act, x2_bmod, raw, mean_rstd=mr)
         return ((hi, lo), raw) if want_raw else (hi, lo)
 
+    def _film16(self, norm: nn.GroupNorm, h, film, film_off, film_bstride):
+        """SiLU(GroupNorm(h) * (1 + scale) + shift) as 16-bit planes, scale | shift = columns [film_off, film_off + 2 C) of sample b's row of
+        `film` (row stride film_bstride; 0: one shared row). Training keeps the planes and {mean, rstd} exactly as _norm16 / _res do."""
+        B, H, W, C = h.shape
+        keep = self._tape is not None and self.precision.npass == 1 and self.precision.mm_dtype == BF16
+        if keep:
+            self._plane_ctr += 1
+            hi, lo = self._planes(B, H, W, C, f"keep{self._plane_ctr}.a16")
+            self._saved16[(id(norm), h.data_ptr())] = (hi, lo)
+        else:
+            hi, lo = self._planes(B, H, W, C, "g16")
+        mr = None
+        if self._tape is not None:
+            self._mr_ctr += 1
+            mr = self._buf(f"keep{self._mr_ctr}.mr", (B, norm.num_groups, 2))
+            self._saved_mr[(id(norm), h.data_ptr())] = mr
+        ops.gn_apply16c_film(h, self._chan_stats(h), hi, lo, self.precision, norm.weight, norm.bias, film, film_off, film_bstride, norm.eps,
+                             norm.num_groups, 1, mean_rstd=mr)
+        return hi, lo
+
     def _coop_for(self, site: str, B, H, W, co, prec):
         """(words, state) for stedm_conv_args.gn_coop at call site `site`, or None: a sample of 2 .. 4 tiles at 128 channels on a grid that fills
         the chip (smaller ones split K or take other kernels and end with the pass anyway), single product. The first use in a forward advances
@@ -551,7 +581,11 @@ class UNetModel(nn.Module):
         # that sums the partial tiles owns whole groups of a sample and writes the normalised planes itself; otherwise the call ends with the
         # same stedm_gn_apply16c pass as before
         gn2 = rb.out_layers[0]
-        if (prec.npass == 1 and (self._tape is None or prec.mm_dtype == BF16)) or (prec.npass == 3 and self._tape is None):
+        # A scale-shift-norm block (FiLM): the embedding row does not add onto h (no epilogue term) but modulates out_layers' GroupNorm per
+        # sample, so none of the producer-side forms of that GroupNorm applies (gn_next in the epilogue / reduce pass, gn_coop, the
+        # 16-bit-only h): the convolution writes fp32 h and its statistics, and one stedm_gn_apply16c_film pass writes the planes (_film16)
+        film = rb.use_scale_shift_norm
+        if not film and ((prec.npass == 1 and (self._tape is None or prec.mm_dtype == BF16)) or (prec.npass == 3 and self._tape is None)):
             if self._tape is None:
                 # NOT the planes _norm16 would hand out: for cin == cout those are the planes this convolution is reading, and an epilogue
                 # that writes the GroupNorm output would overwrite rows other tiles still gather
@@ -592,9 +626,11 @@ class UNetModel(nn.Module):
                 ops.gn_apply16c_x16(co, self._cs[h.data_ptr()], None, None, h16_next[0], hraw, prec, gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1)
                 done1 = True
         if not done1:
-            kw1 = dict(prec=prec, bias=pk.bias, emb=emb_all, emb_offset=emb_off, emb_bstride=emb_bstride, w_frag=pk.frag,
+            kw1 = dict(prec=prec, bias=pk.bias, emb=None if film else emb_all, emb_offset=emb_off, emb_bstride=emb_bstride, w_frag=pk.frag,
                        chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16, gn_next=gn_next, coop=coop)
             self._in_conv(tag, rb, pk, a16, x1.shape[-1], x2_bmod if x2 is not None else 0, h, kw1)
+        if film:
+            h16_next = self._film16(gn2, h, emb_all, emb_off, emb_bstride)
         out = self._buf(tag + ".out", (B, H, W, co))
         pk2 = self._packed[id(rb.out_layers[3])]
         o16 = None
@@ -810,7 +846,8 @@ class UNetModel(nn.Module):
         under ("sfront", ...): the share count of the partials-only launch, 0 when the block is not routed."""
         B, H, W, C = x1shape
         if (self.cfg_shared_front is False or self._tape is not None or self.precision.npass != 1 or not isinstance(rb.skip_connection, nn.Identity) or
-                rb.out_channels != C):
+                rb.out_channels != C or rb.use_scale_shift_norm):
+            # (a scale-shift-norm style block: the finish pass adds the style row onto h, which that block does not do)
             return False
         key = ("sfront", id(rb), 2 * B, H, W, self.cfg_shared_front)
         hit = self._consts.get(key)
@@ -1119,6 +1156,7 @@ class UNetModel(nn.Module):
         if self._tape is not None:
             self._tape.append(("conv_in", x, c_concat, h))
             self._tape_emb = (timesteps, emb, contexts[0])
+            self._tape_film = (emb_e, style_all)          # scale | shift rows of the scale-shift-norm blocks (the backward reads them again)
         hs = [h]
         mid = list(self.middle_block)
         nblk = len(self.input_blocks)
