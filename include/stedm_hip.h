@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 27
+#define STEDM_ABI_VERSION 28
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -559,6 +559,42 @@ int stedm_dropout_rows(const float* src, const float* res, float* out, void* out
 int stedm_lsa_flash_drop(const void* q_hi, const void* q_lo, const void* k_hi, const void* k_lo, const void* vt_hi,
                          const void* vt_lo, void* out_hi, void* out_lo, int B, int T, int Tp, int heads, int npass,
                          int mm_dtype, float p, unsigned long long seed, unsigned site, void* stream);
+/* Train-mode dropout of the U-Net's ResBlocks (ABI 28) — UNetModel(dropout=p) puts nn.Dropout(p) between out_layers' GroupNorm + SiLU and the
+ * tail convolution of every ResBlock (openaimodel.py:241, :473). THE STREAM is the elementwise one above with the fourth counter word put to
+ * use: element e = ((b HW + pixel) C + c) of the activation's NHWC linear index is kept iff u16 >= thr16 = lrint(p * 65536), u16 = the 16-bit
+ * field (e & 7) - half (j & 1) of output word j >> 1, as above - of
+ *   Philox4x32-10(counter = (lo32(e >> 3), hi32(e >> 3), site, step), key = (lo32 seed, hi32 seed));
+ * kept values are multiplied by inv_keep = (float)(1.0 / (1.0 - p)) (formed in double, narrowed once), dropped ones are +0. One Philox call
+ * serves 8 consecutive channels of one pixel: C % 8 == 0. site = 0x55000000 + k, k the ordinal of the ResBlock in execution order over all
+ * ResBlocks (input blocks, the middle block's three - the inner block of ResBlockStyle included -, output blocks). step: a 32-bit forward
+ * counter; the entries take it as step + (step_ptr ? *step_ptr : 0) (mod 2^32) with step_ptr a DEVICE word read when the kernel runs, so a
+ * captured launch replays with new masks. With step 0 the stream is the elementwise stream of the sViT sites.
+ * Forward: stedm_gn_apply16c_mr / stedm_gn_apply16c_film with, after the activation and before the 16-bit rounding (hi / lo split), each
+ * value w replaced by keep ? w * inv_keep : 0. One source tensor (x2 NULL, c2 0), no raw planes (raw_hi, raw_lo NULL), C % 8 == 0, the
+ * 8-wide table kernel (C <= 4096, 2456 with film); stedm_gn_apply16c_film_drop accepts film == NULL (= stedm_gn_apply16c_drop). p outside
+ * [0, 1) is an argument error; p == 0 is the plain entry (same launch, same bits). The fp16 range guard's switch for the normalised planes
+ * is taken on the affine scaled by inv_keep.
+ * Backward: stedm_gn_bwd / stedm_gn_bwd_film with dA replaced on load by dA_eff = keep ? dA * inv_keep : 0 (one fp32 multiply, the mask
+ * regenerated from the counters - nothing is stored); everything else is the plain entry's arithmetic on dA_eff in the plain entry's
+ * order, so the results equal stedm_gn_bwd(dA_eff) bit for bit. One source tensor (x2, dx2 NULL), C % 8 == 0. */
+int stedm_gn_apply16c_drop(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
+                           const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                           void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, int mm_dtype, float p,
+                           unsigned long long seed, unsigned site, unsigned step, const int32_t* step_ptr, void* stream);
+int stedm_gn_apply16c_film_drop(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2,
+                                int x2_bmod, const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                                void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, const float* film,
+                                long film_bstride, int film_off, int mm_dtype, float p, unsigned long long seed, unsigned site,
+                                unsigned step, const int32_t* step_ptr, void* stream);
+int stedm_gn_bwd_drop(const float* x1, int c1, const float* x2, int c2, const float* mean_rstd, const float* gamma, const float* beta, int groups,
+                      int act, const float* dA, const float* add, int B, int HW, float* ws, float* dx1, int acc1, float* dx2, int acc2,
+                      void* dx16_hi, void* dx16_lo, int mm_dtype, float* dgamma, float* dbeta, int acc_param, float p, unsigned long long seed,
+                      unsigned site, unsigned step, const int32_t* step_ptr, void* stream);
+int stedm_gn_bwd_film_drop(const float* x1, int c1, const float* mean_rstd, const float* gamma, const float* beta, int groups, int act,
+                           const float* film, long film_bstride, int film_off, const float* dA, const float* add, int B, int HW, float* ws,
+                           float* dx1, int acc1, void* dx16_hi, void* dx16_lo, int mm_dtype, float* dgamma, float* dbeta, int acc_param,
+                           float* d_film, long d_film_bstride, int d_film_off, float p, unsigned long long seed, unsigned site, unsigned step,
+                           const int32_t* step_ptr, void* stream);
 /* pool (0 mean, 1 cls, 2 sum) over tokens (+ c_old) -> mlp_head LayerNorm + Linear, vit_set.py:191-206. wt [dim][ncls].
  * ws (optional, ws_floats >= B * 2 * dim): lets the token pooling run as slab partials over ~1024 blocks before the per-sample head
  * (a batch of 8 alone would read its 34 MB of tokens on 8 of the 256 CUs); fixed summation order either way. */

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 STREAM_POSTERIOR = 0x40000          # STEDM_STREAM_POSTERIOR: the stedm_philox_normal stream of the KL posterior's draw (stedm_gauss_sample)
@@ -87,6 +87,10 @@ SIGNATURES = {
     "stedm_ddpm_step_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _F, _P, _I, _P, C.c_long, C.c_long, _P, _P, _P, _P, _P, _P, _P, _P,
                                _I, _I, _I, C.c_long, C.c_ulonglong, C.c_ulonglong, _P]),
     "stedm_gn_apply16c_film": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.c_long, _I, _I, _P]),
+    "stedm_gn_apply16c_drop": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, C.c_ulonglong, C.c_uint,
+                                    C.c_uint, _P, _P]),
+    "stedm_gn_apply16c_film_drop": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.c_long, _I, _I, _F,
+                                         C.c_ulonglong, C.c_uint, C.c_uint, _P, _P]),
     "stedm_gn_apply16c_x16": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _F, _I, _I, _I, _I, _P, _P, _I, _P]),
     "stedm_conv_igemm": (_I, [C.POINTER(ConvArgs), _P]),
     "stedm_conv_fused_skip_ok": (_I, [C.POINTER(ConvArgs)]),
@@ -141,6 +145,10 @@ SIGNATURES = {
     "stedm_gn_fold": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P]),
     "stedm_gn_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P]),
     "stedm_gn_bwd_film": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, C.c_long, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, C.c_long, _I, _P]),
+    "stedm_gn_bwd_drop": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _F, C.c_ulonglong, C.c_uint,
+                               C.c_uint, _P, _P]),
+    "stedm_gn_bwd_film_drop": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, C.c_long, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, C.c_long, _I, _F,
+                                    C.c_ulonglong, C.c_uint, C.c_uint, _P, _P]),
     "stedm_gn_bwd_ws_floats": (C.c_long, [_I, _I, _I, _I]),
     "stedm_im2col_t16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_long, _P]),
     "stedm_wgrad_to_oihw": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

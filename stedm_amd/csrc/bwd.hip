@@ -6,6 +6,7 @@
 // No atomics: every reduction has a fixed order, gradients are bitwise reproducible.
 #include "common.hpp"
 #include "gn_fold.hpp"
+#include "dropmask.hpp"
 #include "sgemm.hpp"
 #include "wfrag.hpp"
 
@@ -54,7 +55,17 @@ struct GnBwdArgs {
   float* dx1; float* dx2; int acc1, acc2;
   void* o_hi; void* o_lo;   // optional 16-bit planes of dx (operand of the producer convolution's dgrad / wgrad)
   const float* film; long film_bs; int film_off;   // FILM kernels (stedm_gn_bwd_film): sample b's row film + b * film_bs + film_off = {scale[C], shift[C]}
+  DropArgs dr;        // DROP kernels (stedm_gn_bwd_drop / _film_drop): the keep mask of the forward's dropout pass, regenerated from the counters
 };
+
+// DROP: the activation went through train-mode dropout before the convolution that produced dA (openaimodel.py:241). The first thing a
+// thread does with a loaded dA quad is dA_eff = keep ? dA * inv_keep : +0 (drop_quad, dropmask.hpp: one fp32 multiply, the forward's mask
+// of element ((b HW + pixel) C + c)); everything after it is the arithmetic of the plain kernels on dA_eff, so the results equal the plain
+// entry's on a pre-masked dA bit for bit. The DROP = false instantiations compile to what they were. Needs C % 8 == 0.
+template <bool DROP>
+__device__ __forceinline__ void gn_bwd_drop4(float (&ds)[4], const GnBwdArgs& a, int b, int pix, int C, int c, uint32_t dstep) {
+  if constexpr (DROP) drop_quad(ds[0], ds[1], ds[2], ds[3], (uint64_t)((long)b * a.HW + pix) * (uint64_t)C + (uint64_t)c, a.dr, dstep);
+}
 
 // FiLM form (use_scale_shift_norm, openaimodel.py:280-284): z = u (1 + s) + sh with u = xh gamma + beta, the two steps of the forward's
 // gn_film; dy = dA silu'(z); dx is the GroupNorm backward with the per-sample weight gamma (1 + s_b) in place of gamma. The FILM = false
@@ -68,7 +79,7 @@ __device__ __forceinline__ float gn_bwd_arg(float xh, float ga, float be, float 
 // grid (B, kGnBwdSlab-pixel slabs, blocks of 64 channel quads). 64-pixel slabs: with 256 the grid of a 16x16 x 512-channel tensor at batch 64
 // was 128 blocks (half the chip idle, 64 dependent pixel steps per thread)
 constexpr int kGnBwdSlab = 64;
-template <bool FILM = false>
+template <bool FILM = false, bool DROP = false>
 __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(GnBwdArgs a) {
   __shared__ float cpart[256 * 8];
   const int b = blockIdx.x, slab = blockIdx.y, nslab = gridDim.y;
@@ -90,10 +101,14 @@ __global__ void __launch_bounds__(256) gn_bwd_stats_kernel(GnBwdArgs a) {
     const float* px = c < a.c1 ? a.x1 + (long)b * a.HW * a.c1 + c : a.x2 + (long)b * a.HW * a.c2 + (c - a.c1);
     const int ldx = c < a.c1 ? a.c1 : a.c2;
     const float* pd = a.dA + (long)b * a.HW * C + c;
+    uint32_t dstep = 0u;
+    if constexpr (DROP) dstep = drop_step_of(a.dr);
     for (int pix = px0 + tp; pix < px1; pix += npl) {
       const float4 xv = *reinterpret_cast<const float4*>(px + (long)pix * ldx);
       const float4 dv = *reinterpret_cast<const float4*>(pd + (long)pix * C);
-      const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds[4] = {dv.x, dv.y, dv.z, dv.w};
+      const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+      float ds[4] = {dv.x, dv.y, dv.z, dv.w};
+      gn_bwd_drop4<DROP>(ds, a, b, pix, C, c, dstep);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float xh = (xs[j] - mean[j]) * rstd[j];
@@ -206,11 +221,13 @@ __global__ void __launch_bounds__(256) gn_bwd_film_param_kernel(const float* __r
 }
 
 // dx = rstd * (gamma*dy - m1 - xhat*m2) (+ add); grid (B, ceil(HW*Q / 1024)), one float4 per thread x 4
-template <typename T, bool FILM = false>
+template <typename T, bool FILM = false, bool DROP = false>
 __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(GnBwdArgs a) {
   typedef T V4 __attribute__((ext_vector_type(4)));
   const int b = blockIdx.x, C = a.c1 + a.c2, Q = C >> 2, cpg = C / a.groups;
   const long total = (long)a.HW * Q;
+  uint32_t dstep = 0u;
+  if constexpr (DROP) dstep = drop_step_of(a.dr);
   for (int k = 0; k < 4; ++k) {
     const long e = ((long)blockIdx.y * 4 + k) * 256 + threadIdx.x;
     if (e >= total) return;
@@ -220,7 +237,9 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(GnBwdArgs a) {
                             : *reinterpret_cast<const float4*>(a.x2 + ((long)b * a.HW + pix) * a.c2 + (c - a.c1));
     const long o = ((long)b * a.HW + pix) * C + c;
     const float4 dv = *reinterpret_cast<const float4*>(a.dA + o);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ds[4] = {dv.x, dv.y, dv.z, dv.w};
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+    float ds[4] = {dv.x, dv.y, dv.z, dv.w};
+    gn_bwd_drop4<DROP>(ds, a, b, pix, C, c, dstep);
     // per-channel constants: 16-B loads of gamma / beta; the group's {mean, rstd} and {m1, m2} once per quad when a quad never straddles
     // two groups (channels per group % 4 == 0: every shape of the U-Net) — 4 loads instead of 24 scalar ones per quad
     const float4 ga4 = *reinterpret_cast<const float4*>(a.gamma + c), be4 = *reinterpret_cast<const float4*>(a.beta + c);
@@ -288,7 +307,7 @@ struct GnBwdFusedArgs {
   int cb;
 };
 
-template <typename T, int PPT, bool FILM = false>
+template <typename T, int PPT, bool FILM = false, bool DROP = false>
 __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
   typedef T V4 __attribute__((ext_vector_type(4)));
   __shared__ float red[512 * 8 + 2 * 288 + 2 * 72];  // [npl][qb][8] lane partials | [cb][2] gamma-weighted sums | [groups of the block][2]
@@ -331,10 +350,14 @@ __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
         if (pix < a.HW) av[k] = *reinterpret_cast<const float4*>(a.add + ((long)b * a.HW + pix) * C + c);
       }
     }
+    uint32_t dstep = 0u;
+    if constexpr (DROP) dstep = drop_step_of(a.dr);
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       const bool live = tp + k * npl < a.HW;
-      const float xi[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w}, di[4] = {dv[k].x, dv[k].y, dv[k].z, dv[k].w};
+      const float xi[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w};
+      float di[4] = {dv[k].x, dv[k].y, dv[k].z, dv[k].w};
+      gn_bwd_drop4<DROP>(di, a, b, tp + k * npl, C, c, dstep);      // (a dead pixel's quad is zeros: the mask leaves them +0)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         xh[k][j] = (xi[j] - mean[j]) * rstd[j];
@@ -412,11 +435,11 @@ __global__ void __launch_bounds__(512) gn_bwd_fused_kernel(GnBwdFusedArgs fa) {
   }
 }
 
-template <typename T, bool FILM = false>
+template <typename T, bool FILM = false, bool DROP = false>
 static void launch_gn_bwd_fused(const GnBwdFusedArgs& fa, int ppt, dim3 grid, hipStream_t st) {
-  if (ppt <= 2) gn_bwd_fused_kernel<T, 2, FILM><<<grid, 512, 0, st>>>(fa);
-  else if (ppt <= 4) gn_bwd_fused_kernel<T, 4, FILM><<<grid, 512, 0, st>>>(fa);
-  else gn_bwd_fused_kernel<T, 8, FILM><<<grid, 512, 0, st>>>(fa);
+  if (ppt <= 2) gn_bwd_fused_kernel<T, 2, FILM, DROP><<<grid, 512, 0, st>>>(fa);
+  else if (ppt <= 4) gn_bwd_fused_kernel<T, 4, FILM, DROP><<<grid, 512, 0, st>>>(fa);
+  else gn_bwd_fused_kernel<T, 8, FILM, DROP><<<grid, 512, 0, st>>>(fa);
 }
 
 // channel run of the one-pass kernel for this shape (0: use the three-kernel chain): whole groups, one side of the concat seam, rows of
@@ -1389,6 +1412,98 @@ extern "C" int stedm_gn_bwd_film(const float* x1, int c1, const float* mean_rstd
     const dim3 grid(B, (unsigned)(((long)HW * Q + 1023) / 1024));
     if (mm_dtype == STEDM_F16) gn_bwd_apply_kernel<_Float16, true><<<grid, 256, 0, st>>>(a);
     else gn_bwd_apply_kernel<__bf16, true><<<grid, 256, 0, st>>>(a);
+  }
+  gn_bwd_film_param_kernel<<<(C + 15) / 16, 256, 0, st>>>(bc, B, C, gamma, beta, film, film_bstride, film_off, d_film, d_film_bstride, d_film_off, dgamma,
+                                                          dbeta, acc_param);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+// stedm_gn_bwd / stedm_gn_bwd_film for a GroupNorm whose activation went through the dropout pass (stedm_gn_apply16c_drop / _film_drop with the
+// same p, seed, site and effective step): the DROP instantiations, same kernel selection (gn_bwd_fused_cb), same parameter kernels. One
+// source tensor, C % 8 == 0. p == 0 is the plain entry.
+static int gn_bwd_drop_args(float p, unsigned long long seed, unsigned site, unsigned step, const int32_t* step_ptr, int C, DropArgs* d) {
+  STEDM_CHECK_ARG(p >= 0.f && p < 1.f, "gn_bwd_drop: p must be in [0, 1) (p=%g)", (double)p);
+  STEDM_CHECK_ARG(C > 0 && C % 8 == 0, "gn_bwd_drop: need C %% 8 == 0 (C=%d)", C);
+  *d = DropArgs{(uint64_t)seed, site, step, step_ptr, (uint32_t)lrint((double)p * 65536.0), (float)(1.0 / (1.0 - (double)p))};
+  return 0;
+}
+
+extern "C" int stedm_gn_bwd_drop(const float* x1, int c1, const float* x2, int c2, const float* mean_rstd, const float* gamma, const float* beta, int groups,
+                                 int act, const float* dA, const float* add, int B, int HW, float* ws, float* dx1, int acc1, float* dx2, int acc2,
+                                 void* dx16_hi, void* dx16_lo, int mm_dtype, float* dgamma, float* dbeta, int acc_param, float p, unsigned long long seed,
+                                 unsigned site, unsigned step, const int32_t* step_ptr, void* stream) {
+  const int C = c1;
+  DropArgs d;
+  if (const int rc = gn_bwd_drop_args(p, seed, site, step, step_ptr, C, &d)) return rc;
+  STEDM_CHECK_ARG(x2 == nullptr && c2 == 0 && dx2 == nullptr, "gn_bwd_drop: one source tensor only (x2, dx2 must be NULL)");
+  (void)acc2;
+  if (p == 0.f) return stedm_gn_bwd(x1, c1, nullptr, 0, mean_rstd, gamma, beta, groups, act, dA, add, B, HW, ws, dx1, acc1, nullptr, 0, dx16_hi, dx16_lo, mm_dtype,
+                                    dgamma, dbeta, acc_param, stream);
+  STEDM_CHECK_ARG(x1 && mean_rstd && gamma && beta && dA && ws && dx1 && dgamma && dbeta, "gn_bwd_drop: null pointer");
+  STEDM_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0 && C * 8 <= 65536 && B > 0 && HW > 0, "gn_bwd_drop: channel constraints");
+  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_bwd_drop: bad mm_dtype");
+  const int nslab = (HW + kGnBwdSlab - 1) / kGnBwdSlab, Q = C / 4;
+  float* part = ws;
+  float* bc = part + (long)B * nslab * C * 2;
+  float* gm = bc + (long)B * C * 2;
+  GnBwdArgs a{x1, nullptr, c1, 0, mean_rstd, gamma, beta, dA, groups, HW, act, part, gm, add, dx1, nullptr, acc1, 0, dx16_hi, dx16_lo, nullptr, 0, 0, d};
+  hipStream_t st = as_stream(stream);
+  int ppt = 0;
+  const int cb = gn_bwd_fused_cb(c1, 0, groups, HW, &ppt);
+  if (cb > 0) {
+    GnBwdFusedArgs fa{a, bc, cb};
+    if (mm_dtype == STEDM_F16) launch_gn_bwd_fused<_Float16, false, true>(fa, ppt, dim3(B, C / cb), st);
+    else launch_gn_bwd_fused<__bf16, false, true>(fa, ppt, dim3(B, C / cb), st);
+    gn_bwd_param_kernel<<<(C + 15) / 16, 256, 0, st>>>(bc, B, C, dgamma, dbeta, acc_param);
+    STEDM_LAUNCH_CHECK();
+    return 0;
+  }
+  gn_bwd_stats_kernel<false, true><<<dim3(B, nslab, (Q + 63) / 64), 256, 0, st>>>(a);
+  gn_bwd_fold_kernel<<<B, 256, (size_t)C * 8, st>>>(part, nslab, C, groups, HW, gamma, bc, gm);
+  gn_bwd_param_kernel<<<(C + 15) / 16, 256, 0, st>>>(bc, B, C, dgamma, dbeta, acc_param);
+  const dim3 grid(B, (unsigned)(((long)HW * Q + 1023) / 1024));
+  if (mm_dtype == STEDM_F16) gn_bwd_apply_kernel<_Float16, false, true><<<grid, 256, 0, st>>>(a);
+  else gn_bwd_apply_kernel<__bf16, false, true><<<grid, 256, 0, st>>>(a);
+  STEDM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int stedm_gn_bwd_film_drop(const float* x1, int c1, const float* mean_rstd, const float* gamma, const float* beta, int groups, int act,
+                                      const float* film, long film_bstride, int film_off, const float* dA, const float* add, int B, int HW, float* ws,
+                                      float* dx1, int acc1, void* dx16_hi, void* dx16_lo, int mm_dtype, float* dgamma, float* dbeta, int acc_param,
+                                      float* d_film, long d_film_bstride, int d_film_off, float p, unsigned long long seed, unsigned site, unsigned step,
+                                      const int32_t* step_ptr, void* stream) {
+  const int C = c1;
+  DropArgs d;
+  if (const int rc = gn_bwd_drop_args(p, seed, site, step, step_ptr, C, &d)) return rc;
+  if (p == 0.f) return stedm_gn_bwd_film(x1, c1, mean_rstd, gamma, beta, groups, act, film, film_bstride, film_off, dA, add, B, HW, ws, dx1, acc1, dx16_hi, dx16_lo,
+                                         mm_dtype, dgamma, dbeta, acc_param, d_film, d_film_bstride, d_film_off, stream);
+  STEDM_CHECK_ARG(x1 && mean_rstd && gamma && beta && film && dA && ws && dx1 && dgamma && dbeta && d_film, "gn_bwd_film_drop: null pointer");
+  STEDM_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0 && C * 8 <= 65536, "gn_bwd_film_drop: channel constraints");
+  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_bwd_film_drop: bad mm_dtype");
+  STEDM_CHECK_ARG(B > 0 && HW > 0 && film_off >= 0 && film_off % 4 == 0 && film_bstride % 4 == 0 && (film_bstride == 0 || film_bstride >= (long)film_off + 2 * C),
+                  "gn_bwd_film_drop: a film row holds 2 C values from film_off, 16-byte aligned (film_bstride=%ld film_off=%d C=%d)", film_bstride, film_off, C);
+  STEDM_CHECK_ARG(((uintptr_t)film & 15) == 0, "gn_bwd_film_drop: film must be 16-byte aligned");
+  STEDM_CHECK_ARG(d_film_off >= 0 && d_film_bstride >= (long)d_film_off + 2 * C, "gn_bwd_film_drop: a d_film row receives 2 C values from d_film_off");
+  const int nslab = (HW + kGnBwdSlab - 1) / kGnBwdSlab, Q = C / 4;
+  float* part = ws;
+  float* bc = part + (long)B * nslab * C * 2;
+  float* gm = bc + (long)B * C * 2;
+  GnBwdArgs a{x1, nullptr, c1, 0, mean_rstd, gamma, beta, dA, groups, HW, act, part, gm, add, dx1, nullptr, acc1, 0, dx16_hi, dx16_lo, film, film_bstride, film_off, d};
+  hipStream_t st = as_stream(stream);
+  int ppt = 0;
+  const int cb = gn_bwd_fused_cb(c1, 0, groups, HW, &ppt);
+  if (cb > 0) {
+    GnBwdFusedArgs fa{a, bc, cb};
+    if (mm_dtype == STEDM_F16) launch_gn_bwd_fused<_Float16, true, true>(fa, ppt, dim3(B, C / cb), st);
+    else launch_gn_bwd_fused<__bf16, true, true>(fa, ppt, dim3(B, C / cb), st);
+  } else {
+    gn_bwd_stats_kernel<true, true><<<dim3(B, nslab, (Q + 63) / 64), 256, 0, st>>>(a);
+    gn_bwd_fold_kernel<<<B, 256, (size_t)C * 8, st>>>(part, nslab, C, groups, HW, gamma, bc, gm, film + film_off, film_bstride);
+    const dim3 grid(B, (unsigned)(((long)HW * Q + 1023) / 1024));
+    if (mm_dtype == STEDM_F16) gn_bwd_apply_kernel<_Float16, true, true><<<grid, 256, 0, st>>>(a);
+    else gn_bwd_apply_kernel<__bf16, true, true><<<grid, 256, 0, st>>>(a);
   }
   gn_bwd_film_param_kernel<<<(C + 15) / 16, 256, 0, st>>>(bc, B, C, gamma, beta, film, film_bstride, film_off, d_film, d_film_bstride, d_film_off, dgamma,
                                                           dbeta, acc_param);

@@ -21,12 +21,36 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
 }
 
 // elementwise sites: the eight 16-bit uniforms of elements 8 g .. 8 g + 7 (field j = half (j & 1) of word j >> 1)
-__device__ __forceinline__ U4 drop_group(uint64_t g, uint32_t site, uint64_t seed) {
-  return philox4x32_10(U4{(uint32_t)g, (uint32_t)(g >> 32), site, 0u}, (uint32_t)seed, (uint32_t)(seed >> 32));
+// (step: the fourth counter word - 0 at the sViT sites, the forward counter of the U-Net's ResBlock sites)
+__device__ __forceinline__ U4 drop_group(uint64_t g, uint32_t site, uint64_t seed, uint32_t step = 0u) {
+  return philox4x32_10(U4{(uint32_t)g, (uint32_t)(g >> 32), site, step}, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 __device__ __forceinline__ uint32_t drop_u16(const U4& r, int j) {
   const uint32_t w = (j >> 1) == 0 ? r.x : (j >> 1) == 1 ? r.y : (j >> 1) == 2 ? r.z : r.w;
   return (w >> (16 * (j & 1))) & 0xFFFFu;
+}
+
+// ResBlock sites of the U-Net (include/stedm_hip.h, "train-mode dropout": site 0x55000000 + k): what a GroupNorm pass needs to regenerate
+// the keep mask of out_layers[2] from the counters - in the forward on the activation, in the backward on its gradient; no mask is stored.
+struct DropArgs {
+  uint64_t seed;
+  uint32_t site, step;
+  const int32_t* step_ptr;   // optional DEVICE word added to `step` when the kernel runs (a captured launch replays with new masks)
+  uint32_t thr16;
+  float inv_keep;            // (float)(1.0 / (1.0 - p))
+};
+__device__ __forceinline__ uint32_t drop_step_of(const DropArgs& d) { return d.step + (d.step_ptr ? (uint32_t)*d.step_ptr : 0u); }
+// four values against the two output words that hold their uniforms (fields 0 .. 3 or 4 .. 7 of a group): keep ? v * inv_keep : +0
+__device__ __forceinline__ void drop_apply(float& v0, float& v1, float& v2, float& v3, uint32_t w0, uint32_t w1, const DropArgs& d) {
+  v0 = (w0 & 0xFFFFu) >= d.thr16 ? v0 * d.inv_keep : 0.f;
+  v1 = (w0 >> 16) >= d.thr16 ? v1 * d.inv_keep : 0.f;
+  v2 = (w1 & 0xFFFFu) >= d.thr16 ? v2 * d.inv_keep : 0.f;
+  v3 = (w1 >> 16) >= d.thr16 ? v3 * d.inv_keep : 0.f;
+}
+// the four values of elements e .. e + 3 (e % 4 == 0: one half of an element group)
+__device__ __forceinline__ void drop_quad(float& v0, float& v1, float& v2, float& v3, uint64_t e, const DropArgs& d, uint32_t step) {
+  const U4 r = drop_group(e >> 3, d.site, d.seed, step);
+  drop_apply(v0, v1, v2, v3, (e & 4u) ? r.z : r.x, (e & 4u) ? r.w : r.y, d);
 }
 
 // attention site: one xorshift128 stream (Marsaglia 2003) per (query, sample-head, key half), seeded by Philox

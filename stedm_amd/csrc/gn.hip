@@ -5,6 +5,7 @@
 
 #include "common.hpp"
 #include "gn_fold.hpp"
+#include "dropmask.hpp"
 using namespace stedm;
 
 struct GnArgs {
@@ -408,6 +409,8 @@ struct GnApplyCArgs {
   const float* film;   // FiLM form (stedm_gn_apply16c_film): sample b's row film + b * film_bs + film_off = {scale[C], shift[C]}; NULL otherwise
   long film_bs;
   int film_off;
+  int drop;            // DROP form (stedm_gn_apply16c_drop / _film_drop): the keep mask of out_layers[2] on the activation, dropmask.hpp
+  DropArgs dr;
   __device__ GnPartials partials() const { return GnPartials{cs1, nslab1, c1, cs2, nslab2, c2, groups, HW, eps, mr}; }
 };
 
@@ -509,7 +512,11 @@ __global__ void __launch_bounds__(256) gn_apply16c_kernel(GnApplyCArgs a, int sl
 // 1024 - 2048 channels: six pixel-run blocks per sample each built the whole table for 11 pixels of streaming).
 // FILM: the per-sample modulation z = u (1 + scale) + shift between the affine and the activation (gn_fold.hpp: gn_film); the table gets
 // the two rows 1 + scale and shift of the block's sample. The plain instantiations compile to what they were.
-template <typename T, bool FILM = false>
+// DROP: train-mode dropout between the activation and the 16-bit rounding (openaimodel.py:241): element ((b HW + pixel) C + c) becomes
+// keep ? w * inv_keep : +0 with the mask of drop_quad (dropmask.hpp). A lane's quad is one half of an 8-element group and the lanes of a
+// pair hold the two halves of one group in BOTH cursors: each lane evaluates one group's Philox call per iteration and the pair trades
+// two words each way (with a call per quad the pass ran at 2.4 TB/s against the plain form's 3.6). Needs x2 == NULL.
+template <typename T, bool FILM = false, bool DROP = false>
 __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int slab, int cb) {
   typedef T V4 __attribute__((ext_vector_type(4)));
   __shared__ double dsu[256], dsq[256];
@@ -561,7 +568,11 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
   const bool guard = a.ovf != nullptr && __is_same(T, _Float16);
   const bool maybe_over = gn_fold_block(a.partials(), b, b2, c_lo / cpg, c_n / cpg, cb > 0 || sl == 0, dsu, dsq, lmean, lrstd) && guard;   // raw planes
   bool norm_over;                                                                                                                          // normalised planes
-  if constexpr (FILM) norm_over = gn_build_table_film(tab, lmean, lrstd, a.gamma, a.beta, a.film + (long)b * a.film_bs + a.film_off, C, cpg, a.HW, c_lo, c_n, guard);
+  uint32_t dstep = 0u;
+  if constexpr (DROP) dstep = drop_step_of(a.dr);
+  if constexpr (FILM && DROP) norm_over = gn_build_table_film(tab, lmean, lrstd, a.gamma, a.beta, a.film + (long)b * a.film_bs + a.film_off, C, cpg, a.HW, c_lo, c_n, guard, a.dr.inv_keep);
+  else if constexpr (FILM) norm_over = gn_build_table_film(tab, lmean, lrstd, a.gamma, a.beta, a.film + (long)b * a.film_bs + a.film_off, C, cpg, a.HW, c_lo, c_n, guard);
+  else if constexpr (DROP) norm_over = gn_build_table(tab, lmean, lrstd, a.gamma, a.beta, C, cpg, a.HW, c_lo, c_n, guard, a.dr.inv_keep);
   else norm_over = gn_build_table(tab, lmean, lrstd, a.gamma, a.beta, C, cpg, a.HW, c_lo, c_n, guard);
   unsigned bad_raw = 0u, bad_norm = 0u;
   const bool odd = threadIdx.x & 1;
@@ -583,6 +594,19 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
     const int i = it * 256 * U + (int)threadIdx.x;
     const bool live0 = !TAIL || i < total, live1 = !TAIL || i + 256 < total;
     uint2 oq[U], rq[U], olq[U], rlq[U];
+    uint2 dw[U];       // DROP: the two Philox words (four 16-bit uniforms) of this lane's quad of each cursor
+    if constexpr (DROP) {
+      // one Philox call per lane and iteration: the even lane evaluates the pair's 8-element group of cursor 0, the odd lane that of
+      // cursor 1 (the group starts at the even lane's quad), and the pair trades the halves the partner needs - words (z, w) of cursor 0
+      // go to the odd lane, words (x, y) of cursor 1 to the even lane
+      const int mk0 = odd ? 1 : 0;
+      const uint64_t e0 = (uint64_t)((long)b * a.HW + pixs[mk0]) * (uint64_t)C + (uint64_t)((q_lo + (qs[mk0] & ~1)) * 4);
+      const U4 r = drop_group(e0 >> 3, a.dr.site, a.dr.seed, dstep);
+      uint2 got;
+      got.x = __shfl_xor(odd ? r.x : r.z, 1, 64); got.y = __shfl_xor(odd ? r.y : r.w, 1, 64);
+      dw[0] = odd ? got : make_uint2(r.x, r.y);
+      dw[1] = odd ? make_uint2(r.z, r.w) : got;
+    }
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       const int c = (q_lo + qs[k]) * 4;
@@ -608,6 +632,7 @@ __global__ void __launch_bounds__(256) gn_apply16c_v8_kernel(GnApplyCArgs a, int
         w.x = (w.x - mn.x) * sc.x + bt.x; w.y = (w.y - mn.y) * sc.y + bt.y; w.z = (w.z - mn.z) * sc.z + bt.z; w.w = (w.w - mn.w) * sc.w + bt.w;
       }
       if (a.act == 1) { w.x = silu_f(w.x); w.y = silu_f(w.y); w.z = silu_f(w.z); w.w = silu_f(w.w); }
+      if constexpr (DROP) drop_apply(w.x, w.y, w.z, w.w, dw[k].x, dw[k].y, a.dr);
       oq[k] = __builtin_bit_cast(uint2, split16<T>(w, ol != nullptr, lo));
       if (norm_over) bad_norm |= f16_over4<T>(oq[k]);
       if (ol) olq[k] = __builtin_bit_cast(uint2, lo);
@@ -782,7 +807,15 @@ static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream)
       if (cb > 0 && (C % cb != 0 || c1 % cb != 0 || cb % unit != 0 || cb / cpg > 64)) cb = 0;
     }
     if (cb > 0) grid = dim3(B, C / cb);
-    if (a.film) {     // the FiLM form of the quad-pair kernel (stedm_gn_apply16c_film: one fp32 source)
+    if (a.drop) {     // the dropout forms (stedm_gn_apply16c_drop / _film_drop: one fp32 source)
+      if (a.film) {
+        if (mm_dtype == STEDM_F16) gn_apply16c_v8_kernel<_Float16, true, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
+        else gn_apply16c_v8_kernel<__bf16, true, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
+      } else {
+        if (mm_dtype == STEDM_F16) gn_apply16c_v8_kernel<_Float16, false, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
+        else gn_apply16c_v8_kernel<__bf16, false, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
+      }
+    } else if (a.film) {     // the FiLM form of the quad-pair kernel (stedm_gn_apply16c_film: one fp32 source)
       if (mm_dtype == STEDM_F16) gn_apply16c_v8_kernel<_Float16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
       else gn_apply16c_v8_kernel<__bf16, true><<<grid, 256, lds, as_stream(stream)>>>(a, slab, cb);
     } else if (a.x16) {      // the octet kernel (single-product planes only: the entry has no lo planes; cb is a multiple of 8)
@@ -801,6 +834,7 @@ static int gn_apply16c_launch(GnApplyCArgs a, int B, int mm_dtype, void* stream)
   }
   STEDM_CHECK_ARG(!a.x16, "gn_apply16c_x16: the 16-bit source form belongs to the vector kernel");
   STEDM_CHECK_ARG(!a.film, "gn_apply16c_film: the FiLM form belongs to the 8-wide table kernel");
+  STEDM_CHECK_ARG(!a.drop, "gn_apply16c_drop: the dropout form belongs to the 8-wide table kernel");
   if (mm_dtype == STEDM_F16)
     gn_apply16c_kernel<_Float16><<<grid, 256, 0, as_stream(stream)>>>(a, slab);
   else
@@ -873,4 +907,53 @@ extern "C" int stedm_gn_apply16c_film(const float* x1, int c1, const float* cs1,
   GnApplyCArgs a{x1, nullptr, cs1, nullptr, c1, 0, 0, groups, HW, act, nslab1, 0, gamma, beta, eps, out_hi, out_lo, raw_hi, raw_lo, mean_rstd,
                  mm_dtype == STEDM_F16 ? f16_guard_flag() : nullptr, nullptr, film, film_bstride, film_off};
   return gn_apply16c_launch(a, B, mm_dtype, stream);
+}
+
+// The dropout forms of the two passes above: out_layers[0..2] of a ResBlock in train() (openaimodel.py:239-241), GroupNorm (+ FiLM) + SiLU +
+// Dropout(p) into the 16-bit planes. The mask is the stream of include/stedm_hip.h ("train-mode dropout", ResBlock sites); the effective
+// step is (uint32)(step + (step_ptr ? *step_ptr : 0)), read when the kernel runs. One source tensor, no raw planes, C % 8 == 0; p == 0 is the
+// plain entry. The guard's switch is taken on the affine scaled by inv_keep.
+static int gn_drop_args(float p, unsigned long long seed, unsigned site, unsigned step, const int32_t* step_ptr, DropArgs* d) {
+  STEDM_CHECK_ARG(p >= 0.f && p < 1.f, "gn dropout: p must be in [0, 1) (p=%g)", (double)p);
+  *d = DropArgs{(uint64_t)seed, site, step, step_ptr, (uint32_t)lrint((double)p * 65536.0), (float)(1.0 / (1.0 - (double)p))};
+  return 0;
+}
+
+extern "C" int stedm_gn_apply16c_film_drop(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2,
+                                           int x2_bmod, const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                                           void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, const float* film,
+                                           long film_bstride, int film_off, int mm_dtype, float p, unsigned long long seed, unsigned site,
+                                           unsigned step, const int32_t* step_ptr, void* stream) {
+  DropArgs d;
+  if (const int rc = gn_drop_args(p, seed, site, step, step_ptr, &d)) return rc;
+  STEDM_CHECK_ARG(raw_hi == nullptr && raw_lo == nullptr, "gn_apply16c_drop: no raw planes");
+  if (p == 0.f) {
+    if (film) return stedm_gn_apply16c_film(x1, c1, cs1, nslab1, x2, c2, cs2, nslab2, x2_bmod, gamma, beta, eps, groups, act, B, HW, out_hi, out_lo, nullptr,
+                                            nullptr, mean_rstd, film, film_bstride, film_off, mm_dtype, stream);
+    STEDM_CHECK_ARG(x2 == nullptr && c2 == 0 && cs2 == nullptr, "gn_apply16c_drop: one source tensor only (x2 must be NULL)");
+    return stedm_gn_apply16c_mr(x1, c1, cs1, nslab1, nullptr, 0, nullptr, 0, 0, gamma, beta, eps, groups, act, B, HW, out_hi, out_lo, nullptr, nullptr,
+                                mean_rstd, mm_dtype, stream);
+  }
+  STEDM_CHECK_ARG(x1 && cs1 && out_hi && gamma && beta, "gn_apply16c_drop: null pointer");
+  STEDM_CHECK_ARG(x2 == nullptr && c2 == 0 && cs2 == nullptr, "gn_apply16c_drop: one source tensor only (x2 must be NULL)");
+  (void)nslab2; (void)x2_bmod;
+  const int C = c1;
+  STEDM_CHECK_ARG(C > 0 && C % 8 == 0 && (size_t)(film ? 5 : 3) * C * sizeof(float) <= 48 * 1024,
+                  "gn_apply16c_drop: need C %% 8 == 0 and C <= 4096 (2456 with film) (C=%d)", C);
+  STEDM_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0, "gn_apply16c_drop: need groups <= 64 and C %% groups == 0");
+  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "gn_apply16c_drop: bad mm_dtype");
+  STEDM_CHECK_ARG(nslab1 > 0 && B > 0 && HW > 0, "gn_apply16c_drop: nslab1 must be the slot count of cs1");
+  STEDM_CHECK_ARG(!film || (film_off >= 0 && (film_bstride == 0 || film_bstride >= (long)film_off + 2 * C)),
+                  "gn_apply16c_film_drop: a row holds 2 C values from film_off (film_bstride=%ld film_off=%d C=%d)", film_bstride, film_off, C);
+  GnApplyCArgs a{x1, nullptr, cs1, nullptr, c1, 0, 0, groups, HW, act, nslab1, 0, gamma, beta, eps, out_hi, out_lo, nullptr, nullptr, mean_rstd,
+                 mm_dtype == STEDM_F16 ? f16_guard_flag() : nullptr, nullptr, film, film ? film_bstride : 0, film ? film_off : 0, 1, d};
+  return gn_apply16c_launch(a, B, mm_dtype, stream);
+}
+
+extern "C" int stedm_gn_apply16c_drop(const float* x1, int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
+                                      const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
+                                      void* out_hi, void* out_lo, void* raw_hi, void* raw_lo, float* mean_rstd, int mm_dtype, float p,
+                                      unsigned long long seed, unsigned site, unsigned step, const int32_t* step_ptr, void* stream) {
+  return stedm_gn_apply16c_film_drop(x1, c1, cs1, nslab1, x2, c2, cs2, nslab2, x2_bmod, gamma, beta, eps, groups, act, B, HW, out_hi, out_lo, raw_hi, raw_lo,
+                                     mean_rstd, nullptr, 0, 0, mm_dtype, p, seed, site, step, step_ptr, stream);
 }

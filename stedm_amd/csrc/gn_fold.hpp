@@ -90,8 +90,9 @@ __device__ __forceinline__ bool gn_norm_over(const float* gamma, const float* be
 
 // The same switch for the channels [c_lo, c_lo + c_n) while building their rows of the LDS table tab[3][C] of the 8-wide kernels:
 // tab[c] = mean, tab[C + c] = rstd * gamma, tab[2 C + c] = beta. Waits for the fold's lmean / lrstd first; the table is complete on return.
+// gscale: a factor on the plane values after the activation (the 1 / (1 - p) of a dropout pass; |act(z)| <= |z|): the switch is taken on the scaled affine.
 __device__ __forceinline__ bool gn_build_table(float* tab, const float* lmean, const float* lrstd, const float* gamma, const float* beta, int C,
-                                               int cpg, int HW, int c_lo, int c_n, bool guard) {
+                                               int cpg, int HW, int c_lo, int c_n, bool guard, float gscale = 1.0f) {
   __syncthreads();
   int nb = 0;
   const float rn = sqrtf((float)cpg * (float)HW);
@@ -101,7 +102,7 @@ __device__ __forceinline__ bool gn_build_table(float* tab, const float* lmean, c
     tab[c] = lmean[gc];
     tab[C + c] = lrstd[gc] * gmc;
     tab[2 * C + c] = btc;
-    if (guard) nb |= gn_norm_admits_over(rn, gmc, btc);
+    if (guard) nb |= gn_norm_admits_over(rn, gmc * gscale, btc * gscale);
   }
   return __syncthreads_or(nb) != 0;
 }
@@ -120,7 +121,7 @@ __device__ __forceinline__ float gn_film(float x, float mean, float rg, float be
 // switch is evaluated on the sample's effective affine gamma (1 + scale), beta (1 + scale) + shift: a plane value can leave the fp16
 // range through scale / shift alone. film_row: the sample's row, already offset (film + b * film_bstride + film_off).
 __device__ __forceinline__ bool gn_build_table_film(float* tab, const float* lmean, const float* lrstd, const float* gamma, const float* beta,
-                                                    const float* film_row, int C, int cpg, int HW, int c_lo, int c_n, bool guard) {
+                                                    const float* film_row, int C, int cpg, int HW, int c_lo, int c_n, bool guard, float gscale = 1.0f) {
   __syncthreads();
   int nb = 0;
   const float rn = sqrtf((float)cpg * (float)HW);
@@ -133,7 +134,7 @@ __device__ __forceinline__ bool gn_build_table_film(float* tab, const float* lme
     tab[2 * C + c] = btc;
     tab[3 * C + c] = op;
     tab[4 * C + c] = sh;
-    if (guard) nb |= gn_norm_admits_over(rn, gmc * op, btc * op + sh);
+    if (guard) nb |= gn_norm_admits_over(rn, gmc * op * gscale, (btc * op + sh) * gscale);
   }
   return __syncthreads_or(nb) != 0;
 }

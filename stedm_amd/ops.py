@@ -364,6 +364,36 @@ def gn_apply16c_film(x1: torch.Tensor, cs1: torch.Tensor, out_hi: torch.Tensor, 
                                        film.data_ptr(), int(film_bstride), int(film_off), prec.mm_dtype, _stream()), "stedm_gn_apply16c_film")
 
 
+def _drop_tail(drop):
+    """(p, seed, site, step, step_ptr) of a ResBlock dropout site as the five trailing C arguments; step_ptr: int32[1] device tensor or None"""
+    p, seed, site, step, step_ptr = drop
+    if step_ptr is not None:
+        assert step_ptr.is_cuda and step_ptr.dtype == torch.int32 and step_ptr.numel() >= 1
+    return float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF, _ptr(step_ptr)
+
+
+def gn_apply16c_drop(x1: torch.Tensor, cs1: torch.Tensor, out_hi: torch.Tensor, out_lo: Optional[torch.Tensor], prec: Precision, gamma: torch.Tensor,
+                     beta: torch.Tensor, drop, eps: float = 1e-5, groups: int = 32, act: int = 0, mean_rstd: Optional[torch.Tensor] = None,
+                     film: Optional[torch.Tensor] = None, film_off: int = 0, film_bstride: int = 0) -> None:
+    """Dropout(act(GroupNorm(x1) [* (1 + scale) + shift])) -> 16-bit planes (stedm_gn_apply16c_drop; with `film` stedm_gn_apply16c_film_drop).
+    drop = (p, seed, site, step, step_ptr): the mask stream of include/stedm_hip.h ("train-mode dropout", ResBlock sites); the kernel uses
+    step + step_ptr[0] (step_ptr: device int32[1] or None)."""
+    _chk(x1, name="x1")
+    B, C = x1.shape[0], x1.shape[-1]
+    HW = x1.numel() // (B * C)
+    if mean_rstd is not None:
+        assert mean_rstd.dtype == torch.float32 and mean_rstd.is_contiguous() and tuple(mean_rstd.shape) == (B, groups, 2)
+    head = (x1.data_ptr(), C, cs1.data_ptr(), cs1.shape[1], None, 0, None, 0, 0, gamma.data_ptr(), beta.data_ptr(), float(eps), groups, act, B, HW,
+            out_hi.data_ptr(), _ptr(out_lo), None, None, _ptr(mean_rstd))
+    if film is None:
+        check(lib().stedm_gn_apply16c_drop(*head, prec.mm_dtype, *_drop_tail(drop), _stream()), "stedm_gn_apply16c_drop")
+    else:
+        _chk(film, name="film")
+        assert film_off >= 0 and film.numel() >= (B - 1) * film_bstride + film_off + 2 * C, "film rows out of range"
+        check(lib().stedm_gn_apply16c_film_drop(*head, film.data_ptr(), int(film_bstride), int(film_off), prec.mm_dtype, *_drop_tail(drop), _stream()),
+              "stedm_gn_apply16c_film_drop")
+
+
 def gn_apply16c_x16(c1: int, cs1: torch.Tensor, x2: Optional[torch.Tensor], cs2: Optional[torch.Tensor], out_hi: torch.Tensor, raw_hi: torch.Tensor,
                     prec: Precision, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, groups: int = 32, act: int = 0, x2_bmod: int = 0) -> None:
     """act(GroupNorm([x1|x2])) where x1 (c1 channels) already sits as 16-bit values in channels [0, c1) of raw_hi [B,H,W,c1+c2] (written there by
@@ -1510,6 +1540,30 @@ def gn_bwd_film(x1, mean_rstd, gamma, beta, groups: int, act: int, film, film_of
                                   None if dx16 is None else dx16[0].data_ptr(), None if dx16 is None else _ptr(dx16[1]), prec.mm_dtype,
                                   dgamma.data_ptr(), dbeta.data_ptr(), int(acc_param), d_film.data_ptr(), d_film.stride(0), int(d_film_off),
                                   _stream()), "stedm_gn_bwd_film")
+
+
+def gn_bwd_drop(x1, mean_rstd, gamma, beta, groups: int, act: int, dA, add, ws, dx1, acc1: bool, dx16, prec: Precision, dgamma, dbeta,
+                acc_param: bool, drop, film=None, film_off: int = 0, film_bstride: int = 0, d_film=None, d_film_off: int = 0) -> None:
+    """gn_bwd / gn_bwd_film (with `film`) of a GroupNorm whose activation went through gn_apply16c_drop with the same `drop` =
+    (p, seed, site, step, step_ptr): dA is masked and scaled on load (stedm_gn_bwd_drop / stedm_gn_bwd_film_drop). One source tensor."""
+    _chk(x1, name="x1"); _chk(dA, name="dA")
+    B, C = x1.shape[0], x1.shape[-1]
+    HW = x1.numel() // (B * C)
+    assert dA.numel() == B * HW * C and ws.numel() >= gn_bwd_ws_floats(B, HW, C, groups)
+    d16 = (None if dx16 is None else dx16[0].data_ptr(), None if dx16 is None else _ptr(dx16[1]))
+    if film is None:
+        check(lib().stedm_gn_bwd_drop(x1.data_ptr(), C, None, 0, mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, act, dA.data_ptr(),
+                                      _ptr(add), B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1), None, 0, *d16, prec.mm_dtype, dgamma.data_ptr(),
+                                      dbeta.data_ptr(), int(acc_param), *_drop_tail(drop), _stream()), "stedm_gn_bwd_drop")
+        return
+    _chk(film, name="film")
+    assert film_off >= 0 and film.numel() >= (B - 1) * film_bstride + film_off + 2 * C, "film rows out of range"
+    assert d_film.dtype == torch.float32 and d_film.dim() == 2 and d_film.shape[0] == B and d_film.stride(1) == 1
+    assert 0 <= d_film_off and d_film_off + 2 * C <= d_film.shape[1], "d_film columns out of range"
+    check(lib().stedm_gn_bwd_film_drop(x1.data_ptr(), C, mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, act, film.data_ptr(),
+                                       int(film_bstride), int(film_off), dA.data_ptr(), _ptr(add), B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1),
+                                       *d16, prec.mm_dtype, dgamma.data_ptr(), dbeta.data_ptr(), int(acc_param), d_film.data_ptr(), d_film.stride(0),
+                                       int(d_film_off), *_drop_tail(drop), _stream()), "stedm_gn_bwd_film_drop")
 
 
 def im2col_t16(src16: torch.Tensor, dst16: torch.Tensor, ks: int, mode: int) -> None:

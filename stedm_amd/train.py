@@ -137,13 +137,19 @@ class UNetTrainer:
                         norm.eps, norm.num_groups, act)
         return hi, lo
 
-    def _film16(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int):
-        """_norm16 for out_layers[0] of a scale-shift-norm block: SiLU(GroupNorm(h) * (1 + scale) + shift) in the backward's operand format"""
+    def _film16(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int, drop=None):
+        """_norm16 for out_layers[0] of a scale-shift-norm block: SiLU(GroupNorm(h) * (1 + scale) + shift) in the backward's operand format.
+        drop: the forward's dropout arguments of a live block (film may then be None) - the recomputed planes carry the forward's mask,
+        the counter has not moved since"""
         m = self.m
         kept = m._saved16.get((id(norm), h.data_ptr()))
         if kept is not None and self.bprec.npass == 1:
             return kept
         hi, lo = self._planes("a16", tuple(h.shape))
+        if drop is not None:
+            ops.gn_apply16c_drop(h, m._chan_stats(h), hi, lo, self.bprec, norm.weight, norm.bias, drop, norm.eps, norm.num_groups, 1,
+                                 film=film, film_off=film_off, film_bstride=film_bstride)
+            return hi, lo
         ops.gn_apply16c_film(h, m._chan_stats(h), hi, lo, self.bprec, norm.weight, norm.bias, film, film_off, film_bstride, norm.eps,
                              norm.num_groups, 1)
         return hi, lo
@@ -377,9 +383,10 @@ class UNetTrainer:
         ops.gn_bwd(x1, x2, mr, norm.weight, norm.bias, G, act, dA, add, ws, g1, a1, g2, a2, dx16, self.bprec, self._param_grad(norm.weight),
                    self._param_grad(norm.bias), False)
 
-    def _gn_bwd_film(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int, dA, dx16, d_film, d_film_off: int):
+    def _gn_bwd_film(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int, dA, dx16, d_film, d_film_off: int, drop=None):
         """backward of SiLU(GroupNorm(h) * (1 + scale) + shift): dh, the GroupNorm's parameter gradients, and dscale | dshift into columns
-        [d_film_off, d_film_off + 2 C) of d_film (stedm_gn_bwd_film)"""
+        [d_film_off, d_film_off + 2 C) of d_film (stedm_gn_bwd_film). drop: the block's dropout was live - dA is masked and scaled on load
+        (stedm_gn_bwd_drop, or stedm_gn_bwd_film_drop with film)"""
         m = self.m
         B, C = h.shape[0], h.shape[-1]
         HW = h.numel() // (B * C)
@@ -390,6 +397,11 @@ class UNetTrainer:
             ops.gn_fold(m._chan_stats(h), None, G, HW, norm.eps, mr)
         ws = self._buf("gnws", (ops.gn_bwd_ws_floats(B, HW, C, G),))
         g1, a1 = self._grad_of(h)
+        if drop is not None:
+            ops.gn_bwd_drop(h, mr, norm.weight, norm.bias, G, 1, dA, None, ws, g1, a1, dx16, self.bprec, self._param_grad(norm.weight),
+                            self._param_grad(norm.bias), False, drop, film=film, film_off=film_off, film_bstride=film_bstride, d_film=d_film,
+                            d_film_off=d_film_off)
+            return
         ops.gn_bwd_film(h, mr, norm.weight, norm.bias, G, 1, film, film_off, film_bstride, dA, None, ws, g1, a1, dx16, self.bprec,
                         self._param_grad(norm.weight), self._param_grad(norm.bias), False, d_film, d_film_off)
 
@@ -400,6 +412,8 @@ class UNetTrainer:
         m = self.m
         m._tape = []
         try:
+            if m.dropout_live():
+                m._dropout_begin()       # one launch moves the mask counter; every drop pass of this forward and its backward reads it
             out = m._forward_impl(x, c_concat, t, [context], None, uniform_t=False)
         except Exception:
             m._tape = None
@@ -537,11 +551,14 @@ class UNetTrainer:
             add = dout
         # conv2 and its GroupNorm + SiLU
         film = rb.use_scale_shift_norm
+        drop = self.m._drop_used.get(id(rb))       # the forward's dropout arguments when the block's dropout was live
         if film:
             # scale | shift of this block: its columns of the concatenated embedding projection, or the style projection (row stride = width)
             fsrc = self.tape_film[1] if emb_off is None else self.tape_film[0]
             foff, fbs = (0 if emb_off is None else emb_off), fsrc.shape[1]
-            h16 = self._film16(rb.out_layers[0], h, fsrc, foff, fbs)
+            h16 = self._film16(rb.out_layers[0], h, fsrc, foff, fbs, drop)
+        elif drop is not None:
+            h16 = self._film16(rb.out_layers[0], h, None, 0, 0, drop)
         else:
             h16 = self._norm16(rb.out_layers[0], 1, h)
         self._wgrad(h16, dout16, dout, conv2.weight, 3, 0)
@@ -556,7 +573,7 @@ class UNetTrainer:
                 dmat, doff = self.dEs, 0
             else:
                 dmat, doff = self.dE, emb_off
-            self._gn_bwd_film(rb.out_layers[0], h, fsrc, foff, fbs, dA2, dh16, dmat, doff)
+            self._gn_bwd_film(rb.out_layers[0], h, fsrc, foff, fbs, dA2, dh16, dmat, doff, drop)
             dh = self.G[h.data_ptr()]
             self._bias_grad(dh, conv1.bias)
             blk = dmat
@@ -566,7 +583,10 @@ class UNetTrainer:
             self._colsum(blk, self._param_grad(rb.emb_layers[1].bias))       # emb_layers[1].bias: the column sums of its dE block
             self._res_bwd_front(rb, x1, x2, dh, dh16, add, cin)
             return
-        self._gn_bwd(rb.out_layers[0], 1, h, None, dA2, None, dx16=dh16)
+        if drop is not None:
+            self._gn_bwd_film(rb.out_layers[0], h, None, 0, 0, dA2, dh16, None, 0, drop)
+        else:
+            self._gn_bwd(rb.out_layers[0], 1, h, None, dA2, None, dx16=dh16)
         dh = self.G[h.data_ptr()]
         # the embedding enters between conv1 and the second GroupNorm (openaimodel.py:276-287): its gradient is the per-sample
         # channel sum of dh, conv1's bias gradient the batch total
@@ -1341,6 +1361,8 @@ class UNetTrainer:
             key = key + (objective.key(),)           # the captured loss launch holds the objective's scalars and table pointers
         if self.max_grad_norm is not None:
             key = key + (("max_grad_norm", float(self.max_grad_norm)),)      # a baked argument of the captured norm launch
+        if self.m.dropout_live():
+            key = key + (("dropout_seed", self.m._dropout_seed_now()),)      # baked into the captured drop passes (the step is a device word)
         g = getattr(self, "_graph", None)
         if g is not None and (g["key"] != key or g["token"] != self.m.freshness_token() or g["host_step"] != self.step_count):
             g = self._graph = None                    # someone else moved the parameters or the counters: the captured plan is stale
@@ -1363,6 +1385,9 @@ class UNetTrainer:
         self.step_count += 1
         if self.ema_decay is not None:
             self.ema_updates += 1
+        if g["drop"]:                        # the captured step_advance moved the mask counter
+            self.m._drop_step = (self.m._drop_step + 1) & 0xFFFFFFFF
+            self.m.last_dropout = (self.m.last_dropout[0], self.m._drop_step)
         ops.note_raw_write()                 # (the replayed optimizer wrote the parameters through raw pointers, like the eager launches it stands for)
         self._after_optimizer(g["fu"])
         g["token"], g["host_step"] = self.m.freshness_token(), self.step_count
@@ -1379,6 +1404,7 @@ class UNetTrainer:
         self._graph_window(g)
         # the capture pass runs the host side of one step without running its kernels: counters and flags are put back afterwards
         keep = (self.step_count, self.ema_updates, self.overlap_opt_fires, self.overlap_fires)
+        keep_drop = (self.m._drop_step, self.m.last_dropout)
         graph = torch.cuda.CUDAGraph()
         torch.cuda.synchronize()
         self._cap_sched = (g["sched"], g["idx"])
@@ -1389,7 +1415,8 @@ class UNetTrainer:
         finally:
             self._cap_sched = None
             self.step_count, self.ema_updates, self.overlap_opt_fires, self.overlap_fires = keep
+            self.m._drop_step, self.m.last_dropout = keep_drop
         fu = self._fused_opt() if self.fuse_packs else None
-        g.update(graph=graph, loss=loss, fu=fu, token=self.m.freshness_token(), host_step=self.step_count)
+        g.update(graph=graph, loss=loss, fu=fu, token=self.m.freshness_token(), host_step=self.step_count, drop=self.m.dropout_live())
         self._graph = g
         return g

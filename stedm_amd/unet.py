@@ -73,7 +73,8 @@ class Downsample(nn.Module):
 
 class ResBlock(TimestepBlock):
     """openaimodel.py:176-288 without up / down. use_scale_shift_norm (:199, :280-284): emb_layers emits 2 * out_channels values and the block
-    computes h = out_norm(h) * (1 + scale) + shift in place of h + emb_out (AdaGN / FiLM)."""
+    computes h = out_norm(h) * (1 + scale) + shift in place of h + emb_out (AdaGN / FiLM). dropout (:241): out_layers[2], live in train();
+    drop_site is the block's ordinal in execution order over all ResBlocks of its UNetModel (the mask stream's site, include/stedm_hip.h)."""
 
     def __init__(self, channels, emb_channels, dropout, out_channels=None, use_conv=False, use_scale_shift_norm=False,
                  dims=2, use_checkpoint=False, up=False, down=False):
@@ -84,6 +85,7 @@ class ResBlock(TimestepBlock):
         self.channels = channels
         self.emb_channels = emb_channels
         self.dropout = dropout
+        self.drop_site = 0
         self.out_channels = out_channels or channels
         self.use_scale_shift_norm = bool(use_scale_shift_norm)
         self.in_layers = nn.Sequential(GroupNorm32(32, channels), nn.SiLU(), nn.Conv2d(channels, self.out_channels, 3, padding=1))
@@ -144,9 +146,11 @@ class UNetModel(nn.Module):
             assert use_spatial_transformer, "context_dim is only meaningful with use_spatial_transformer=True"
             if not isinstance(context_dim, int):
                 context_dim = list(context_dim)
-        if num_classes is not None or n_embed is not None or resblock_updown or not conv_resample or dims != 2 or dropout != 0:
-            raise NotImplementedError("num_classes / n_embed / resblock_updown / conv_resample=False / dims != 2 / dropout: "
+        if num_classes is not None or n_embed is not None or resblock_updown or not conv_resample or dims != 2:
+            raise NotImplementedError("num_classes / n_embed / resblock_updown / conv_resample=False / dims != 2: "
                                       "not used by the reference configs, not implemented")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f"dropout must be in [0, 1), got {dropout}")
         if num_heads_upsample == -1:
             num_heads_upsample = num_heads
         if num_heads == -1:
@@ -221,6 +225,16 @@ class UNetModel(nn.Module):
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(GroupNorm32(32, ch), nn.SiLU(), zero_module(nn.Conv2d(model_channels, out_channels, 3, padding=1)))
+        for k, rb in enumerate(self._all_resblocks()):
+            rb.drop_site = k
+        # train-mode dropout (out_layers[2] of every ResBlock, live iff the block is in train() and dropout > 0). The masks are counter-based
+        # (include/stedm_hip.h, "train-mode dropout"): seed - None: drawn once from torch's generator at first use, so torch.manual_seed governs
+        # it -, site 0x55000000 + drop_site, and a forward counter that UNetTrainer.forward advances by one device launch (eager or captured)
+        self.dropout_seed: Optional[int] = None
+        self._drop_ctr: Optional[torch.Tensor] = None      # device int32[1]: the forward counter the kernels read
+        self._drop_step = 0                                 # its host mirror
+        self._drop_used: Dict[int, tuple] = {}              # id(block) -> the drop arguments of the last training forward (the backward's)
+        self.last_dropout: Optional[Tuple[int, int]] = None   # (effective seed, step) of the last training forward with live dropout
 
         # ---- engine state (not part of the state dict)
         self._packed: Dict[int, _Packed] = {}
@@ -297,6 +311,61 @@ class UNetModel(nn.Module):
                 if isinstance(layer, ResBlock):
                     out.append(layer)
         return out
+
+    def _all_resblocks(self) -> List[ResBlock]:
+        """Every ResBlock in execution order, the inner block of ResBlockStyle included: the order of the dropout sites."""
+        out = []
+        for blk in list(self.input_blocks) + [self.middle_block] + list(self.output_blocks):
+            for layer in blk:
+                if isinstance(layer, ResBlock):
+                    out.append(layer)
+                elif isinstance(layer, ResBlockStyle):
+                    out.append(layer.block)
+        return out
+
+    @staticmethod
+    def _drop_live(rb: ResBlock) -> bool:
+        return bool(rb.training and rb.dropout > 0)
+
+    def dropout_live(self) -> bool:
+        """Is train-mode dropout live in any ResBlock (the block in train() and dropout > 0)?"""
+        return self.dropout > 0 and any(self._drop_live(rb) for rb in self._all_resblocks())
+
+    @staticmethod
+    def rank_dropout_seed(seed: int, rank: int) -> int:
+        """The seed rank `rank` uses under torch.distributed, so that ranks do not drop the same pattern on their shards"""
+        return (int(seed) ^ ((int(rank) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF)) & 0xFFFFFFFFFFFFFFFF
+
+    def set_dropout_step(self, step: int) -> None:
+        """Set the forward counter (device word and host mirror): the next training forward advances it and uses step + 1."""
+        dev = next(self.parameters()).device
+        step = int(step) & 0xFFFFFFFF
+        if self._drop_ctr is None or self._drop_ctr.device != dev:
+            self._drop_ctr = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._drop_ctr.fill_(step - (1 << 32) if step >= (1 << 31) else step)
+        self._drop_step = step
+
+    def _dropout_seed_now(self) -> int:
+        """dropout_seed, drawn from torch's generator first when it is still None (once: it stays)"""
+        if self.dropout_seed is None:
+            self.dropout_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        return self.dropout_seed
+
+    def _dropout_begin(self) -> None:
+        """Start of a training forward with live dropout: one launch advances the device counter (the same launch eager or captured), the
+        host mirror follows, and the seed is fixed (drawn once when dropout_seed is None)."""
+        import torch.distributed as dist
+        if self._drop_ctr is None or self._drop_ctr.device != next(self.parameters()).device:
+            self.set_dropout_step(self._drop_step)
+        seed = self._dropout_seed_now()
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        ops.step_advance(self._drop_ctr, 1)
+        self._drop_step = (self._drop_step + 1) & 0xFFFFFFFF
+        self.last_dropout = (self.rank_dropout_seed(seed, rank), self._drop_step)
+
+    def _drop_args(self, rb: ResBlock) -> tuple:
+        """(p, seed, site, step, step_ptr) of a live block for ops.gn_apply16c_drop / ops.gn_bwd_drop: the step is read from the device counter"""
+        return (float(rb.dropout), self.last_dropout[0], 0x55000000 + rb.drop_site, 0, self._drop_ctr)
 
     def _emb_columns(self) -> Tuple[List[Tuple[ResBlock, int]], int]:
         """([(block, first column)], columns) of the concatenated emb_layers projection: every timestep block takes the width of its own
@@ -517,9 +586,10 @@ class UNetModel(nn.Module):
                         norm.weight, norm.bias, norm.eps, norm.num_groups, act, x2_bmod, raw, mean_rstd=mr)
         return ((hi, lo), raw) if want_raw else (hi, lo)
 
-    def _film16(self, norm: nn.GroupNorm, h, film, film_off, film_bstride):
+    def _film16(self, norm: nn.GroupNorm, h, film, film_off, film_bstride, drop=None):
         """SiLU(GroupNorm(h) * (1 + scale) + shift) as 16-bit planes, scale | shift = columns [film_off, film_off + 2 C) of sample b's row of
-        `film` (row stride film_bstride; 0: one shared row). Training keeps the planes and {mean, rstd} exactly as _norm16 / _res do."""
+        `film` (row stride film_bstride; 0: one shared row). Training keeps the planes and {mean, rstd} exactly as _norm16 / _res do.
+        drop (_drop_args): the block's dropout is live - the same pass masks and scales the activation (film may then be None: a plain block)."""
         B, H, W, C = h.shape
         keep = self._tape is not None and self.precision.npass == 1 and self.precision.mm_dtype == BF16
         if keep:
@@ -533,6 +603,10 @@ class UNetModel(nn.Module):
             self._mr_ctr += 1
             mr = self._buf(f"keep{self._mr_ctr}.mr", (B, norm.num_groups, 2))
             self._saved_mr[(id(norm), h.data_ptr())] = mr
+        if drop is not None:
+            ops.gn_apply16c_drop(h, self._chan_stats(h), hi, lo, self.precision, norm.weight, norm.bias, drop, norm.eps, norm.num_groups, 1,
+                                 mean_rstd=mr, film=film, film_off=film_off, film_bstride=film_bstride)
+            return hi, lo
         ops.gn_apply16c_film(h, self._chan_stats(h), hi, lo, self.precision, norm.weight, norm.bias, film, film_off, film_bstride, norm.eps,
                              norm.num_groups, 1, mean_rstd=mr)
         return hi, lo
@@ -584,8 +658,13 @@ class UNetModel(nn.Module):
         # A scale-shift-norm block (FiLM): the embedding row does not add onto h (no epilogue term) but modulates out_layers' GroupNorm per
         # sample, so none of the producer-side forms of that GroupNorm applies (gn_next in the epilogue / reduce pass, gn_coop, the
         # 16-bit-only h): the convolution writes fp32 h and its statistics, and one stedm_gn_apply16c_film pass writes the planes (_film16)
+        # Live dropout (train(), dropout > 0) sits between that GroupNorm's SiLU and the 16-bit rounding: the same treatment - fp32 h and its
+        # statistics, then one stedm_gn_apply16c_drop / _film_drop pass; the embedding row still adds onto h in the epilogue of a plain block
         film = rb.use_scale_shift_norm
-        if not film and ((prec.npass == 1 and (self._tape is None or prec.mm_dtype == BF16)) or (prec.npass == 3 and self._tape is None)):
+        drop = None
+        if self._tape is not None and self._drop_live(rb):
+            drop = self._drop_used[id(rb)] = self._drop_args(rb)
+        if not film and drop is None and ((prec.npass == 1 and (self._tape is None or prec.mm_dtype == BF16)) or (prec.npass == 3 and self._tape is None)):
             if self._tape is None:
                 # NOT the planes _norm16 would hand out: for cin == cout those are the planes this convolution is reading, and an epilogue
                 # that writes the GroupNorm output would overwrite rows other tiles still gather
@@ -629,8 +708,8 @@ class UNetModel(nn.Module):
             kw1 = dict(prec=prec, bias=pk.bias, emb=None if film else emb_all, emb_offset=emb_off, emb_bstride=emb_bstride, w_frag=pk.frag,
                        chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16, gn_next=gn_next, coop=coop)
             self._in_conv(tag, rb, pk, a16, x1.shape[-1], x2_bmod if x2 is not None else 0, h, kw1)
-        if film:
-            h16_next = self._film16(gn2, h, emb_all, emb_off, emb_bstride)
+        if film or drop is not None:
+            h16_next = self._film16(gn2, h, emb_all if film else None, emb_off, emb_bstride, drop)
         out = self._buf(tag + ".out", (B, H, W, co))
         pk2 = self._packed[id(rb.out_layers[3])]
         o16 = None
@@ -846,8 +925,9 @@ class UNetModel(nn.Module):
         under ("sfront", ...): the share count of the partials-only launch, 0 when the block is not routed."""
         B, H, W, C = x1shape
         if (self.cfg_shared_front is False or self._tape is not None or self.precision.npass != 1 or not isinstance(rb.skip_connection, nn.Identity) or
-                rb.out_channels != C or rb.use_scale_shift_norm):
-            # (a scale-shift-norm style block: the finish pass adds the style row onto h, which that block does not do)
+                rb.out_channels != C or rb.use_scale_shift_norm or self._drop_live(rb)):
+            # (a scale-shift-norm style block: the finish pass adds the style row onto h, which that block does not do; a block with live
+            #  dropout: the finish pass writes out_layers' planes without the mask)
             return False
         key = ("sfront", id(rb), 2 * B, H, W, self.cfg_shared_front)
         hit = self._consts.get(key)
@@ -1096,6 +1176,10 @@ class UNetModel(nn.Module):
         return style_all
 
     def _forward_impl(self, x, c_concat, timesteps, contexts, out, uniform_t=False):
+        if self._tape is None and self.dropout_live():
+            raise RuntimeError("UNetModel: dropout is live (train() with dropout > 0) and this is an inference entry point - call .eval() first; "
+                               "train-mode dropout runs through UNetTrainer only")
+        self._drop_used = {}
         self._prepare()
         self._cs = {}
         self._raw16 = {}
