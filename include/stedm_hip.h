@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 28
+#define STEDM_ABI_VERSION 29
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -170,6 +170,20 @@ int stedm_gn_apply16c_film(const float* x1, int c1, const float* cs1, int nslab1
 int stedm_gn_apply16c_x16(int c1, const float* cs1, int nslab1, const float* x2, int c2, const float* cs2, int nslab2, int x2_bmod,
                           const float* gamma, const float* beta, float eps, int groups, int act, int B, int HW,
                           void* out_hi, void* raw_hi, int mm_dtype, void* stream);
+/* The conv-less resampling layers of conv_resample=False (ABI 29; openaimodel.py:113-132 Upsample without its conv = F.interpolate(scale 2, nearest);
+ * :156-173 Downsample = AvgPool2d(2, 2)), also h_upd / x_upd of ResBlock(up / down) (:222-229). NHWC fp32, 16-byte aligned, C %% 4 == 0; the high-resolution
+ * side has even H and W (an odd one given to stedm_avgpool2x2 is an argument error). Both are producers of a tensor the next GroupNorm reads and leave its statistics in the format above when
+ * chan_stats != NULL: chan_stats [B][nslab][C][2] = {sum, sum of squares} of `out`, nslab = stedm_gn_chan_nslab(Hout * Wout) (any other value
+ * is an argument error). The slots: stedm_avgpool2x2 - runs of 256 output pixels; stedm_replicate2x2 - the four copies of a run of 64 input
+ * pixels (256 output pixels; the sums are four times those over the run, which is exact). No atomics, a fixed order of additions: bitwise
+ * reproducible. Nothing is allocated or synchronised.
+ * avgpool2x2: in [B][H][W][C] -> out [B][H/2][W/2][C], out = 0.25 * (((in00 + in01) + in10) + in11) in fp32.
+ * replicate2x2: in [B][H][W][C] -> out [B][2H][2W][C], out[b][2y+dy][2x+dx][c] (+)= scale * in[b][y][x][c]: scale 1, accumulate 0 is the
+ * nearest x2 (its backward is stedm_sum2x2); scale 0.25 is the backward of avgpool2x2, accumulate != 0 adding onto a gradient that is already
+ * there. chan_stats needs accumulate == 0 (the statistics are those of scale * in). */
+int stedm_avgpool2x2(const float* in, float* out, int B, int H, int W, int C, float* chan_stats, int nslab, void* stream);
+int stedm_replicate2x2(const float* in, float* out, int B, int H, int W, int C, float scale, int accumulate, float* chan_stats, int nslab,
+                       void* stream);
 int stedm_gn_stats(const float* x1, int c1, const float* x2, int c2, int x2_bmod, int groups, int B, int HW,
                    double* stats, void* stream);
 int stedm_gn_apply16(const float* x1, int c1, const float* x2, int c2, int x2_bmod, const float* gamma,

@@ -1642,6 +1642,36 @@ def sum2x2(x: torch.Tensor, out: torch.Tensor, accumulate: bool) -> None:
     check(lib().stedm_sum2x2(x.data_ptr(), out.data_ptr(), B, H, W, Cc, int(accumulate), _stream()), "stedm_sum2x2")
 
 
+def _resample_cs(out: torch.Tensor, chan_stats: Optional[torch.Tensor]) -> int:
+    """slot count of the statistics avgpool2x2 / replicate2x2 leave for `out`: gn_chan_nslab of its pixels (include/stedm_hip.h)"""
+    if chan_stats is None:
+        return 0
+    B, Ho, Wo, Cc = out.shape
+    assert chan_stats.dtype == torch.float32 and chan_stats.is_contiguous() and tuple(chan_stats.shape) == (B, gn_chan_nslab(Ho * Wo), Cc, 2), \
+        f"chan_stats must be [B][gn_chan_nslab(Hout * Wout)][C][2] fp32, got {tuple(chan_stats.shape)}"
+    return chan_stats.shape[1]
+
+
+def avgpool2x2(x: torch.Tensor, out: torch.Tensor, chan_stats: Optional[torch.Tensor] = None) -> None:
+    """out [B][H/2][W/2][C] = 2 x 2 average pool of x [B][H][W][C] (the conv-less Downsample); chan_stats: also the channel statistics of out"""
+    _chk(x, name="x")
+    _chk(out, name="out")
+    B, H, W, Cc = x.shape
+    assert tuple(out.shape) == (B, H // 2, W // 2, Cc)      # (an odd H or W is the library's argument error)
+    check(lib().stedm_avgpool2x2(x.data_ptr(), out.data_ptr(), B, H, W, Cc, _ptr(chan_stats), _resample_cs(out, chan_stats), _stream()),
+          "stedm_avgpool2x2")
+
+
+def replicate2x2(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0, accumulate: bool = False, chan_stats: Optional[torch.Tensor] = None) -> None:
+    """out [B][2H][2W][C] (+)= scale * x [B][H][W][C] at all four positions: the conv-less Upsample (scale 1), the backward of avgpool2x2 (0.25)"""
+    _chk(x, name="x")
+    _chk(out, name="out")
+    B, H, W, Cc = x.shape
+    assert tuple(out.shape) == (B, 2 * H, 2 * W, Cc)
+    check(lib().stedm_replicate2x2(x.data_ptr(), out.data_ptr(), B, H, W, Cc, float(scale), int(accumulate), _ptr(chan_stats),
+                                   _resample_cs(out, chan_stats), _stream()), "stedm_replicate2x2")
+
+
 def zero_insert16(x: torch.Tensor, hi: torch.Tensor, lo: Optional[torch.Tensor], prec: Precision) -> None:
     B, Ho, Wo, Cc = x.shape
     assert tuple(hi.shape) == (B, 2 * Ho, 2 * Wo, Cc)

@@ -711,6 +711,10 @@ class UNetTrainer:
         B, H, W, Cc = hin.shape
         dout, have = self._grad_of(out)
         assert have
+        if not layer.use_conv:      # the bare nearest x2 (conv_resample=False): no parameters, the gradient is the 2 x 2 block sum
+            g, acc = self._grad_of(hin)
+            ops.sum2x2(dout, g, acc)
+            return
         dout16 = self._bias_grad(dout, layer.conv.bias, cast="dy")
         src16 = self._cast16(hin, kind="x16")
         if self.direct_wgrad and self.bprec.npass == 1 and ops.wgrad3x3_plan(B, 2 * H, 2 * W, Cc, out.shape[-1]) > 0:
@@ -730,6 +734,10 @@ class UNetTrainer:
         co = out.shape[-1]
         dout, have = self._grad_of(out)
         assert have
+        if not layer.use_conv:      # the 2 x 2 average pool (conv_resample=False): no parameters, a quarter of the gradient to each of the four
+            g, acc = self._grad_of(hin)
+            ops.replicate2x2(dout, g, 0.25, acc)
+            return
         dout16 = self._bias_grad(dout, layer.op.bias, cast="dy")
         src16 = self._cast16(hin, kind="x16")
         self._wgrad(src16, dout16, dout, layer.op.weight, 3, 2)

@@ -50,25 +50,34 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
 
 
 class Upsample(nn.Module):
-    """openaimodel.py:104-132: nearest x2 then 3x3 conv (fused: the conv's patch loader reads src//2)."""
+    """openaimodel.py:104-132: nearest x2 then 3x3 conv (fused: the conv's patch loader reads src//2). use_conv=False (conv_resample=False):
+    the bare nearest x2, no parameters (stedm_replicate2x2)."""
 
     def __init__(self, channels, use_conv, dims=2, out_channels=None, padding=1):
         super().__init__()
-        assert dims == 2 and use_conv, "only the conv_resample=True 2-D form is implemented (shipped configs)"
+        assert dims == 2, "only the 2-D form is implemented (shipped configs)"
         self.channels = channels
         self.out_channels = out_channels or channels
-        self.conv = nn.Conv2d(self.channels, self.out_channels, 3, padding=padding)
+        self.use_conv = bool(use_conv)
+        if self.use_conv:
+            self.conv = nn.Conv2d(self.channels, self.out_channels, 3, padding=padding)
 
 
 class Downsample(nn.Module):
-    """openaimodel.py:147-173: 3x3 stride-2 pad-1 conv."""
+    """openaimodel.py:147-173: 3x3 stride-2 pad-1 conv. use_conv=False (conv_resample=False): the 2 x 2 average pool, no parameters
+    (stedm_avgpool2x2)."""
 
     def __init__(self, channels, use_conv, dims=2, out_channels=None, padding=1):
         super().__init__()
-        assert dims == 2 and use_conv, "only the conv_resample=True 2-D form is implemented (shipped configs)"
+        assert dims == 2, "only the 2-D form is implemented (shipped configs)"
         self.channels = channels
         self.out_channels = out_channels or channels
-        self.op = nn.Conv2d(self.channels, self.out_channels, 3, stride=2, padding=padding)
+        self.use_conv = bool(use_conv)
+        if self.use_conv:
+            self.op = nn.Conv2d(self.channels, self.out_channels, 3, stride=2, padding=padding)
+        else:
+            assert self.channels == self.out_channels      # openaimodel.py:162
+            self.op = nn.AvgPool2d(kernel_size=2, stride=2)
 
 
 class ResBlock(TimestepBlock):
@@ -146,8 +155,8 @@ class UNetModel(nn.Module):
             assert use_spatial_transformer, "context_dim is only meaningful with use_spatial_transformer=True"
             if not isinstance(context_dim, int):
                 context_dim = list(context_dim)
-        if num_classes is not None or n_embed is not None or resblock_updown or not conv_resample or dims != 2:
-            raise NotImplementedError("num_classes / n_embed / resblock_updown / conv_resample=False / dims != 2: "
+        if num_classes is not None or n_embed is not None or resblock_updown or dims != 2:
+            raise NotImplementedError("num_classes / n_embed / resblock_updown / dims != 2: "
                                       "not used by the reference configs, not implemented")
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout must be in [0, 1), got {dropout}")
@@ -451,6 +460,8 @@ class UNetModel(nn.Module):
                 pack(m.out_layers[3])
                 if not isinstance(m.skip_connection, nn.Identity):
                     pack(m.skip_connection)
+            elif isinstance(m, (Downsample, Upsample)) and not m.use_conv:
+                pass          # conv_resample=False: the pool and the nearest x2 have no weights
             elif isinstance(m, Downsample):
                 pack(m.op)
                 if prec.npass == 1 and m.op.in_channels % 8 == 0:
@@ -1002,12 +1013,16 @@ class UNetModel(nn.Module):
         return out
 
     def _down(self, ltag: str, layer: Downsample, h):
-        """Downsample.forward openaimodel.py:165-167: the stride-2 3x3 convolution."""
-        pk = self._packed[id(layer.op)]
+        """Downsample.forward openaimodel.py:165-167: the stride-2 3x3 convolution, or (conv_resample=False) the 2 x 2 average pool."""
         B, H, W, _ = h.shape
         out = self._buf(ltag + ".out", (B, H // 2, W // 2, layer.out_channels))
         if self._tape is not None:
             self._tape.append(("down", layer, h, out))
+        if not layer.use_conv:
+            # one pass: the pooled tensor and its channel statistics (the next ResBlock's GroupNorm and a decoder concat GroupNorm read them)
+            ops.avgpool2x2(h, out, self._cs_new(out))
+            return out
+        pk = self._packed[id(layer.op)]
         ps2 = self._packed.get((id(layer.op), "s2d"))
         if H % 2 == 0 and W % 2 == 0 and not ops.conv3x3_tiles_ok(H // 2, W // 2):
             # an output grid the tiled kernels cannot tile (latent widths that are not powers of two): im2col + flat GEMM (ops.conv_igemm)
@@ -1031,12 +1046,16 @@ class UNetModel(nn.Module):
 
     def _up(self, ltag: str, layer: Upsample, h, nxt, cat_ok, next_skip_c):
         """Upsample.forward openaimodel.py:124-132: nearest x2 + 3x3 convolution. cat_ok / next_skip_c as in _run_block: as the block's last layer
-        (nxt is None) it may write its output as 16-bit values into the next block's concat plane."""
-        pk = self._packed[id(layer.conv)]
+        (nxt is None) it may write its output as 16-bit values into the next block's concat plane. conv_resample=False: the bare nearest x2 -
+        an fp32 tensor and its statistics in every mode (the next block's concat GroupNorm reads both)."""
         B, H, W, _ = h.shape
         out = self._buf(ltag + ".out", (B, H * 2, W * 2, layer.out_channels))
         if self._tape is not None:
             self._tape.append(("up", layer, h, out))
+        if not layer.use_conv:
+            ops.replicate2x2(h, out, 1.0, False, self._cs_new(out))
+            return out
+        pk = self._packed[id(layer.conv)]
         pu = self._packed[(id(layer.conv), "up")]
         src16 = self._raw16.get(h.data_ptr()) or self._norm16(None, 0, h)
         if not ops.conv3x3_tiles_ok(H, W):
@@ -1094,7 +1113,7 @@ class UNetModel(nn.Module):
                 if cat_ok and nxt is None and ops.gn_apply16c_x16_ok(layer.out_channels, next_skip_c):
                     ncat = layer.out_channels + next_skip_c
                 h = self._res(ltag, layer, h, skip, emb_all, self._emb_off[id(layer)], emb_bstride, x2_bmod=skip_bmod,
-                              want16=isinstance(nxt, Upsample), next_cat=ncat, next_norm=self._first_norm(nxt if nxt is not None else next_layer))
+                              want16=isinstance(nxt, Upsample) and nxt.use_conv, next_cat=ncat, next_norm=self._first_norm(nxt if nxt is not None else next_layer))
                 if self._tape is not None:
                     self._tape.append(("res", layer, x1, skip, self._last_h, h, self._emb_off[id(layer)]))
                 skip = None
