@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 29
+#define STEDM_ABI_VERSION 30
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -184,6 +184,23 @@ int stedm_gn_apply16c_x16(int c1, const float* cs1, int nslab1, const float* x2,
 int stedm_avgpool2x2(const float* in, float* out, int B, int H, int W, int C, float* chan_stats, int nslab, void* stream);
 int stedm_replicate2x2(const float* in, float* out, int B, int H, int W, int C, float scale, int accumulate, float* chan_stats, int nslab,
                        void* stream);
+/* The front of ResBlock(up / down) (ABI 30; openaimodel.py:268-275: h = h_upd(in_layers[:-1](x)), x = x_upd(x)): GroupNorm + activation + 2x2 resample
+ * into the 16-bit operand planes of in_layers[-1], and the resampled raw input, from ONE read of x [B][H][W][C] (NHWC fp32). cs / nslab: the
+ * producer-side statistics of x in the chan_stats format above, folded as stedm_gn_apply16c folds them. Per source element, in fp32:
+ * u = (x - mean) * (rstd * gamma) + beta, a = act(u) - the order and the functions of stedm_gn_apply16c's 8-wide kernel, so a carries the bits
+ * that pass forms before its rounding.
+ * mode 1 (pool): out_hi / out_lo [B][H/2][W/2][C] = split16(0.25 * (((a00 + a01) + a10) + a11)); xr [B][H/2][W/2][C] the same expression on raw
+ *   x (bit-equal to stedm_avgpool2x2). H and W even.
+ * mode 2 (nearest): a is split once and stored at the four positions (2y + dy, 2x + dx) of out_hi / out_lo [B][2H][2W][C]; xr [B][2H][2W][C]
+ *   = x at those positions (bit-equal to stedm_replicate2x2, scale 1).
+ * out_lo NULL: single-product modes. xr and mean_rstd ([B][groups][2] = {mean, rstd}, as stedm_gn_apply16c_mr) are optional. xr gets no
+ * statistics (nothing normalises it). C % 8 == 0, C <= 4096, groups <= 64; x, the planes and xr 16-byte aligned; anything else is an
+ * argument error. 16-byte accesses, no atomics, bitwise reproducible, nothing allocated or synchronised. The f16 planes go through the fp16
+ * operand range guard at the site of the normalised planes (STEDM_F16G_NORM), switched on the affine as in stedm_gn_apply16c: an average of
+ * four in-range values stays in range. */
+int stedm_gn_apply16c_resample(const float* x, int C, const float* cs, int nslab, const float* gamma, const float* beta, float eps, int groups,
+                               int act, int B, int H, int W, int mode, void* out_hi, void* out_lo, float* xr, float* mean_rstd, int mm_dtype,
+                               void* stream);
 int stedm_gn_stats(const float* x1, int c1, const float* x2, int c2, int x2_bmod, int groups, int B, int HW,
                    double* stats, void* stream);
 int stedm_gn_apply16(const float* x1, int c1, const float* x2, int c2, int x2_bmod, const float* gamma,

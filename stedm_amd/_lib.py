@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 STREAM_POSTERIOR = 0x40000          # STEDM_STREAM_POSTERIOR: the stedm_philox_normal stream of the KL posterior's draw (stedm_gauss_sample)
@@ -164,6 +164,7 @@ SIGNATURES = {
     "stedm_zero_insert16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "stedm_avgpool2x2": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "stedm_replicate2x2": (_I, [_P, _P, _I, _I, _I, _I, _F, _I, _P, _I, _P]),
+    "stedm_gn_apply16c_resample": (_I, [_P, _I, _P, _I, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
     "stedm_attn_legacy_bwd_ws_floats": (C.c_long, [_I, _I, _I]),
     "stedm_attn_legacy_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "stedm_gemm_f32": (_I, [_P, C.c_long, _I, _P, C.c_long, _I, _P, C.c_long, _I, _I, _I, _F, _F, _P, C.c_long, _P]),

@@ -1672,6 +1672,31 @@ def replicate2x2(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0, accumul
                                    _resample_cs(out, chan_stats), _stream()), "stedm_replicate2x2")
 
 
+def gn_apply16c_resample(x: torch.Tensor, cs: torch.Tensor, out_hi: torch.Tensor, out_lo: Optional[torch.Tensor], prec: Precision, gamma: torch.Tensor,
+                         beta: torch.Tensor, mode: int, eps: float = 1e-5, groups: int = 32, act: int = 0, xr: Optional[torch.Tensor] = None,
+                         mean_rstd: Optional[torch.Tensor] = None) -> None:
+    """The front of ResBlock(up / down) (stedm_gn_apply16c_resample): act(GroupNorm(x)) of x [B][H][W][C] from its channel partials `cs`,
+    resampled into the 16-bit planes out_hi (/ out_lo) at the new resolution - mode 1: 2 x 2 average pool, [B][H/2][W/2][C]; mode 2: nearest
+    x2, [B][2H][2W][C] - and, with xr, the same resampling of raw x (fp32; = avgpool2x2 / replicate2x2 at scale 1). mean_rstd as gn_apply16c."""
+    _chk(x, name="x")
+    assert mode in (1, 2), "mode: 1 (pool) or 2 (nearest)"
+    B, H, W, Cc = x.shape
+    new = (B, H // 2, W // 2, Cc) if mode == 1 else (B, 2 * H, 2 * W, Cc)      # (an odd H or W in mode 1, C % 8 != 0: the library's argument errors)
+    assert cs.dtype == torch.float32 and cs.is_contiguous() and cs.dim() == 4 and cs.shape[0] == B and tuple(cs.shape[2:]) == (Cc, 2), \
+        f"cs must be [B][nslab][C][2] fp32, got {tuple(cs.shape)}"
+    assert gamma.numel() == Cc and beta.numel() == Cc and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+    for pl in (out_hi, out_lo):
+        assert pl is None or (pl.element_size() == 2 and pl.is_contiguous() and tuple(pl.shape) == new), f"planes must be 16-bit {new}"
+    if xr is not None:
+        _chk(xr, name="xr")
+        assert tuple(xr.shape) == new
+    if mean_rstd is not None:
+        assert mean_rstd.dtype == torch.float32 and mean_rstd.is_contiguous() and tuple(mean_rstd.shape) == (B, groups, 2)
+    check(lib().stedm_gn_apply16c_resample(x.data_ptr(), Cc, cs.data_ptr(), cs.shape[1], gamma.data_ptr(), beta.data_ptr(), float(eps), groups, act,
+                                           B, H, W, int(mode), out_hi.data_ptr(), _ptr(out_lo), _ptr(xr), _ptr(mean_rstd), prec.mm_dtype, _stream()),
+          "stedm_gn_apply16c_resample")
+
+
 def zero_insert16(x: torch.Tensor, hi: torch.Tensor, lo: Optional[torch.Tensor], prec: Precision) -> None:
     B, Ho, Wo, Cc = x.shape
     assert tuple(hi.shape) == (B, 2 * Ho, 2 * Wo, Cc)

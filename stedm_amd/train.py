@@ -137,6 +137,18 @@ class UNetTrainer:
                         norm.eps, norm.num_groups, act)
         return hi, lo
 
+    def _updown16(self, rb: ResBlock, x1):
+        """_norm16 for in_layers[0] of an up / down block: the resampled SiLU(GroupNorm(x1)) planes at the block's new resolution (the operand
+        of in_layers[2]'s weight gradient), kept by the forward or recomputed by the same pass (stedm_gn_apply16c_resample)"""
+        m, norm = self.m, rb.in_layers[0]
+        kept = m._saved16.get((id(norm), x1.data_ptr()))
+        if kept is not None and self.bprec.npass == 1:
+            return kept
+        B, H, W, C = x1.shape
+        hi, lo = self._planes("a16", (B, 2 * H, 2 * W, C) if rb.up else (B, H // 2, W // 2, C))
+        ops.gn_apply16c_resample(x1, m._chan_stats(x1), hi, lo, self.bprec, norm.weight, norm.bias, 2 if rb.up else 1, norm.eps, norm.num_groups, 1)
+        return hi, lo
+
     def _film16(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int, drop=None):
         """_norm16 for out_layers[0] of a scale-shift-norm block: SiLU(GroupNorm(h) * (1 + scale) + shift) in the backward's operand format.
         drop: the forward's dropout arguments of a live block (film may then be None) - the recomputed planes carry the forward's mask,
@@ -602,10 +614,21 @@ class UNetTrainer:
         B, H, W, _ = dh.shape
         conv1 = rb.in_layers[2]
         # conv1 and the first GroupNorm + SiLU over the (virtual concat) input
-        a16 = self._norm16(rb.in_layers[0], 1, x1, x2)
+        a16 = self._updown16(rb, x1) if rb.updown else self._norm16(rb.in_layers[0], 1, x1, x2)
         self._wgrad(a16, dh16, dh, conv1.weight, 3, 0)
         dA1 = self._buf(f"dA1.{B}x{H}x{W}x{cin}", (B, H, W, cin))
         self._dgrad(conv1, dh16, dA1)
+        if rb.updown:
+            # h_upd / x_upd (openaimodel.py:268-275) have no parameters: both gradients - dA1 into in_layers' activation and `add` = dout into
+            # the resampled input - go back to the input resolution: a quarter to each of the four (pool), the 2 x 2 block sum (nearest x2)
+            dA1s = self._buf(f"dA1s.{tuple(x1.shape)}", tuple(x1.shape))
+            adds = self._buf(f"adds.{tuple(x1.shape)}", tuple(x1.shape))
+            for src, dst in ((dA1, dA1s), (add, adds)):
+                if rb.up:
+                    ops.sum2x2(src, dst, False)
+                else:
+                    ops.replicate2x2(src, dst, 0.25, False)
+            dA1, add = dA1s, adds
         self._gn_bwd(rb.in_layers[0], 1, x1, x2, dA1, add)
 
     def _attn_bwd(self, ab: AttentionBlock, x, qkv, a, out):

@@ -81,16 +81,21 @@ class Downsample(nn.Module):
 
 
 class ResBlock(TimestepBlock):
-    """openaimodel.py:176-288 without up / down. use_scale_shift_norm (:199, :280-284): emb_layers emits 2 * out_channels values and the block
+    """openaimodel.py:176-288. up / down (:220-229, resblock_updown): both branches are resampled without parameters - h_upd = x_upd = the
+    conv-less Upsample / Downsample, up wins when both are set - between in_layers' SiLU and its convolution (:268-275); one pass writes the
+    resampled activation planes and the resampled input (stedm_gn_apply16c_resample). use_scale_shift_norm (:199, :280-284): emb_layers emits 2 * out_channels values and the block
     computes h = out_norm(h) * (1 + scale) + shift in place of h + emb_out (AdaGN / FiLM). dropout (:241): out_layers[2], live in train();
     drop_site is the block's ordinal in execution order over all ResBlocks of its UNetModel (the mask stream's site, include/stedm_hip.h)."""
 
     def __init__(self, channels, emb_channels, dropout, out_channels=None, use_conv=False, use_scale_shift_norm=False,
                  dims=2, use_checkpoint=False, up=False, down=False):
         super().__init__()
-        if up or down or dims != 2 or use_conv:
-            raise NotImplementedError("ResBlock: up / down / use_conv / dims != 2 are not "
+        if dims != 2 or use_conv:
+            raise NotImplementedError("ResBlock: use_conv / dims != 2 are not "
                                       "exercised by the reference configs and are not implemented in the HIP path")
+        if (up or down) and (out_channels or channels) != channels:
+            raise NotImplementedError("ResBlock(up / down) with out_channels != channels: UNetModel never builds one, and the 1x1 skip_connection "
+                                      "would need raw 16-bit planes of the resampled input")
         self.channels = channels
         self.emb_channels = emb_channels
         self.dropout = dropout
@@ -98,6 +103,15 @@ class ResBlock(TimestepBlock):
         self.out_channels = out_channels or channels
         self.use_scale_shift_norm = bool(use_scale_shift_norm)
         self.in_layers = nn.Sequential(GroupNorm32(32, channels), nn.SiLU(), nn.Conv2d(channels, self.out_channels, 3, padding=1))
+        self.up = bool(up)
+        self.down = bool(down) and not self.up       # openaimodel.py:222-229: `if up ... elif down`
+        self.updown = self.up or self.down
+        if self.up:
+            self.h_upd = Upsample(channels, False, dims)
+            self.x_upd = Upsample(channels, False, dims)
+        elif self.down:
+            self.h_upd = Downsample(channels, False, dims)
+            self.x_upd = Downsample(channels, False, dims)
         self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_channels, 2 * self.out_channels if use_scale_shift_norm else self.out_channels))
         self.out_layers = nn.Sequential(GroupNorm32(32, self.out_channels), nn.SiLU(), nn.Dropout(p=dropout),
                                         zero_module(nn.Conv2d(self.out_channels, self.out_channels, 3, padding=1)))
@@ -155,9 +169,15 @@ class UNetModel(nn.Module):
             assert use_spatial_transformer, "context_dim is only meaningful with use_spatial_transformer=True"
             if not isinstance(context_dim, int):
                 context_dim = list(context_dim)
-        if num_classes is not None or n_embed is not None or resblock_updown or dims != 2:
-            raise NotImplementedError("num_classes / n_embed / resblock_updown / dims != 2: "
+        if num_classes is not None or n_embed is not None or dims != 2:
+            raise NotImplementedError("num_classes / n_embed / dims != 2: "
                                       "not used by the reference configs, not implemented")
+        if resblock_updown and not conv_resample:
+            raise NotImplementedError("resblock_updown=True with conv_resample=False: the reference ignores conv_resample there (a no-op), but the "
+                                      "combination stays refused until the follow-up that lifts it together with the dropout one (DESIGN.md 4.6)")
+        if resblock_updown and float(dropout) > 0:
+            raise NotImplementedError("resblock_updown=True with dropout > 0: the up / down blocks would take the ordinary drop pass, but the "
+                                      "combination stays refused until the follow-up that lifts it together with conv_resample=False (DESIGN.md 4.6)")
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError(f"dropout must be in [0, 1), got {dropout}")
         if num_heads_upsample == -1:
@@ -176,6 +196,7 @@ class UNetModel(nn.Module):
         self.dropout = dropout
         self.channel_mult = channel_mult
         self.conv_resample = conv_resample
+        self.resblock_updown = bool(resblock_updown)
         self.num_classes = num_classes
         self.use_checkpoint = use_checkpoint
         self.dtype = torch.float32
@@ -203,7 +224,9 @@ class UNetModel(nn.Module):
                 ch = mult * model_channels
                 input_block_chans.append(ch)
             if level != len(channel_mult) - 1:
-                self.input_blocks.append(TimestepEmbedSequential(Downsample(ch, conv_resample, out_channels=ch)))
+                self.input_blocks.append(TimestepEmbedSequential(
+                    ResBlock(ch, ted, dropout, out_channels=ch, use_scale_shift_norm=ssn, down=True) if resblock_updown
+                    else Downsample(ch, conv_resample, out_channels=ch)))
                 input_block_chans.append(ch)
                 ds *= 2
         if num_head_channels != -1:
@@ -230,7 +253,8 @@ class UNetModel(nn.Module):
                 if ds in attention_resolutions:
                     raise TypeError("reference output block with ds in attention_resolutions is not runnable (openaimodel.py:689-698)")
                 if level and i == num_res_blocks:
-                    layers.append(Upsample(ch, conv_resample, out_channels=ch))
+                    layers.append(ResBlock(ch, ted, dropout, out_channels=ch, use_scale_shift_norm=ssn, up=True) if resblock_updown
+                                  else Upsample(ch, conv_resample, out_channels=ch))
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
         self.out = nn.Sequential(GroupNorm32(32, ch), nn.SiLU(), zero_module(nn.Conv2d(model_channels, out_channels, 3, padding=1)))
@@ -597,6 +621,30 @@ class UNetModel(nn.Module):
                         norm.weight, norm.bias, norm.eps, norm.num_groups, act, x2_bmod, raw, mean_rstd=mr)
         return ((hi, lo), raw) if want_raw else (hi, lo)
 
+    def _updown16(self, rb: "ResBlock", x1):
+        """The front of an up / down ResBlock (openaimodel.py:268-275): SiLU(GroupNorm(x1)) resampled into 16-bit planes, and x1 resampled the
+        same way (the block's residual), both at the new resolution, from one read of x1 (ops.gn_apply16c_resample). Training keeps the
+        planes and {mean, rstd} under the keys _norm16 uses."""
+        norm = rb.in_layers[0]
+        B, H, W, C = x1.shape
+        Hn, Wn = (2 * H, 2 * W) if rb.up else (H // 2, W // 2)
+        keep = self._tape is not None and self.precision.npass == 1 and self.precision.mm_dtype == BF16
+        if keep:
+            self._plane_ctr += 1
+            hi, lo = self._planes(B, Hn, Wn, C, f"keep{self._plane_ctr}.a16")
+            self._saved16[(id(norm), x1.data_ptr())] = (hi, lo)
+        else:
+            hi, lo = self._planes(B, Hn, Wn, C)
+        mr = None
+        if self._tape is not None:
+            self._mr_ctr += 1
+            mr = self._buf(f"keep{self._mr_ctr}.mr", (B, norm.num_groups, 2))
+            self._saved_mr[(id(norm), x1.data_ptr())] = mr
+        xr = self._buf(f"xr.{B}x{Hn}x{Wn}x{C}", (B, Hn, Wn, C))
+        ops.gn_apply16c_resample(x1, self._chan_stats(x1), hi, lo, self.precision, norm.weight, norm.bias, 2 if rb.up else 1, norm.eps,
+                                 norm.num_groups, 1, xr=xr, mean_rstd=mr)
+        return (hi, lo), xr
+
     def _film16(self, norm: nn.GroupNorm, h, film, film_off, film_bstride, drop=None):
         """SiLU(GroupNorm(h) * (1 + scale) + shift) as 16-bit planes, scale | shift = columns [film_off, film_off + 2 C) of sample b's row of
         `film` (row stride film_bstride; 0: one shared row). Training keeps the planes and {mean, rstd} exactly as _norm16 / _res do.
@@ -652,14 +700,20 @@ class UNetModel(nn.Module):
         B, H, W, _ = x1.shape
         co = rb.out_channels
         pk = self._packed[id(rb.in_layers[2])]
+        has_skip = not isinstance(rb.skip_connection, nn.Identity)
+        xres = x1                      # the residual of a block without a skip_connection convolution
+        if rb.updown:
+            # openaimodel.py:268-275: one pass leaves in_layers' activation planes and the input at the NEW resolution, which is H, W from here on
+            assert x2 is None and not has_skip
+            a16, xres = self._updown16(rb, x1)
+            H, W = xres.shape[1], xres.shape[2]
         # training keeps every block's intermediate (the backward pass reads it); inference shares one buffer per shape
         h = self._buf(tag + ".h" if self._tape is not None else f"h.{B}x{H}x{W}x{co}", (B, H, W, co))
         self._last_h = h
-        has_skip = not isinstance(rb.skip_connection, nn.Identity)
         h16_next = gn_next = None
         if has_skip:
             a16, x16 = self._norm16(rb.in_layers[0], 1, x1, x2, x2_bmod, want_raw=True)
-        else:
+        elif not rb.updown:
             a16 = self._norm16(rb.in_layers[0], 1, x1, x2, x2_bmod)
         ws = self._splitk_ws_res(B * H * W * co)
         # out_layers' GroupNorm + SiLU of h rides on this call (inference, single product): where the convolution splits K, the reduce pass
@@ -794,7 +848,7 @@ class UNetModel(nn.Module):
         h16 = h16_next if h16_next is not None else self._norm16(rb.out_layers[0], 1, h)
         if next_cat is not None and o16 is None:
             rawn = self._cat_plane(B, H, W, co, next_cat)
-            kwc = dict(prec=prec, src16=h16, bias=pk2.bias, res=x1, w_frag=pk2.frag, chan_stats=self._cs_new(out), ws=ws, w_frag16=pk2.frag16,
+            kwc = dict(prec=prec, src16=h16, bias=pk2.bias, res=xres, w_frag=pk2.frag, chan_stats=self._cs_new(out), ws=ws, w_frag16=pk2.frag16,
                        out16=(rawn, None), out16_stride=next_cat, cout=co)
             keyc = ("rescat", id(rb), B, H, W, next_cat)
             okc = self._consts.get(keyc)
@@ -805,7 +859,7 @@ class UNetModel(nn.Module):
                 ops.conv_igemm(None, pk2.hi, pk2.lo, None, **kwc)
                 self._x16[out.data_ptr()] = (rawn, co)
                 return out
-        ops.conv_igemm(None, pk2.hi, pk2.lo, out, prec=prec, src16=h16, bias=pk2.bias, res=x1, w_frag=pk2.frag,
+        ops.conv_igemm(None, pk2.hi, pk2.lo, out, prec=prec, src16=h16, bias=pk2.bias, res=xres, w_frag=pk2.frag,
                        chan_stats=self._cs_new(out), ws=ws, out16=o16, w_frag16=pk2.frag16, gn_next=gnn, coop=coop2)
         return filed()
 
@@ -1089,7 +1143,8 @@ class UNetModel(nn.Module):
         if isinstance(layer, ResBlockStyle):
             layer = layer.block
         if isinstance(layer, ResBlock):
-            return (layer.in_layers[0], 1) if isinstance(layer.skip_connection, nn.Identity) else None
+            # (an up / down block resamples between its GroupNorm and its convolution: no producer can write same-resolution planes for it)
+            return (layer.in_layers[0], 1) if isinstance(layer.skip_connection, nn.Identity) and not layer.updown else None
         if isinstance(layer, AttentionBlock):
             return (layer.norm, 0)
         return None
