@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STEDM_ABI_VERSION 30
+#define STEDM_ABI_VERSION 31
 
 #define STEDM_F16 0
 #define STEDM_BF16 1
@@ -426,6 +426,16 @@ int stedm_attn_legacy(const float* qkv, float* out, int B, int T, int heads, int
  * Also T = 64 n <= 4096 tokens with ch in {64, 128} and qkv_is16 = 1 (the middle block at 64x64 / 128x128 latents): 64-key tiles with
  * an online softmax around the same products. Any other shape returns an error (the caller uses stedm_attn_legacy). */
 int stedm_attn_legacy16(const void* qkv, int qkv_is16, void* out16, int B, int T, int heads, int ch, int mm_dtype, void* stream);
+/* Both orders of the qkv split (AttentionBlock's use_new_attention_order). The plane is [B][T][3 C], C = heads*ch, in either:
+ *   STEDM_ATTN_HEADS_FIRST (QKVAttentionLegacy, openaimodel.py:369-394): channel = h*3*ch + {q:0, k:ch, v:2ch} + c
+ *   STEDM_ATTN_QKV_FIRST   (QKVAttention, openaimodel.py:401-428):       channel = {q:0, k:C, v:2C} + h*ch + c
+ * out is [B][T][C] with channel h*ch + c in both; scale and softmax are the same. A (sample, head) problem is the same arithmetic at
+ * other addresses: no copy or repacking of the plane is made. stedm_attn_legacy / stedm_attn_legacy16 are the STEDM_ATTN_HEADS_FIRST
+ * calls of these two (same shapes covered, same kernels); any other order is an argument error. */
+#define STEDM_ATTN_HEADS_FIRST 0
+#define STEDM_ATTN_QKV_FIRST 1
+int stedm_attn_qkv(const float* qkv, float* out, int B, int T, int heads, int ch, int order, void* stream);
+int stedm_attn_qkv16(const void* qkv, int qkv_is16, void* out16, int B, int T, int heads, int ch, int mm_dtype, int order, void* stream);
 
 /* ---- DDIM update with rescaled classifier-free guidance ----------------------------------- */
 /* ddim.py:179-184 (CFG + std rescale over dims (C,H), unbiased) and :195-210 (x0 / dir / noise).
@@ -764,6 +774,9 @@ int stedm_geglu_bwd(const float* g, const float* dh, float* dg, long M, int I, v
  * stedm_attn_legacy_bwd_ws_floats(B, T, heads) floats (0 = none: both T x T matrices stay in LDS, T <= 128). */
 long stedm_attn_legacy_bwd_ws_floats(int B, int T, int heads);
 int stedm_attn_legacy_bwd(const float* qkv, const float* d_out, float* d_qkv, int B, int T, int heads, int ch, float* ws, void* stream);
+/* the same for either order of the qkv split (STEDM_ATTN_HEADS_FIRST / STEDM_ATTN_QKV_FIRST: qkv and d_qkv in that order); same workspace
+ * rule. stedm_attn_legacy_bwd is its STEDM_ATTN_HEADS_FIRST call. */
+int stedm_attn_qkv_bwd(const float* qkv, const float* d_out, float* d_qkv, int B, int T, int heads, int ch, int order, float* ws, void* stream);
 /* C = alpha op(A) op(B) + beta C (fp32; the embedding Linears' backward: rows = batch). ws (optional, ws_floats floats): partial
  * sums of the split-K form taken when the output is small and K long (fixed-order reduce). */
 int stedm_gemm_f32(const float* A, long lda, int trans_a, const float* B, long ldb, int trans_b, float* C, long ldc, int M,

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEDM_HIP_LIB") or os.path.join(_HERE, "libstedm_hip.so")     # STEDM_HIP_LIB: A/B timing of another build
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 F16, BF16 = 0, 1
 CONV_S1, CONV_DOWN, CONV_UP, CONV_UP_SUBPIXEL, CONV_S2D = 0, 1, 2, 3, 4
 STREAM_POSTERIOR = 0x40000          # STEDM_STREAM_POSTERIOR: the stedm_philox_normal stream of the KL posterior's draw (stedm_gauss_sample)
@@ -105,6 +105,8 @@ SIGNATURES = {
     "stedm_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "stedm_attn_legacy": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "stedm_attn_legacy16": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "stedm_attn_qkv": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "stedm_attn_qkv16": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "stedm_ddim_step": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I, _P]),
     "stedm_ddim_step_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _F, _I, _F, _F, C.c_long, C.c_ulonglong, _P, _P, _P, _P, _I, _I, _I, _I,
                                _P]),
@@ -167,6 +169,7 @@ SIGNATURES = {
     "stedm_gn_apply16c_resample": (_I, [_P, _I, _P, _I, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
     "stedm_attn_legacy_bwd_ws_floats": (C.c_long, [_I, _I, _I]),
     "stedm_attn_legacy_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "stedm_attn_qkv_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "stedm_gemm_f32": (_I, [_P, C.c_long, _I, _P, C.c_long, _I, _P, C.c_long, _I, _I, _I, _F, _F, _P, C.c_long, _P]),
     "stedm_silu": (_I, [_P, _P, _P, C.c_long, _I, _P]),
     "stedm_q_sample": (_I, [_P, _P, _P, _P, _P, _P, _I, C.c_long, _P]),

@@ -2,6 +2,9 @@
 // the [T][T] weights. qkv is [B][T][heads*3*ch] (token-major, the NHWC view of the reference's
 // [B][3C][T]) with channel = h*3*ch + {q:0, k:ch, v:2*ch} + c. Softmax runs in fp32 exactly as the
 // reference's `softmax(weight.float())`; q and k are each scaled by ch^-1/4 before the product.
+// QKVAttention (openaimodel.py:401-428, use_new_attention_order) is the same arithmetic on the other channel order of the plane,
+// {q:0, k:C, v:2C} + h*ch + c with C = heads*ch: every kernel of this unit takes the order as the template parameter ORD
+// (common.hpp: attn_head_off / attn_opnd_stride), and ORD = 0 compiles from the expressions it always had.
 //
 // v1: VALU fp32 (the U-Net's middle attention is 0.03 % of the forward's FLOPs at 32x32 latents);
 // one 256-thread block per (sample*head, 64-query tile); K/V tiles of 64 keys streamed through LDS.
@@ -14,6 +17,7 @@ using namespace stedm;
 
 constexpr int AT = 64;  // query rows per block == keys per tile
 
+template <int ORD>
 __global__ void __launch_bounds__(256) attn_legacy_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T,
                                                           int heads, int ch, float scale) {
   extern __shared__ __attribute__((aligned(16))) float smf[];
@@ -27,7 +31,8 @@ __global__ void __launch_bounds__(256) attn_legacy_kernel(const float* __restric
   const int bh = blockIdx.x, b = bh / heads, hd = bh % heads;
   const int q0 = blockIdx.y * AT;
   const int C3 = heads * 3 * ch, C = heads * ch;
-  const float* base = qkv + (long)b * T * C3 + hd * 3 * ch;
+  const int OS = attn_opnd_stride<ORD>(heads, ch);      // k / v rows at base + OS / + 2 OS
+  const float* base = qkv + (long)b * T * C3 + attn_head_off<ORD>(hd, ch);
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
   const int c4n = ch >> 2;
 
@@ -58,8 +63,8 @@ __global__ void __launch_bounds__(256) attn_legacy_kernel(const float* __restric
       float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
       if (k0 + row < T) {
         const float* pr = base + (long)(k0 + row) * C3 + c4 * 4;
-        kv = *reinterpret_cast<const float4*>(pr + ch);
-        vv = *reinterpret_cast<const float4*>(pr + 2 * ch);
+        kv = *reinterpret_cast<const float4*>(pr + OS);
+        vv = *reinterpret_cast<const float4*>(pr + 2 * OS);
         kv.x *= scale; kv.y *= scale; kv.z *= scale; kv.w *= scale;
       }
       *reinterpret_cast<float4*>(Ks + row * LD + c4 * 4) = kv;
@@ -158,18 +163,28 @@ __global__ void __launch_bounds__(256) attn_legacy_kernel(const float* __restric
   }
 }
 
-extern "C" int stedm_attn_legacy(const float* qkv, float* out, int B, int T, int heads, int ch, void* stream) {
-  STEDM_CHECK_ARG(qkv && out, "attn_legacy: null pointer");
-  STEDM_CHECK_ARG(B > 0 && T > 0 && heads > 0, "attn_legacy: bad sizes");
-  STEDM_CHECK_ARG(ch % 4 == 0 && ch >= 4 && ch <= 128, "attn_legacy: head width %d unsupported (need ch %% 4 == 0, ch <= 128)", ch);
+template <int ORD>
+static int attn_qkv_launch(const float* qkv, float* out, int B, int T, int heads, int ch, void* stream) {
   const size_t lds = ((size_t)3 * AT * (ch + 4) + (size_t)AT * (AT + 4)) * sizeof(float);
   if (lds > 64 * 1024)
-    STEDM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_legacy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    STEDM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_legacy_kernel<ORD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const float scale = 1.0f / sqrtf(sqrtf((float)ch));
   dim3 grid(B * heads, (T + AT - 1) / AT);
-  attn_legacy_kernel<<<grid, 256, lds, as_stream(stream)>>>(qkv, out, T, heads, ch, scale);
+  attn_legacy_kernel<ORD><<<grid, 256, lds, as_stream(stream)>>>(qkv, out, T, heads, ch, scale);
   STEDM_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int stedm_attn_qkv(const float* qkv, float* out, int B, int T, int heads, int ch, int order, void* stream) {
+  STEDM_CHECK_ARG(qkv && out, "attn_qkv: null pointer");
+  STEDM_CHECK_ARG(B > 0 && T > 0 && heads > 0, "attn_qkv: bad sizes");
+  STEDM_CHECK_ARG(ch % 4 == 0 && ch >= 4 && ch <= 128, "attn_qkv: head width %d unsupported (need ch %% 4 == 0, ch <= 128)", ch);
+  STEDM_CHECK_ARG(order == STEDM_ATTN_HEADS_FIRST || order == STEDM_ATTN_QKV_FIRST, "attn_qkv: order %d is neither STEDM_ATTN_HEADS_FIRST nor STEDM_ATTN_QKV_FIRST", order);
+  return order == STEDM_ATTN_QKV_FIRST ? attn_qkv_launch<1>(qkv, out, B, T, heads, ch, stream) : attn_qkv_launch<0>(qkv, out, B, T, heads, ch, stream);
+}
+
+extern "C" int stedm_attn_legacy(const float* qkv, float* out, int B, int T, int heads, int ch, void* stream) {
+  return stedm_attn_qkv(qkv, out, B, T, heads, ch, STEDM_ATTN_HEADS_FIRST, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -183,7 +198,7 @@ extern "C" int stedm_attn_legacy(const float* qkv, float* out, int B, int T, int
 #include "conv_common.hpp"
 
 // IN16: qkv arrives as the 16-bit plane the qkv convolution's epilogue wrote (same rounding as converting here, half the bytes).
-template <typename T, int CH, bool IN16>
+template <typename T, int CH, bool IN16, int ORD>
 __global__ void __launch_bounds__(256) attn64_mfma_kernel(const void* __restrict__ qkv_, T* __restrict__ out, int nprob, int heads, float scale2) {
   using V8 = typename MM<T>::V8;
   typedef T V4T __attribute__((ext_vector_type(4)));
@@ -192,7 +207,8 @@ __global__ void __launch_bounds__(256) attn64_mfma_kernel(const void* __restrict
   if (prob >= nprob) return;
   const int b = prob / heads, hd = prob % heads;
   const int C3 = heads * 3 * CH, C = heads * CH;
-  const long boff = (long)b * 64 * C3 + hd * 3 * CH;
+  const int OS = attn_opnd_stride<ORD>(heads, CH);      // k / v rows at + OS / + 2 OS (order 0: the constants CH, 2 CH)
+  const long boff = (long)b * 64 * C3 + attn_head_off<ORD>(hd, CH);
   const float* base = reinterpret_cast<const float*>(qkv_) + boff;
   const T* base16 = reinterpret_cast<const T*>(qkv_) + boff;
   const int r = lane & 31, h = lane >> 5;
@@ -216,7 +232,7 @@ __global__ void __launch_bounds__(256) attn64_mfma_kernel(const void* __restrict
   for (int s = 0; s < CH / 16; ++s) {
     V8 ka[2], qb[2];
 #pragma unroll
-    for (int it = 0; it < 2; ++it) ka[it] = frag8((long)(32 * it + r) * C3 + CH + 16 * s + 8 * h);
+    for (int it = 0; it < 2; ++it) ka[it] = frag8((long)(32 * it + r) * C3 + OS + 16 * s + 8 * h);
 #pragma unroll
     for (int jt = 0; jt < 2; ++jt) qb[jt] = frag8((long)(32 * jt + r) * C3 + 16 * s + 8 * h);
 #pragma unroll
@@ -269,7 +285,7 @@ __global__ void __launch_bounds__(256) attn64_mfma_kernel(const void* __restrict
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int key = (j & 3) + 8 * (2 * u + (j >> 2)) + 4 * h + 32 * it;
-          const long vo = (long)key * C3 + 2 * CH + 32 * dt + r;
+          const long vo = (long)key * C3 + 2 * OS + 32 * dt + r;
           va[j] = IN16 ? base16[vo] : (T)base[vo];
         }
 #pragma unroll
@@ -313,7 +329,7 @@ __global__ void __launch_bounds__(256) attn64_mfma_kernel(const void* __restrict
 static __device__ __attribute__((aligned(256))) unsigned char g_attn_zero[256];   // source of the zero extension (ch = 16)
 
 struct AttnFlashArgs {
-  const void* qkv;   // 16-bit plane [B][T][heads * 3 * ch], channel = head * 3 ch + {q: 0, k: ch, v: 2 ch} + c
+  const void* qkv;   // 16-bit plane [B][T][heads * 3 * ch], channel = head * 3 ch + {q: 0, k: ch, v: 2 ch} + c (ORD 0) or {q: 0, k: C, v: 2 C} + head * ch + c (ORD 1)
   void* out;         // 16-bit plane [B][T][heads * ch]
   int T, heads, nbh, nq;
   float c;           // logit scale x log2(e): p = exp2((s - m) c)
@@ -336,7 +352,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-template <typename T, int CH, int NW, int NBUF>
+template <typename T, int CH, int NW, int NBUF, int ORD>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn_flash_kernel(const AttnFlashArgs a) {
   using V8 = typename MM<T>::V8;
   typedef T V4T __attribute__((ext_vector_type(4)));
@@ -362,7 +378,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn_flash_kernel(co
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int C3 = a.heads * 3 * CH, C = a.heads * CH;
-  const T* base = reinterpret_cast<const T*>(a.qkv) + (long)b * a.T * C3 + hd * 3 * CH;
+  // the order enters `base` and the wave-uniform K / V tile pointers only: a head's rows keep their length and their pitch C3
+  const T* base = reinterpret_cast<const T*>(a.qkv) + (long)b * a.T * C3 + attn_head_off<ORD>(hd, CH);
   const int q0 = qtile * (NW * 32) + wave * 32;
   const bool live = q0 < a.T;                    // wave-uniform
   const int ntiles = (a.T + 63) >> 6;
@@ -387,7 +404,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn_flash_kernel(co
   auto issue = [&](int kt, const int which /* 1: K rows, 2: V rows */) __attribute__((always_inline)) {
     unsigned char* dst = ring + (which == 2 ? NBUF * STAGE : 0) + (kt % NBUF) * STAGE + wave * (NI * 1024);
     if (kt * 64 + 64 <= a.T) {
-      const unsigned char* tp = reinterpret_cast<const unsigned char*>(base + (long)kt * 64 * C3 + which * CH);
+      // (order 1: C3 = 3 C and OS = C, one product with the one live stride)
+      const unsigned char* tp = reinterpret_cast<const unsigned char*>(ORD ? base + (long)(kt * 192 + which) * C : base + (long)kt * 64 * C3 + which * CH);
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         if (dok[i]) GLDS16(tp + doff[i], dst + i * 1024);
@@ -398,7 +416,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn_flash_kernel(co
       for (int i = 0; i < NI; ++i) {              // last, partial tile: rows beyond T re-read row T - 1 (their logits are masked)
         const int n = wave * NI + i, row = 8 * (n >> 1) + drr;
         const int ch = 4 * (2 * (n & 1) + dsub) + (dpc ^ ((row >> 2) & 3));
-        const T* src = base + (long)min(kt * 64 + row, a.T - 1) * C3 + ch * 8 + which * CH;
+        const T* src = ORD ? base + (long)(min(kt * 64 + row, a.T - 1) * 3 + which) * C + ch * 8 : base + (long)min(kt * 64 + row, a.T - 1) * C3 + ch * 8 + which * CH;
         if (dok[i]) GLDS16(src, dst + i * 1024);
         else if (which == 1 && CH < DP) GLDS16(g_attn_zero + (lane & 15) * 16, dst + i * 1024);
       }
@@ -658,44 +676,41 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn_flash_kernel(co
     }
 }
 
-template <typename T, int NW, int NBUF>
+template <typename T, int NW, int NBUF, int ORD>
 static int attn_flash_launch(AttnFlashArgs a, int ch, hipStream_t st) {
   static_assert(NBUF == 2 || NBUF == 4, "ring depth");
   a.nq = (a.T + NW * 32 - 1) / (NW * 32);
   const int grid = a.nbh * a.nq;
-  if (ch == 128) attn_flash_kernel<T, 128, NW, NBUF><<<grid, NW * 64, 0, st>>>(a);
-  else if (ch == 64) attn_flash_kernel<T, 64, NW, NBUF><<<grid, NW * 64, 0, st>>>(a);
-  else if (ch == 32) attn_flash_kernel<T, 32, NW, NBUF><<<grid, NW * 64, 0, st>>>(a);
-  else attn_flash_kernel<T, 16, NW, NBUF><<<grid, NW * 64, 0, st>>>(a);
+  if (ch == 128) attn_flash_kernel<T, 128, NW, NBUF, ORD><<<grid, NW * 64, 0, st>>>(a);
+  else if (ch == 64) attn_flash_kernel<T, 64, NW, NBUF, ORD><<<grid, NW * 64, 0, st>>>(a);
+  else if (ch == 32) attn_flash_kernel<T, 32, NW, NBUF, ORD><<<grid, NW * 64, 0, st>>>(a);
+  else attn_flash_kernel<T, 16, NW, NBUF, ORD><<<grid, NW * 64, 0, st>>>(a);
   STEDM_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int stedm_attn_legacy16(const void* qkv, int qkv_is16, void* out16, int B, int T, int heads, int ch, int mm_dtype, void* stream) {
-  STEDM_CHECK_ARG(qkv && out16 && B > 0 && heads > 0, "attn_legacy16: bad args");
-  STEDM_CHECK_ARG(T > 0 && (ch == 128 || ch == 64 || ch == 32 || ch == 16) && ((T == 64 && ch != 16) || qkv_is16),
-                  "attn_legacy16: covers head widths 16 / 32 / 64 / 128 from the 16-bit qkv plane (any T) and T == 64 (ch >= 32) from fp32 rows (T=%d ch=%d is16=%d)", T, ch, qkv_is16);
-  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "attn_legacy16: bad mm_dtype");
+template <int ORD>
+static int attn_qkv16_launch(const void* qkv, int qkv_is16, void* out16, int B, int T, int heads, int ch, int mm_dtype, void* stream) {
   if (T != 64 || ch == 16) {
     hipStream_t s_ = as_stream(stream);
     AttnFlashArgs fa{qkv, out16, T, heads, B * heads, (T + 127) / 128, 1.4426950408889634f / sqrtf((float)ch)};
-    STEDM_CHECK_ARG((long)64 * heads * 3 * ch * 2 < (1l << 31), "attn_legacy16: row too wide");
+    STEDM_CHECK_ARG((long)64 * heads * 3 * ch * 2 < (1l << 31), "attn_qkv16: row too wide");
     // 256-query workgroups (one per CU, four-stage rings) for long sequences of 128-wide heads when they fill the chip (+2.5 % at T = 1024,
     // +3.5 % at 4096; slower at T = 256 and at ch = 64: profiles/r05_attn_flash.md); otherwise 128-query workgroups, two per CU
     static int cus = 0;
     if (cus == 0) { cus = stedm_device_cus(); if (cus <= 0) cus = 256; }
     static const int force = getenv("STEDM_ATTN_FORM") ? atoi(getenv("STEDM_ATTN_FORM")) : 0;      // A/B timing only: 4 / 8 waves
     const bool wide = force ? force == 8 : (T >= 1024 && ch == 128 && (long)B * heads * ((T + 255) / 256) >= cus);
-    if (wide) return mm_dtype == STEDM_F16 ? attn_flash_launch<_Float16, 8, 4>(fa, ch, s_) : attn_flash_launch<__bf16, 8, 4>(fa, ch, s_);
-    return mm_dtype == STEDM_F16 ? attn_flash_launch<_Float16, 4, 2>(fa, ch, s_) : attn_flash_launch<__bf16, 4, 2>(fa, ch, s_);
+    if (wide) return mm_dtype == STEDM_F16 ? attn_flash_launch<_Float16, 8, 4, ORD>(fa, ch, s_) : attn_flash_launch<__bf16, 8, 4, ORD>(fa, ch, s_);
+    return mm_dtype == STEDM_F16 ? attn_flash_launch<_Float16, 4, 2, ORD>(fa, ch, s_) : attn_flash_launch<__bf16, 4, 2, ORD>(fa, ch, s_);
   }
   const int nprob = B * heads, grid = (nprob + 3) / 4;
   const float scale2 = 1.0f / sqrtf((float)ch);
   hipStream_t st = as_stream(stream);
 #define LAUNCH_ATTN(TT, CHH)                                                                                         \
   {                                                                                                                 \
-    if (qkv_is16) attn64_mfma_kernel<TT, CHH, true><<<grid, 256, 0, st>>>(qkv, (TT*)out16, nprob, heads, scale2);    \
-    else attn64_mfma_kernel<TT, CHH, false><<<grid, 256, 0, st>>>(qkv, (TT*)out16, nprob, heads, scale2);           \
+    if (qkv_is16) attn64_mfma_kernel<TT, CHH, true, ORD><<<grid, 256, 0, st>>>(qkv, (TT*)out16, nprob, heads, scale2);    \
+    else attn64_mfma_kernel<TT, CHH, false, ORD><<<grid, 256, 0, st>>>(qkv, (TT*)out16, nprob, heads, scale2);           \
   }
   if (mm_dtype == STEDM_F16) {
     if (ch == 128) LAUNCH_ATTN(_Float16, 128) else if (ch == 64) LAUNCH_ATTN(_Float16, 64) else LAUNCH_ATTN(_Float16, 32)
@@ -705,4 +720,18 @@ extern "C" int stedm_attn_legacy16(const void* qkv, int qkv_is16, void* out16, i
 #undef LAUNCH_ATTN
   STEDM_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int stedm_attn_qkv16(const void* qkv, int qkv_is16, void* out16, int B, int T, int heads, int ch, int mm_dtype, int order, void* stream) {
+  STEDM_CHECK_ARG(qkv && out16 && B > 0 && heads > 0, "attn_qkv16: bad args");
+  STEDM_CHECK_ARG(T > 0 && (ch == 128 || ch == 64 || ch == 32 || ch == 16) && ((T == 64 && ch != 16) || qkv_is16),
+                  "attn_qkv16: covers head widths 16 / 32 / 64 / 128 from the 16-bit qkv plane (any T) and T == 64 (ch >= 32) from fp32 rows (T=%d ch=%d is16=%d)", T, ch, qkv_is16);
+  STEDM_CHECK_ARG(mm_dtype == STEDM_F16 || mm_dtype == STEDM_BF16, "attn_qkv16: bad mm_dtype");
+  STEDM_CHECK_ARG(order == STEDM_ATTN_HEADS_FIRST || order == STEDM_ATTN_QKV_FIRST, "attn_qkv16: order %d is neither STEDM_ATTN_HEADS_FIRST nor STEDM_ATTN_QKV_FIRST", order);
+  return order == STEDM_ATTN_QKV_FIRST ? attn_qkv16_launch<1>(qkv, qkv_is16, out16, B, T, heads, ch, mm_dtype, stream)
+                                       : attn_qkv16_launch<0>(qkv, qkv_is16, out16, B, T, heads, ch, mm_dtype, stream);
+}
+
+extern "C" int stedm_attn_legacy16(const void* qkv, int qkv_is16, void* out16, int B, int T, int heads, int ch, int mm_dtype, void* stream) {
+  return stedm_attn_qkv16(qkv, qkv_is16, out16, B, T, heads, ch, mm_dtype, STEDM_ATTN_HEADS_FIRST, stream);
 }

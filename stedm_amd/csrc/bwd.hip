@@ -625,6 +625,7 @@ __global__ void zero_insert16_kernel(const float* __restrict__ in, T* __restrict
 // ------------------------------------------------------------------------------------------------ attention backward
 // QKVAttentionLegacy (openaimodel.py:378-394) reversed; one block per (sample, head); P and dS live in LDS ([T][T] fp32 each), the
 // q / k / v / dO operands are staged through LDS 32 channels at a time ([T][33] images).
+template <int ORD>
 __global__ void __launch_bounds__(256) attn_legacy_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dO, float* __restrict__ dqkv, int T,
                                                               int heads, int ch) {
   extern __shared__ float sm[];
@@ -634,13 +635,14 @@ __global__ void __launch_bounds__(256) attn_legacy_bwd_kernel(const float* __res
   float* sq = st; float* sk = st + T * 33; float* sv = st + 2 * T * 33; float* sg = st + 3 * T * 33;
   const int b = blockIdx.x / heads, h = blockIdx.x % heads;
   const long ld = (long)heads * 3 * ch, ldo = (long)heads * ch;
-  const float* q = qkv + (long)b * T * ld + (long)h * 3 * ch;
-  const float* k = q + ch;
-  const float* v = q + 2 * ch;
+  const int os = attn_opnd_stride<ORD>(heads, ch);
+  const float* q = qkv + (long)b * T * ld + attn_head_off<ORD>((long)h, ch);
+  const float* k = q + os;
+  const float* v = q + 2 * os;
   const float* go = dO + (long)b * T * ldo + (long)h * ch;
-  float* dq = dqkv + (long)b * T * ld + (long)h * 3 * ch;
-  float* dk = dq + ch;
-  float* dv = dq + 2 * ch;
+  float* dq = dqkv + (long)b * T * ld + attn_head_off<ORD>((long)h, ch);
+  float* dk = dq + os;
+  float* dv = dq + 2 * os;
   const float s2 = 1.0f / sqrtf((float)ch);   // (ch^-1/4)^2: the scale sits on both q and k
   auto stage = [&](int c0) {
     for (int e = threadIdx.x; e < T * 32; e += 256) {
@@ -707,6 +709,7 @@ __global__ void __launch_bounds__(256) attn_legacy_bwd_kernel(const float* __res
 //            the B reads.
 typedef float att_f32x16 __attribute__((ext_vector_type(16)));
 constexpr int A64_PP = 68;
+template <int ORD>
 __global__ void __launch_bounds__(256) attn64_bwd_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ dO, float* __restrict__ dqkv,
                                                               int heads, int ch) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -721,11 +724,12 @@ __global__ void __launch_bounds__(256) attn64_bwd_mfma_kernel(const float* __res
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, r = l & 31, hh = l >> 5;
   const int b = blockIdx.x / heads, h = blockIdx.x % heads;
   const long ld = (long)heads * 3 * ch, ldo = (long)heads * ch;
-  const float* q = qkv + (long)b * 64 * ld + (long)h * 3 * ch;
-  const float* k = q + ch;
-  const float* v = q + 2 * ch;
+  const int os = attn_opnd_stride<ORD>(heads, ch);
+  const float* q = qkv + (long)b * 64 * ld + attn_head_off<ORD>((long)h, ch);
+  const float* k = q + os;
+  const float* v = q + 2 * os;
   const float* go = dO + (long)b * 64 * ldo + (long)h * ch;
-  float* dq = dqkv + (long)b * 64 * ld + (long)h * 3 * ch;
+  float* dq = dqkv + (long)b * 64 * ld + attn_head_off<ORD>((long)h, ch);
   const float s2 = 1.0f / sqrtf((float)ch);
   const int c4n = ch >> 2;
 #pragma unroll 2
@@ -806,7 +810,7 @@ __global__ void __launch_bounds__(256) attn64_bwd_mfma_kernel(const float* __res
   __syncthreads();
   const int nct = ch >> 5;
   for (int it = w; it < 3 * nct; it += 4) {
-    const int ct = it % nct, o = it / nct;           // o: 0 dV (column offset 2 ch), 1 dQ (0), 2 dK (ch)
+    const int ct = it % nct, o = it / nct;           // o: 0 dV (column offset 2 os), 1 dQ (0), 2 dK (os)
     // A element (m, kk): o = 0: P[kk][m]; 1: dS[m][kk]; 2: dS[kk][m]   ->   base[kk * ak + m * am]
     const float* abase = o == 0 ? sP : sD;
     const int ak = o == 1 ? 1 : A64_PP, am = o == 1 ? A64_PP : 1;
@@ -824,7 +828,7 @@ __global__ void __launch_bounds__(256) attn64_bwd_mfma_kernel(const float* __res
       acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[k0 * ak], bv, acc1, 0, 0, 0);
     }
     const float sc = o == 0 ? 1.0f : s2;
-    float* dst = dq + (o == 0 ? 2 * ch : (o == 1 ? 0 : ch)) + 32 * ct + r;
+    float* dst = dq + (o == 0 ? 2 * os : (o == 1 ? 0 : os)) + 32 * ct + r;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int row = (e & 3) + 8 * (e >> 2) + 4 * hh;
@@ -837,6 +841,7 @@ __global__ void __launch_bounds__(256) attn64_bwd_mfma_kernel(const float* __res
 // General-T form (T too large for both T x T matrices in LDS): two kernels over a global scratch [B*heads][2][T][T] (P, then dS).
 // A: grid (B*heads, ceil(T/QT)) — the QT query rows of this block against all keys: S, dP in LDS, softmax, dS, dQ; P and dS rows go to
 //    the scratch. B: grid (B*heads, ceil(T/32)) — 32 key rows: dV = P^T dO, dK = s2 dS^T Q reading scratch columns.
+template <int ORD>
 __global__ void __launch_bounds__(256) attn_bwd_rows_kernel(const float* __restrict__ qkv, const float* __restrict__ dO, float* __restrict__ dqkv,
                                                             float* __restrict__ scratch, int T, int heads, int ch, int QT) {
   extern __shared__ float sm[];
@@ -845,11 +850,12 @@ __global__ void __launch_bounds__(256) attn_bwd_rows_kernel(const float* __restr
   const int bh = blockIdx.x, b = bh / heads, h = bh % heads, i0 = blockIdx.y * QT;
   const int nq = min(QT, T - i0);
   const long ld = (long)heads * 3 * ch, ldo = (long)heads * ch;
-  const float* q = qkv + (long)b * T * ld + (long)h * 3 * ch;
-  const float* k = q + ch;
-  const float* v = q + 2 * ch;
+  const int os = attn_opnd_stride<ORD>(heads, ch);
+  const float* q = qkv + (long)b * T * ld + attn_head_off<ORD>((long)h, ch);
+  const float* k = q + os;
+  const float* v = q + 2 * os;
   const float* go = dO + (long)b * T * ldo + (long)h * ch;
-  float* dq = dqkv + (long)b * T * ld + (long)h * 3 * ch;
+  float* dq = dqkv + (long)b * T * ld + attn_head_off<ORD>((long)h, ch);
   const float s2 = 1.0f / sqrtf((float)ch);
   for (int e = threadIdx.x; e < nq * T; e += 256) {
     const int il = e / T, j = e - il * T, i = i0 + il;
@@ -888,15 +894,17 @@ __global__ void __launch_bounds__(256) attn_bwd_rows_kernel(const float* __restr
   }
 }
 
+template <int ORD>
 __global__ void __launch_bounds__(256) attn_bwd_cols_kernel(const float* __restrict__ qkv, const float* __restrict__ dO, float* __restrict__ dqkv,
                                                             const float* __restrict__ scratch, int T, int heads, int ch) {
   const int bh = blockIdx.x, b = bh / heads, h = bh % heads, j0 = blockIdx.y * 32;
   const int nk = min(32, T - j0);
   const long ld = (long)heads * 3 * ch, ldo = (long)heads * ch;
-  const float* q = qkv + (long)b * T * ld + (long)h * 3 * ch;
+  const int os = attn_opnd_stride<ORD>(heads, ch);
+  const float* q = qkv + (long)b * T * ld + attn_head_off<ORD>((long)h, ch);
   const float* go = dO + (long)b * T * ldo + (long)h * ch;
-  float* dk = dqkv + (long)b * T * ld + (long)h * 3 * ch + ch;
-  float* dv = dk + ch;
+  float* dk = dqkv + (long)b * T * ld + attn_head_off<ORD>((long)h, ch) + os;
+  float* dv = dk + os;
   const float* Pm = scratch + (long)bh * 2 * T * T;
   const float* dSm = Pm + (long)T * T;
   const float s2 = 1.0f / sqrtf((float)ch);
@@ -1573,13 +1581,13 @@ extern "C" long stedm_attn_legacy_bwd_ws_floats(int B, int T, int heads) {
   return lds <= 160 * 1024 - 1024 ? 0 : (long)B * heads * 2 * T * T;     // the LDS-resident form needs no workspace
 }
 
-extern "C" int stedm_attn_legacy_bwd(const float* qkv, const float* d_out, float* d_qkv, int B, int T, int heads, int ch, float* ws, void* stream) {
-  STEDM_CHECK_ARG(qkv && d_out && d_qkv && ch % 4 == 0, "attn_legacy_bwd: bad args");
+template <int ORD>
+static int attn_qkv_bwd_launch(const float* qkv, const float* d_out, float* d_qkv, int B, int T, int heads, int ch, float* ws, void* stream) {
   const size_t lds = (size_t)T * T * 8 + (size_t)4 * T * 33 * 4;
   static bool attr = false;
   if (!attr) {
-    STEDM_HIP_TRY(hipFuncSetAttribute((const void*)attn_legacy_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-    STEDM_HIP_TRY(hipFuncSetAttribute((const void*)attn_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+    STEDM_HIP_TRY(hipFuncSetAttribute((const void*)attn_legacy_bwd_kernel<ORD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+    STEDM_HIP_TRY(hipFuncSetAttribute((const void*)attn_bwd_rows_kernel<ORD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
     attr = true;
   }
   const size_t lds64 = ((size_t)3 * 64 * (ch + 4) + (size_t)64 * (ch + 4 > A64_PP ? ch + 4 : A64_PP) + (size_t)64 * A64_PP) * sizeof(float);
@@ -1587,22 +1595,33 @@ extern "C" int stedm_attn_legacy_bwd(const float* qkv, const float* d_out, float
       ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0) {
     static bool attr64 = false;
     if (!attr64) {
-      STEDM_HIP_TRY(hipFuncSetAttribute((const void*)attn64_bwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+      STEDM_HIP_TRY(hipFuncSetAttribute((const void*)attn64_bwd_mfma_kernel<ORD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
       attr64 = true;
     }
-    attn64_bwd_mfma_kernel<<<B * heads, 256, lds64, as_stream(stream)>>>(qkv, d_out, d_qkv, heads, ch);
+    attn64_bwd_mfma_kernel<ORD><<<B * heads, 256, lds64, as_stream(stream)>>>(qkv, d_out, d_qkv, heads, ch);
   } else if (lds <= 160 * 1024 - 1024) {
-    attn_legacy_bwd_kernel<<<B * heads, 256, lds, as_stream(stream)>>>(qkv, d_out, d_qkv, T, heads, ch);
+    attn_legacy_bwd_kernel<ORD><<<B * heads, 256, lds, as_stream(stream)>>>(qkv, d_out, d_qkv, T, heads, ch);
   } else {
-    STEDM_CHECK_ARG(ws, "attn_legacy_bwd: T = %d tokens need the workspace of stedm_attn_legacy_bwd_ws_floats", T);
+    STEDM_CHECK_ARG(ws, "attn_qkv_bwd: T = %d tokens need the workspace of stedm_attn_legacy_bwd_ws_floats", T);
     int QT = 32;
     while (QT > 1 && (size_t)QT * T * 8 > 128 * 1024) QT >>= 1;
-    STEDM_CHECK_ARG((size_t)QT * T * 8 <= 159 * 1024, "attn_legacy_bwd: T = %d tokens too many", T);
-    attn_bwd_rows_kernel<<<dim3(B * heads, (T + QT - 1) / QT), 256, (size_t)QT * T * 8, as_stream(stream)>>>(qkv, d_out, d_qkv, ws, T, heads, ch, QT);
-    attn_bwd_cols_kernel<<<dim3(B * heads, (T + 31) / 32), 256, 0, as_stream(stream)>>>(qkv, d_out, d_qkv, ws, T, heads, ch);
+    STEDM_CHECK_ARG((size_t)QT * T * 8 <= 159 * 1024, "attn_qkv_bwd: T = %d tokens too many", T);
+    attn_bwd_rows_kernel<ORD><<<dim3(B * heads, (T + QT - 1) / QT), 256, (size_t)QT * T * 8, as_stream(stream)>>>(qkv, d_out, d_qkv, ws, T, heads, ch, QT);
+    attn_bwd_cols_kernel<ORD><<<dim3(B * heads, (T + 31) / 32), 256, 0, as_stream(stream)>>>(qkv, d_out, d_qkv, ws, T, heads, ch);
   }
   STEDM_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int stedm_attn_qkv_bwd(const float* qkv, const float* d_out, float* d_qkv, int B, int T, int heads, int ch, int order, float* ws, void* stream) {
+  STEDM_CHECK_ARG(qkv && d_out && d_qkv && ch % 4 == 0, "attn_qkv_bwd: bad args");
+  STEDM_CHECK_ARG(order == STEDM_ATTN_HEADS_FIRST || order == STEDM_ATTN_QKV_FIRST, "attn_qkv_bwd: order %d is neither STEDM_ATTN_HEADS_FIRST nor STEDM_ATTN_QKV_FIRST", order);
+  return order == STEDM_ATTN_QKV_FIRST ? attn_qkv_bwd_launch<1>(qkv, d_out, d_qkv, B, T, heads, ch, ws, stream)
+                                       : attn_qkv_bwd_launch<0>(qkv, d_out, d_qkv, B, T, heads, ch, ws, stream);
+}
+
+extern "C" int stedm_attn_legacy_bwd(const float* qkv, const float* d_out, float* d_qkv, int B, int T, int heads, int ch, float* ws, void* stream) {
+  return stedm_attn_qkv_bwd(qkv, d_out, d_qkv, B, T, heads, ch, STEDM_ATTN_HEADS_FIRST, ws, stream);
 }
 
 extern "C" int stedm_gemm_f32(const float* A, long lda, int trans_a, const float* Bm, long ldb, int trans_b, float* Cm, long ldc, int M, int N, int K, float alpha,

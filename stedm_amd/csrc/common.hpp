@@ -87,4 +87,14 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// Layout of the token-major qkv plane [B][T][3 C], C = heads * ch, as two element strides: head hd's q row starts at
+// attn_head_off = hd * (head stride), its k / v rows one / two attn_opnd_stride further.
+//   ORD 0 (STEDM_ATTN_HEADS_FIRST, QKVAttentionLegacy): channel = hd * 3 ch + {q: 0, k: ch, v: 2 ch} + c
+//   ORD 1 (STEDM_ATTN_QKV_FIRST, QKVAttention):         channel = {q: 0, k: C, v: 2 C} + hd * ch + c
+// A template parameter, not a runtime stride: order 0 compiles from the expressions it always had.
+template <int ORD, typename I>
+__device__ __forceinline__ I attn_head_off(I hd, int ch) { return ORD ? hd * ch : hd * 3 * ch; }
+template <int ORD>
+__device__ __forceinline__ int attn_opnd_stride(int heads, int ch) { return ORD ? heads * ch : ch; }
+
 }  // namespace stedm

@@ -1065,24 +1065,35 @@ def spatial_rescale(x, w, out, n_stages: int):
 
 
 # ------------------------------------------------------------------------------------------- attention
-def attn_legacy(qkv: torch.Tensor, out: torch.Tensor, heads: int) -> torch.Tensor:
-    """qkv [B,T,heads*3*ch] -> out [B,T,heads*ch]."""
+ATTN_HEADS_FIRST, ATTN_QKV_FIRST = 0, 1     # STEDM_ATTN_*: QKVAttentionLegacy / QKVAttention (use_new_attention_order) split of the qkv channels
+
+
+def attn_legacy(qkv: torch.Tensor, out: torch.Tensor, heads: int, order: int = 0) -> torch.Tensor:
+    """qkv [B,T,heads*3*ch] -> out [B,T,heads*ch]. order 0: channel = h*3ch + {q,k,v}*ch + c; 1: {q,k,v}*C + h*ch + c (same out)."""
     _chk(qkv, name="qkv")
     B, T, C3 = qkv.shape
     ch = C3 // (3 * heads)
-    check(lib().stedm_attn_legacy(qkv.data_ptr(), out.data_ptr(), B, T, heads, ch, _stream()), "stedm_attn_legacy")
+    if order == ATTN_HEADS_FIRST:
+        check(lib().stedm_attn_legacy(qkv.data_ptr(), out.data_ptr(), B, T, heads, ch, _stream()), "stedm_attn_legacy")
+    else:
+        check(lib().stedm_attn_qkv(qkv.data_ptr(), out.data_ptr(), B, T, heads, ch, int(order), _stream()), "stedm_attn_qkv")
     return out
 
 
-def attn_legacy16(qkv: torch.Tensor, out16: torch.Tensor, heads: int, prec: Precision) -> torch.Tensor:
+def attn_legacy16(qkv: torch.Tensor, out16: torch.Tensor, heads: int, prec: Precision, order: int = 0) -> torch.Tensor:
     """qkv [B,T,heads*3*ch] (fp32, or the int16 plane a conv epilogue wrote) -> out16 [B,T,heads*ch] 16-bit operand plane
-    (MFMA form, single-product modes). T = 64 with ch in {32, 64, 128}; T = 64 n <= 4096 with ch in {64, 128} from the int16 plane."""
+    (MFMA form, single-product modes). T = 64 with ch in {32, 64, 128}; T = 64 n <= 4096 with ch in {64, 128} from the int16 plane.
+    order: as attn_legacy."""
     is16 = qkv.dtype == torch.int16
     _chk(qkv, torch.int16 if is16 else torch.float32, name="qkv")
     B, T, C3 = qkv.shape
     ch = C3 // (3 * heads)
     assert out16.dtype == torch.int16 and out16.numel() == B * T * heads * ch
-    check(lib().stedm_attn_legacy16(qkv.data_ptr(), 1 if is16 else 0, out16.data_ptr(), B, T, heads, ch, prec.mm_dtype, _stream()), "stedm_attn_legacy16")
+    if order == ATTN_HEADS_FIRST:
+        check(lib().stedm_attn_legacy16(qkv.data_ptr(), 1 if is16 else 0, out16.data_ptr(), B, T, heads, ch, prec.mm_dtype, _stream()), "stedm_attn_legacy16")
+    else:
+        check(lib().stedm_attn_qkv16(qkv.data_ptr(), 1 if is16 else 0, out16.data_ptr(), B, T, heads, ch, prec.mm_dtype, int(order), _stream()),
+              "stedm_attn_qkv16")
     return out16
 
 
@@ -1703,12 +1714,17 @@ def zero_insert16(x: torch.Tensor, hi: torch.Tensor, lo: Optional[torch.Tensor],
     check(lib().stedm_zero_insert16(x.data_ptr(), hi.data_ptr(), _ptr(lo), B, Ho, Wo, Cc, prec.mm_dtype, _stream()), "stedm_zero_insert16")
 
 
-def attn_legacy_bwd(qkv: torch.Tensor, d_out: torch.Tensor, d_qkv: torch.Tensor, heads: int) -> None:
+def attn_legacy_bwd(qkv: torch.Tensor, d_out: torch.Tensor, d_qkv: torch.Tensor, heads: int, order: int = 0) -> None:
+    """order: as attn_legacy (qkv and d_qkv both in that order)."""
     B, T, C3 = qkv.shape
     nws = lib().stedm_attn_legacy_bwd_ws_floats(B, T, heads)
     ws = torch.empty((nws,), dtype=torch.float32, device=qkv.device) if nws else None
-    check(lib().stedm_attn_legacy_bwd(qkv.data_ptr(), d_out.data_ptr(), d_qkv.data_ptr(), B, T, heads, C3 // (3 * heads), _ptr(ws), _stream()),
-          "stedm_attn_legacy_bwd")
+    if order == ATTN_HEADS_FIRST:
+        check(lib().stedm_attn_legacy_bwd(qkv.data_ptr(), d_out.data_ptr(), d_qkv.data_ptr(), B, T, heads, C3 // (3 * heads), _ptr(ws), _stream()),
+              "stedm_attn_legacy_bwd")
+    else:
+        check(lib().stedm_attn_qkv_bwd(qkv.data_ptr(), d_out.data_ptr(), d_qkv.data_ptr(), B, T, heads, C3 // (3 * heads), int(order), _ptr(ws),
+                                       _stream()), "stedm_attn_qkv_bwd")
 
 
 def gemm_f32(A: torch.Tensor, ta: bool, Bm: torch.Tensor, tb: bool, Cm: torch.Tensor, alpha: float = 1.0, beta: float = 0.0,

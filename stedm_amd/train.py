@@ -642,7 +642,7 @@ class UNetTrainer:
         da = self._buf(f"attn.da.{B}x{T}x{Cc}", (B, H, W, Cc))
         self._dgrad(ab.proj_out, dout16, da)
         dqkv = self._buf(f"attn.dqkv.{B}x{T}x{Cc}", (B, H, W, 3 * Cc))
-        ops.attn_legacy_bwd(qkv.view(B, T, 3 * Cc), da.view(B, T, Cc), dqkv.view(B, T, 3 * Cc), ab.num_heads)
+        ops.attn_legacy_bwd(qkv.view(B, T, 3 * Cc), da.view(B, T, Cc), dqkv.view(B, T, 3 * Cc), ab.num_heads, **ab.order_kw())
         dqkv16 = self._bias_grad(dqkv, ab.qkv.bias, cast="dy3")
         n16 = self._norm16(ab.norm, 0, x)
         self._wgrad(n16, dqkv16, dqkv, ab.qkv.weight, 1, 0)

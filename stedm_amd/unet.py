@@ -130,12 +130,12 @@ class ResBlockStyle(StyleBlock):
 
 
 class AttentionBlock(nn.Module):
-    """openaimodel.py:300-346 with QKVAttentionLegacy (use_new_attention_order=False)."""
+    """openaimodel.py:300-346. `attn_order`: how the qkv convolution's 3C channels split into heads - 0: QKVAttentionLegacy (heads
+    first, :369-394), 1: QKVAttention (q | k | v first, :401-428; use_new_attention_order=True). Same parameters in both."""
 
     def __init__(self, channels, num_heads=1, num_head_channels=-1, use_checkpoint=False, use_new_attention_order=False):
         super().__init__()
-        if use_new_attention_order:
-            raise NotImplementedError("QKVAttention (new order) is unused by the reference configs")
+        self.attn_order = ops.ATTN_QKV_FIRST if use_new_attention_order else ops.ATTN_HEADS_FIRST
         self.channels = channels
         if num_head_channels == -1:
             self.num_heads = num_heads
@@ -145,6 +145,11 @@ class AttentionBlock(nn.Module):
         self.norm = GroupNorm32(32, channels)
         self.qkv = nn.Conv1d(channels, channels * 3, 1)
         self.proj_out = zero_module(nn.Conv1d(channels, channels, 1))
+
+    def order_kw(self) -> dict:
+        """keyword arguments of the ops.attn_legacy* calls: none in order 0, so that the default order issues the call it always issued
+        (bench.py's AttnTimer and other tools replace ops.attn_legacy16 by a function of its four original arguments)"""
+        return {"order": self.attn_order} if self.attn_order != ops.ATTN_HEADS_FIRST else {}
 
 
 class _Packed:
@@ -237,7 +242,7 @@ class UNetModel(nn.Module):
             from .attention import SpatialTransformer
             mid_attn = SpatialTransformer(ch, num_heads, dim_head, depth=transformer_depth, context_dim=context_dim)
         else:
-            mid_attn = AttentionBlock(ch, num_heads=num_heads, num_head_channels=dim_head)
+            mid_attn = AttentionBlock(ch, num_heads=num_heads, num_head_channels=dim_head, use_new_attention_order=use_new_attention_order)
         self.middle_block = TimestepEmbedSequential(
             ResBlock(ch, ted, dropout, use_scale_shift_norm=ssn),
             ResBlockStyle(ch, ted, dropout, use_scale_shift_norm=ssn),
@@ -1051,7 +1056,7 @@ class UNetModel(nn.Module):
             ops.conv_igemm(None, pq.hi, pq.lo, None, prec=prec, ks=1, src16=self._norm16(ab.norm, 0, x), bias=pq.bias, w_frag=pq.frag,
                            out16=qkv16)
             a16 = self._planes(B, H, W, Cc, "attn16")
-            ops.attn_legacy16(qkv16[0].view(B, H * W, 3 * Cc), a16[0], ab.num_heads, prec)
+            ops.attn_legacy16(qkv16[0].view(B, H * W, 3 * Cc), a16[0], ab.num_heads, prec, **ab.order_kw())
             ops.conv_igemm(None, pp.hi, pp.lo, out, prec=prec, ks=1, src16=a16, bias=pp.bias, res=x, w_frag=pp.frag,
                            chan_stats=self._cs_new(out), ws=self._splitk_ws(out.numel()))
             return out
@@ -1059,7 +1064,7 @@ class UNetModel(nn.Module):
         ops.conv_igemm(None, pq.hi, pq.lo, qkv, prec=prec, ks=1, src16=self._norm16(ab.norm, 0, x), bias=pq.bias, w_frag=pq.frag,
                        w_frag16=pq.frag16 if prec.npass == 3 else None)
         a = self._buf(tag + ".a", (B, H, W, Cc))
-        ops.attn_legacy(qkv.view(B, H * W, 3 * Cc), a.view(B, H * W, Cc), ab.num_heads)
+        ops.attn_legacy(qkv.view(B, H * W, 3 * Cc), a.view(B, H * W, Cc), ab.num_heads, **ab.order_kw())
         if self._tape is not None:
             self._tape.append(("attn", ab, x, qkv, a, out))
         ops.conv_igemm(None, pp.hi, pp.lo, out, prec=prec, ks=1, src16=self._norm16(None, 0, a), bias=pp.bias, res=x, w_frag=pp.frag,
