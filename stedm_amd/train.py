@@ -126,44 +126,34 @@ class UNetTrainer:
         ops.gn_apply16(x1, x2, hi, lo, self.bprec)
         return hi, lo
 
-    def _norm16(self, norm: nn.GroupNorm, act: int, x1, x2=None):
-        m = self.m
-        kept = m._saved16.get((id(norm), x1.data_ptr()))
-        if kept is not None and self.bprec.npass == 1:       # the forward ran in the backward's operand format and kept this plane
-            return kept
-        shape = tuple(x1.shape[:-1]) + (x1.shape[-1] + (0 if x2 is None else x2.shape[-1]),)
-        hi, lo = self._planes("a16", shape)
-        ops.gn_apply16c(x1, m._chan_stats(x1), x2, None if x2 is None else m._chan_stats(x2), hi, lo, self.bprec, norm.weight, norm.bias,
-                        norm.eps, norm.num_groups, act)
-        return hi, lo
+    def _kept16(self, norm: nn.GroupNorm, x, raw: bool = False):
+        """the planes of act(norm(x)) the last training forward kept (raw: the plain conversion of x written beside them), or None
+        (UNetModel._keep). They count only where the forward ran in the backward's operand format."""
+        kept = self.m._saved16.get(("raw" if raw else id(norm), x.data_ptr()))
+        return kept if self.bprec.npass == 1 else None
 
-    def _updown16(self, rb: ResBlock, x1):
-        """_norm16 for in_layers[0] of an up / down block: the resampled SiLU(GroupNorm(x1)) planes at the block's new resolution (the operand
-        of in_layers[2]'s weight gradient), kept by the forward or recomputed by the same pass (stedm_gn_apply16c_resample)"""
-        m, norm = self.m, rb.in_layers[0]
-        kept = m._saved16.get((id(norm), x1.data_ptr()))
-        if kept is not None and self.bprec.npass == 1:
-            return kept
-        B, H, W, C = x1.shape
-        hi, lo = self._planes("a16", (B, 2 * H, 2 * W, C) if rb.up else (B, H // 2, W // 2, C))
-        ops.gn_apply16c_resample(x1, m._chan_stats(x1), hi, lo, self.bprec, norm.weight, norm.bias, 2 if rb.up else 1, norm.eps, norm.num_groups, 1)
-        return hi, lo
-
-    def _film16(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int, drop=None):
-        """_norm16 for out_layers[0] of a scale-shift-norm block: SiLU(GroupNorm(h) * (1 + scale) + shift) in the backward's operand format.
-        drop: the forward's dropout arguments of a live block (film may then be None) - the recomputed planes carry the forward's mask,
-        the counter has not moved since"""
+    def _kept_mr(self, norm: nn.GroupNorm, x1, x2=None) -> torch.Tensor:
+        """{mean, rstd} of norm over [x1|x2]: left by the forward's normalisation pass (UNetModel._keep), else folded again from the partials"""
         m = self.m
-        kept = m._saved16.get((id(norm), h.data_ptr()))
-        if kept is not None and self.bprec.npass == 1:
+        mr = m._saved_mr.get((id(norm), x1.data_ptr()))
+        if mr is None:
+            B, G = x1.shape[0], norm.num_groups
+            mr = self._buf(f"mr.{B}x{G}", (B, G, 2))
+            ops.gn_fold(m._chan_stats(x1), None if x2 is None else m._chan_stats(x2), G, x1.numel() // (B * x1.shape[-1]), norm.eps, mr)
+        return mr
+
+    def _norm16(self, norm: nn.GroupNorm, act: int, x1, x2=None, resample: int = 0, **form):
+        """act(norm([x1|x2])) in the backward's operand format: the planes the forward kept, or the forward's own pass again
+        (UNetModel._gn_site). resample (1: pool, 2: nearest x2): in_layers[0] of an up / down block, the planes at the block's new
+        resolution; form: film / film_off / film_bstride / drop of out_layers[0] in a scale-shift-norm block or one whose dropout was live
+        (the recomputed planes carry the forward's mask, the counter has not moved since)"""
+        kept = self._kept16(norm, x1)
+        if kept is not None:
             return kept
-        hi, lo = self._planes("a16", tuple(h.shape))
-        if drop is not None:
-            ops.gn_apply16c_drop(h, m._chan_stats(h), hi, lo, self.bprec, norm.weight, norm.bias, drop, norm.eps, norm.num_groups, 1,
-                                 film=film, film_off=film_off, film_bstride=film_bstride)
-            return hi, lo
-        ops.gn_apply16c_film(h, m._chan_stats(h), hi, lo, self.bprec, norm.weight, norm.bias, film, film_off, film_bstride, norm.eps,
-                             norm.num_groups, 1)
+        B, H, W, c1 = x1.shape
+        H, W = {0: (H, W), 1: (H // 2, W // 2), 2: (2 * H, 2 * W)}[resample]
+        hi, lo = self._planes("a16", (B, H, W, c1 + (0 if x2 is None else x2.shape[-1])))
+        self.m._gn_site(norm, act, x1, x2, hi=hi, lo=lo, prec=self.bprec, resample=resample, **form)
         return hi, lo
 
     def _grad_of(self, t: torch.Tensor) -> Tuple[torch.Tensor, bool]:
@@ -379,43 +369,27 @@ class UNetTrainer:
                           None if also is None else self._param_grad(also))
         return planes
 
-    def _gn_bwd(self, norm: nn.GroupNorm, act: int, x1, x2, dA, add, dx16=None):
-        m = self.m
+    def _gn_bwd(self, norm: nn.GroupNorm, act: int, x1, x2, dA, add, dx16=None, film=None, film_off: int = 0, film_bstride: int = 0, d_film=None,
+                d_film_off: int = 0, drop=None):
+        """backward of a normalise site (UNetModel._gn_site): the input gradient(s), the GroupNorm's parameter gradients and, with film,
+        dscale | dshift into columns [d_film_off, d_film_off + 2 C) of d_film (stedm_gn_bwd_film). drop: the block's dropout was live - dA
+        is masked and scaled on load (stedm_gn_bwd_drop, or stedm_gn_bwd_film_drop with film)"""
         B, c1 = x1.shape[0], x1.shape[-1]
         c2 = 0 if x2 is None else x2.shape[-1]
-        HW = x1.numel() // (B * c1)
         G = norm.num_groups
-        mr = getattr(m, "_saved_mr", {}).get((id(norm), x1.data_ptr()))   # left by the forward's normalisation pass
-        if mr is None:
-            mr = self._buf(f"mr.{B}x{G}", (B, G, 2))
-            ops.gn_fold(m._chan_stats(x1), None if x2 is None else m._chan_stats(x2), G, HW, norm.eps, mr)
-        ws = self._buf("gnws", (ops.gn_bwd_ws_floats(B, HW, c1 + c2, G),))
+        mr = self._kept_mr(norm, x1, x2)
+        ws = self._buf("gnws", (ops.gn_bwd_ws_floats(B, x1.numel() // (B * c1), c1 + c2, G),))
         g1, a1 = self._grad_of(x1)
-        g2, a2 = self._grad_of(x2) if x2 is not None else (None, False)
-        ops.gn_bwd(x1, x2, mr, norm.weight, norm.bias, G, act, dA, add, ws, g1, a1, g2, a2, dx16, self.bprec, self._param_grad(norm.weight),
-                   self._param_grad(norm.bias), False)
-
-    def _gn_bwd_film(self, norm: nn.GroupNorm, h, film, film_off: int, film_bstride: int, dA, dx16, d_film, d_film_off: int, drop=None):
-        """backward of SiLU(GroupNorm(h) * (1 + scale) + shift): dh, the GroupNorm's parameter gradients, and dscale | dshift into columns
-        [d_film_off, d_film_off + 2 C) of d_film (stedm_gn_bwd_film). drop: the block's dropout was live - dA is masked and scaled on load
-        (stedm_gn_bwd_drop, or stedm_gn_bwd_film_drop with film)"""
-        m = self.m
-        B, C = h.shape[0], h.shape[-1]
-        HW = h.numel() // (B * C)
-        G = norm.num_groups
-        mr = getattr(m, "_saved_mr", {}).get((id(norm), h.data_ptr()))
-        if mr is None:
-            mr = self._buf(f"mr.{B}x{G}", (B, G, 2))
-            ops.gn_fold(m._chan_stats(h), None, G, HW, norm.eps, mr)
-        ws = self._buf("gnws", (ops.gn_bwd_ws_floats(B, HW, C, G),))
-        g1, a1 = self._grad_of(h)
+        dw, db = self._param_grad(norm.weight), self._param_grad(norm.bias)
         if drop is not None:
-            ops.gn_bwd_drop(h, mr, norm.weight, norm.bias, G, 1, dA, None, ws, g1, a1, dx16, self.bprec, self._param_grad(norm.weight),
-                            self._param_grad(norm.bias), False, drop, film=film, film_off=film_off, film_bstride=film_bstride, d_film=d_film,
-                            d_film_off=d_film_off)
-            return
-        ops.gn_bwd_film(h, mr, norm.weight, norm.bias, G, 1, film, film_off, film_bstride, dA, None, ws, g1, a1, dx16, self.bprec,
-                        self._param_grad(norm.weight), self._param_grad(norm.bias), False, d_film, d_film_off)
+            ops.gn_bwd_drop(x1, mr, norm.weight, norm.bias, G, act, dA, add, ws, g1, a1, dx16, self.bprec, dw, db, False, drop, film=film,
+                            film_off=film_off, film_bstride=film_bstride, d_film=d_film, d_film_off=d_film_off)
+        elif film is not None:
+            ops.gn_bwd_film(x1, mr, norm.weight, norm.bias, G, act, film, film_off, film_bstride, dA, add, ws, g1, a1, dx16, self.bprec, dw, db,
+                            False, d_film, d_film_off)
+        else:
+            g2, a2 = self._grad_of(x2) if x2 is not None else (None, False)
+            ops.gn_bwd(x1, x2, mr, norm.weight, norm.bias, G, act, dA, add, ws, g1, a1, g2, a2, dx16, self.bprec, dw, db, False)
 
     # ------------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -555,66 +529,56 @@ class UNetTrainer:
         dout16 = self._bias_grad(dout, conv2.bias, cast="dy", also=rb.skip_connection.bias if has_skip else None)   # both biases add onto `out`
         if has_skip:
             sk = rb.skip_connection
-            x16 = self.m._saved16.get(("raw", x1.data_ptr())) or self._cast16(x1, x2, kind="x16")
+            x16 = self._kept16(rb.in_layers[0], x1, raw=True) or self._cast16(x1, x2, kind="x16")
             self._wgrad(x16, dout16, dout, sk.weight, 1, 0)
             add = self._buf(f"add.{B}x{H}x{W}x{cin}", (B, H, W, cin))
             self._dgrad(sk, dout16, add)
         else:
             add = dout
         # conv2 and its GroupNorm + SiLU
-        film = rb.use_scale_shift_norm
+        gn2 = rb.out_layers[0]
+        form = {}
         drop = self.m._drop_used.get(id(rb))       # the forward's dropout arguments when the block's dropout was live
-        if film:
+        if drop is not None:
+            form.update(drop=drop)
+        if rb.use_scale_shift_norm:
             # scale | shift of this block: its columns of the concatenated embedding projection, or the style projection (row stride = width)
             fsrc = self.tape_film[1] if emb_off is None else self.tape_film[0]
-            foff, fbs = (0 if emb_off is None else emb_off), fsrc.shape[1]
-            h16 = self._film16(rb.out_layers[0], h, fsrc, foff, fbs, drop)
-        elif drop is not None:
-            h16 = self._film16(rb.out_layers[0], h, None, 0, 0, drop)
-        else:
-            h16 = self._norm16(rb.out_layers[0], 1, h)
+            form.update(film=fsrc, film_off=0 if emb_off is None else emb_off, film_bstride=fsrc.shape[1])
+        h16 = self._norm16(gn2, 1, h, **form)
         self._wgrad(h16, dout16, dout, conv2.weight, 3, 0)
         dA2 = self._buf(f"dA.{B}x{H}x{W}x{co}", (B, H, W, co))
         self._dgrad(conv2, dout16, dA2)
         dh16 = self._planes("dh16", (B, H, W, co))
-        if film:
+        eb = rb.emb_layers[1].bias
+        if rb.use_scale_shift_norm:
             # the embedding modulates out_layers' GroupNorm (openaimodel.py:280-284): its gradient dscale | dshift comes out of that
             # GroupNorm's backward; nothing adds onto h but conv1's bias, whose gradient is the batch sum of dh alone
             if emb_off is None:
-                self.dEs = self._buf("dEs", (B, 2 * co))
-                dmat, doff = self.dEs, 0
+                dmat = self.dEs = self._buf("dEs", (B, 2 * co))
             else:
-                dmat, doff = self.dE, emb_off
-            self._gn_bwd_film(rb.out_layers[0], h, fsrc, foff, fbs, dA2, dh16, dmat, doff, drop)
+                dmat = self.dE
+            self._gn_bwd(gn2, 1, h, None, dA2, None, dh16, d_film=dmat, d_film_off=emb_off or 0, **form)
             dh = self.G[h.data_ptr()]
             self._bias_grad(dh, conv1.bias)
             blk = dmat
             if emb_off is not None:
                 blk = self._buf(f"dEblk.{B}x{2 * co}", (B, 2 * co))
-                blk.copy_(dmat[:, doff:doff + 2 * co])
-            self._colsum(blk, self._param_grad(rb.emb_layers[1].bias))       # emb_layers[1].bias: the column sums of its dE block
-            self._res_bwd_front(rb, x1, x2, dh, dh16, add, cin)
-            return
-        if drop is not None:
-            self._gn_bwd_film(rb.out_layers[0], h, None, 0, 0, dA2, dh16, None, 0, drop)
+                blk.copy_(dmat[:, emb_off:emb_off + 2 * co])
+            self._colsum(blk, self._param_grad(eb))       # emb_layers[1].bias: the column sums of its dE block
         else:
-            self._gn_bwd(rb.out_layers[0], 1, h, None, dA2, None, dx16=dh16)
-        dh = self.G[h.data_ptr()]
-        # the embedding enters between conv1 and the second GroupNorm (openaimodel.py:276-287): its gradient is the per-sample
-        # channel sum of dh, conv1's bias gradient the batch total
-        eb = rb.emb_layers[1].bias                                        # same sums: both biases add onto h
-        if emb_off is None:
-            self.dEs = self._buf("dEs", (B, co))
-            self._bias_grad(dh, conv1.bias, self.dEs, co, also=eb)
-        else:
-            self._bias_grad(dh, conv1.bias, self.dE[:, emb_off:], self.dE.shape[1], also=eb)
-        self._res_bwd_front(rb, x1, x2, dh, dh16, add, cin)
-
-    def _res_bwd_front(self, rb: ResBlock, x1, x2, dh, dh16, add, cin):
-        B, H, W, _ = dh.shape
-        conv1 = rb.in_layers[2]
+            self._gn_bwd(gn2, 1, h, None, dA2, None, dh16, **form)
+            dh = self.G[h.data_ptr()]
+            # the embedding enters between conv1 and the second GroupNorm (openaimodel.py:276-287): its gradient is the per-sample
+            # channel sum of dh, conv1's bias gradient the batch total (same sums: both biases add onto h)
+            if emb_off is None:
+                self.dEs = self._buf("dEs", (B, co))
+                self._bias_grad(dh, conv1.bias, self.dEs, co, also=eb)
+            else:
+                self._bias_grad(dh, conv1.bias, self.dE[:, emb_off:], self.dE.shape[1], also=eb)
         # conv1 and the first GroupNorm + SiLU over the (virtual concat) input
-        a16 = self._updown16(rb, x1) if rb.updown else self._norm16(rb.in_layers[0], 1, x1, x2)
+        gn1 = rb.in_layers[0]
+        a16 = self._norm16(gn1, 1, x1, x2, resample=(2 if rb.up else 1) if rb.updown else 0)
         self._wgrad(a16, dh16, dh, conv1.weight, 3, 0)
         dA1 = self._buf(f"dA1.{B}x{H}x{W}x{cin}", (B, H, W, cin))
         self._dgrad(conv1, dh16, dA1)
@@ -629,7 +593,7 @@ class UNetTrainer:
                 else:
                     ops.replicate2x2(src, dst, 0.25, False)
             dA1, add = dA1s, adds
-        self._gn_bwd(rb.in_layers[0], 1, x1, x2, dA1, add)
+        self._gn_bwd(gn1, 1, x1, x2, dA1, add)
 
     def _attn_bwd(self, ab: AttentionBlock, x, qkv, a, out):
         B, H, W, Cc = x.shape

@@ -600,80 +600,71 @@ class UNetModel(nn.Module):
             ops.gn_apply16c_x16(c1, self._cs[x1.data_ptr()], x2, None if x2 is None else self._chan_stats(x2), hi, rawp, self.precision,
                                 norm.weight, norm.bias, norm.eps, norm.num_groups, act, x2_bmod)
             return (hi, None), (rawp, None)
-        # training forward in the backward's operand format (bf16 single product): each normalised plane gets its own buffer and is kept
-        # for the weight-gradient pass instead of being recomputed there
-        keep = self._tape is not None and norm is not None and self.precision.npass == 1 and self.precision.mm_dtype == BF16
-        if keep:
-            self._plane_ctr += 1
-            hi, lo = self._planes(B, H, W, C, f"keep{self._plane_ctr}.a16")
-            self._saved16[(id(norm), x1.data_ptr())] = (hi, lo)
-        else:
-            hi, lo = self._planes(B, H, W, C)
         if norm is None:
+            hi, lo = self._planes(B, H, W, C)
             ops.gn_apply16(x1, x2, hi, lo, self.precision, x2_bmod=x2_bmod)
             return hi, lo
-        if want_raw and keep:
-            raw = self._planes(B, H, W, C, f"keep{self._plane_ctr}.raw16")
-            self._saved16[("raw", x1.data_ptr())] = raw
-        else:
-            raw = self._planes(B, H, W, C, "raw16") if want_raw else None
-        mr = None
-        if self._tape is not None:       # training forward: keep the group statistics this pass folds (the backward needs them again)
-            self._mr_ctr += 1
-            mr = self._buf(f"keep{self._mr_ctr}.mr", (B, norm.num_groups, 2))
-            self._saved_mr[(id(norm), x1.data_ptr())] = mr
-        ops.gn_apply16c(x1, self._chan_stats(x1), x2, None if x2 is None else self._chan_stats(x2), hi, lo, self.precision,
-                        norm.weight, norm.bias, norm.eps, norm.num_groups, act, x2_bmod, raw, mean_rstd=mr)
+        (hi, lo), raw, mr = self._keep(norm, x1, (B, H, W, C), want_raw=want_raw)
+        self._gn_site(norm, act, x1, x2, x2_bmod, hi=hi, lo=lo, prec=self.precision, raw=raw, mean_rstd=mr)
         return ((hi, lo), raw) if want_raw else (hi, lo)
 
-    def _updown16(self, rb: "ResBlock", x1):
-        """The front of an up / down ResBlock (openaimodel.py:268-275): SiLU(GroupNorm(x1)) resampled into 16-bit planes, and x1 resampled the
-        same way (the block's residual), both at the new resolution, from one read of x1 (ops.gn_apply16c_resample). Training keeps the
-        planes and {mean, rstd} under the keys _norm16 uses."""
-        norm = rb.in_layers[0]
-        B, H, W, C = x1.shape
-        Hn, Wn = (2 * H, 2 * W) if rb.up else (H // 2, W // 2)
+    def _keep(self, norm: nn.GroupNorm, x, shape, kind="a16", want_raw=False):
+        """(planes, raw, mean_rstd) a normalise site of `norm` over x writes: THE statement of what a forward keeps for the backward
+        (UNetTrainer._kept16 / _kept_mr read it back). A training forward in the backward's operand format (bf16 single product) gives each
+        normalised plane - and, with want_raw, the plain conversion beside it - its own buffer, kept for the weight-gradient pass instead of
+        being recomputed there; every training forward keeps the group statistics the pass folds (the backward needs them again).
+        Otherwise: the shape-keyed buffers of `kind` (raw: "raw16"), and no statistics buffer."""
+        B, H, W, C = shape
+        key = (id(norm), x.data_ptr())
         keep = self._tape is not None and self.precision.npass == 1 and self.precision.mm_dtype == BF16
         if keep:
             self._plane_ctr += 1
-            hi, lo = self._planes(B, Hn, Wn, C, f"keep{self._plane_ctr}.a16")
-            self._saved16[(id(norm), x1.data_ptr())] = (hi, lo)
+            planes = self._saved16[key] = self._planes(B, H, W, C, f"keep{self._plane_ctr}.a16")
         else:
-            hi, lo = self._planes(B, Hn, Wn, C)
+            planes = self._planes(B, H, W, C, kind)
+        raw = None
+        if want_raw and keep:
+            raw = self._saved16[("raw", x.data_ptr())] = self._planes(B, H, W, C, f"keep{self._plane_ctr}.raw16")
+        elif want_raw:
+            raw = self._planes(B, H, W, C, "raw16")
         mr = None
         if self._tape is not None:
             self._mr_ctr += 1
-            mr = self._buf(f"keep{self._mr_ctr}.mr", (B, norm.num_groups, 2))
-            self._saved_mr[(id(norm), x1.data_ptr())] = mr
-        xr = self._buf(f"xr.{B}x{Hn}x{Wn}x{C}", (B, Hn, Wn, C))
-        ops.gn_apply16c_resample(x1, self._chan_stats(x1), hi, lo, self.precision, norm.weight, norm.bias, 2 if rb.up else 1, norm.eps,
-                                 norm.num_groups, 1, xr=xr, mean_rstd=mr)
-        return (hi, lo), xr
+            mr = self._saved_mr[key] = self._buf(f"keep{self._mr_ctr}.mr", (B, norm.num_groups, 2))
+        return planes, raw, mr
 
-    def _film16(self, norm: nn.GroupNorm, h, film, film_off, film_bstride, drop=None):
-        """SiLU(GroupNorm(h) * (1 + scale) + shift) as 16-bit planes, scale | shift = columns [film_off, film_off + 2 C) of sample b's row of
-        `film` (row stride film_bstride; 0: one shared row). Training keeps the planes and {mean, rstd} exactly as _norm16 / _res do.
-        drop (_drop_args): the block's dropout is live - the same pass masks and scales the activation (film may then be None: a plain block)."""
-        B, H, W, C = h.shape
-        keep = self._tape is not None and self.precision.npass == 1 and self.precision.mm_dtype == BF16
-        if keep:
-            self._plane_ctr += 1
-            hi, lo = self._planes(B, H, W, C, f"keep{self._plane_ctr}.a16")
-            self._saved16[(id(norm), h.data_ptr())] = (hi, lo)
+    def _gn_site(self, norm: nn.GroupNorm, act: int, x1, x2=None, x2_bmod=0, *, hi, lo, prec, raw=None, mean_rstd=None, film=None, film_off=0,
+                 film_bstride=0, drop=None, resample=0, xr=None) -> None:
+        """One normalise site, act(GroupNorm([x1|x2]) [* (1 + scale) + shift] [dropout]) [resampled], into the 16-bit planes hi (/ lo) in
+        format `prec` - the forward with its own precision and the outputs of _keep, the backward's recompute with its own. The library pass:
+        resample (1: 2 x 2 average pool, 2: nearest x2; the front of an up / down ResBlock, openaimodel.py:268-275; xr: x1 resampled the
+        same way, the block's residual, from the same read) -> gn_apply16c_resample; drop (_drop_args: the block's dropout is live - the
+        pass masks and scales the activation; film may be None) -> gn_apply16c_drop; film (scale | shift = columns [film_off, film_off + 2 C)
+        of sample b's row, row stride film_bstride, 0: one shared row) -> gn_apply16c_film; else gn_apply16c."""
+        w, b, eps, G = norm.weight, norm.bias, norm.eps, norm.num_groups
+        if resample:
+            assert x2 is None and film is None and drop is None and raw is None
+            ops.gn_apply16c_resample(x1, self._chan_stats(x1), hi, lo, prec, w, b, resample, eps, G, act, xr=xr, mean_rstd=mean_rstd)
+        elif drop is not None:
+            ops.gn_apply16c_drop(x1, self._chan_stats(x1), hi, lo, prec, w, b, drop, eps, G, act, mean_rstd=mean_rstd, film=film,
+                                 film_off=film_off, film_bstride=film_bstride)
+        elif film is not None:
+            ops.gn_apply16c_film(x1, self._chan_stats(x1), hi, lo, prec, w, b, film, film_off, film_bstride, eps, G, act, mean_rstd=mean_rstd)
         else:
-            hi, lo = self._planes(B, H, W, C, "g16")
-        mr = None
-        if self._tape is not None:
-            self._mr_ctr += 1
-            mr = self._buf(f"keep{self._mr_ctr}.mr", (B, norm.num_groups, 2))
-            self._saved_mr[(id(norm), h.data_ptr())] = mr
-        if drop is not None:
-            ops.gn_apply16c_drop(h, self._chan_stats(h), hi, lo, self.precision, norm.weight, norm.bias, drop, norm.eps, norm.num_groups, 1,
-                                 mean_rstd=mr, film=film, film_off=film_off, film_bstride=film_bstride)
-            return hi, lo
-        ops.gn_apply16c_film(h, self._chan_stats(h), hi, lo, self.precision, norm.weight, norm.bias, film, film_off, film_bstride, norm.eps,
-                             norm.num_groups, 1, mean_rstd=mr)
-        return hi, lo
+            ops.gn_apply16c(x1, self._chan_stats(x1), x2, None if x2 is None else self._chan_stats(x2), hi, lo, prec, w, b, eps, G, act,
+                            x2_bmod, raw, mean_rstd=mean_rstd)
+
+    def _gn_next(self, norm: nn.GroupNorm, act: int, planes, mr, only: bool) -> tuple:
+        """conv_igemm's gn_next: `norm` + act of the launch's output ride on it, into `planes` - the (hi, lo) pair in the 3-product modes, the
+        hi plane otherwise - with the group statistics into mr (or None); only: nothing else reads the output, its fp32 store is skipped"""
+        return (norm.weight, norm.bias, norm.eps, norm.num_groups, act, planes if self.precision.npass == 3 else planes[0], mr, only)
+
+    def _asked(self, key: tuple, ask):
+        """the answer filed in _consts under `key`, asked (ask()) the first time: the library is asked once per shape whether it takes a launch"""
+        hit = self._consts.get(key)
+        if hit is None:
+            hit = self._consts[key] = ask()
+        return hit
 
     def _coop_for(self, site: str, B, H, W, co, prec):
         """(words, state) for stedm_conv_args.gn_coop at call site `site`, or None: a sample of 2 .. 4 tiles at 128 channels on a grid that fills
@@ -709,9 +700,12 @@ class UNetModel(nn.Module):
         xres = x1                      # the residual of a block without a skip_connection convolution
         if rb.updown:
             # openaimodel.py:268-275: one pass leaves in_layers' activation planes and the input at the NEW resolution, which is H, W from here on
+            # (ops.gn_apply16c_resample: both from one read of x1)
             assert x2 is None and not has_skip
-            a16, xres = self._updown16(rb, x1)
-            H, W = xres.shape[1], xres.shape[2]
+            H, W = (2 * H, 2 * W) if rb.up else (H // 2, W // 2)
+            a16, _, mr = self._keep(rb.in_layers[0], x1, (B, H, W, x1.shape[-1]))
+            xres = self._buf(f"xr.{B}x{H}x{W}x{x1.shape[-1]}", (B, H, W, x1.shape[-1]))
+            self._gn_site(rb.in_layers[0], 1, x1, hi=a16[0], lo=a16[1], prec=prec, mean_rstd=mr, resample=2 if rb.up else 1, xr=xres)
         # training keeps every block's intermediate (the backward pass reads it); inference shares one buffer per shape
         h = self._buf(tag + ".h" if self._tape is not None else f"h.{B}x{H}x{W}x{co}", (B, H, W, co))
         self._last_h = h
@@ -727,7 +721,7 @@ class UNetModel(nn.Module):
         gn2 = rb.out_layers[0]
         # A scale-shift-norm block (FiLM): the embedding row does not add onto h (no epilogue term) but modulates out_layers' GroupNorm per
         # sample, so none of the producer-side forms of that GroupNorm applies (gn_next in the epilogue / reduce pass, gn_coop, the
-        # 16-bit-only h): the convolution writes fp32 h and its statistics, and one stedm_gn_apply16c_film pass writes the planes (_film16)
+        # 16-bit-only h): the convolution writes fp32 h and its statistics, and one stedm_gn_apply16c_film pass writes the planes (_gn_site)
         # Live dropout (train(), dropout > 0) sits between that GroupNorm's SiLU and the 16-bit rounding: the same treatment - fp32 h and its
         # statistics, then one stedm_gn_apply16c_drop / _film_drop pass; the embedding row still adds onto h in the epilogue of a plain block
         film = rb.use_scale_shift_norm
@@ -735,22 +729,11 @@ class UNetModel(nn.Module):
         if self._tape is not None and self._drop_live(rb):
             drop = self._drop_used[id(rb)] = self._drop_args(rb)
         if not film and drop is None and ((prec.npass == 1 and (self._tape is None or prec.mm_dtype == BF16)) or (prec.npass == 3 and self._tape is None)):
-            if self._tape is None:
-                # NOT the planes _norm16 would hand out: for cin == cout those are the planes this convolution is reading, and an epilogue
-                # that writes the GroupNorm output would overwrite rows other tiles still gather
-                h16_next = self._planes(B, H, W, co, "g16")
-                mr2 = None
-            else:
-                # training forward in the backward's operand format: the planes and the group statistics are kept, exactly as _norm16 keeps them
-                self._plane_ctr += 1
-                h16_next = self._planes(B, H, W, co, f"keep{self._plane_ctr}.a16")
-                self._saved16[(id(gn2), h.data_ptr())] = h16_next
-                self._mr_ctr += 1
-                mr2 = self._buf(f"keep{self._mr_ctr}.mr", (B, gn2.num_groups, 2))
-                self._saved_mr[(id(gn2), h.data_ptr())] = mr2
+            # inference: NOT the planes _norm16 would hand out ("g16"): for cin == cout those are the planes this convolution is reading, and
+            # an epilogue that writes the GroupNorm output would overwrite rows other tiles still gather
+            h16_next, _, mr2 = self._keep(gn2, h, (B, H, W, co), "g16")
             # (inference: nothing but that GroupNorm reads h — an epilogue that writes the planes itself skips h's fp32 store)
-            # (3-product modes, round 4: the (hi, lo) pair; single-product: the hi plane)
-            gn_next = (gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1, h16_next if prec.npass == 3 else h16_next[0], mr2, self._tape is None)
+            gn_next = self._gn_next(gn2, 1, h16_next, mr2, self._tape is None)
         done1 = False
         # (where a sample spans 2 .. 4 tiles - 32 x 32 pixels at 128 channels - the tiles exchange their channel sums inside the launch
         #  and the GroupNorm still rides on the epilogue: stedm_conv_args.gn_coop; one word block per call site)
@@ -762,16 +745,11 @@ class UNetModel(nn.Module):
             # the convolution stores h as 16-bit values only (+ the channel statistics) and the GroupNorm pass reads 2 B per element.
             # bf16 mode only: in f16 - the mode that carries the 1e-3 tolerance - the extra rounding in front of five more GroupNorms moved the
             # forward's rel-L2 from 7.55e-4 to 7.86e-4 for +0.5 % of a step (6.165 -> 6.135 ms); the margin is worth more
-            kw1 = dict(prec=prec, src16=a16, bias=pk.bias, emb=emb_all, emb_offset=emb_off, emb_bstride=emb_bstride, w_frag=pk.frag,
-                       chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16)
             hraw = self._buf(f"h16raw.{B}x{H}x{W}x{co}", (B, H, W, co), torch.int16)
-            key1 = ("h16only", id(rb), B, H, W)
-            ok1 = self._consts.get(key1)
-            if ok1 is None:
-                ok1 = bool(ops.conv_igemm(None, pk.hi, pk.lo, None, query_rs=True, out16=(hraw, None), out16_stride=co, cout=co, **kw1))
-                self._consts[key1] = ok1
-            if ok1:
-                ops.conv_igemm(None, pk.hi, pk.lo, None, out16=(hraw, None), out16_stride=co, cout=co, **kw1)
+            kw1 = dict(prec=prec, src16=a16, bias=pk.bias, emb=emb_all, emb_offset=emb_off, emb_bstride=emb_bstride, w_frag=pk.frag,
+                       chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16, out16=(hraw, None), out16_stride=co, cout=co)
+            if self._asked(("h16only", id(rb), B, H, W), lambda: bool(ops.conv_igemm(None, pk.hi, pk.lo, None, query_rs=True, **kw1))):
+                ops.conv_igemm(None, pk.hi, pk.lo, None, **kw1)
                 ops.gn_apply16c_x16(co, self._cs[h.data_ptr()], None, None, h16_next[0], hraw, prec, gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1)
                 done1 = True
         if not done1:
@@ -779,7 +757,9 @@ class UNetModel(nn.Module):
                        chan_stats=self._cs_new(h), ws=ws, w_frag16=pk.frag16, gn_next=gn_next, coop=coop)
             self._in_conv(tag, rb, pk, a16, x1.shape[-1], x2_bmod if x2 is not None else 0, h, kw1)
         if film or drop is not None:
-            h16_next = self._film16(gn2, h, emb_all if film else None, emb_off, emb_bstride, drop)
+            h16_next, _, mr2 = self._keep(gn2, h, (B, H, W, co), "g16")
+            self._gn_site(gn2, 1, h, hi=h16_next[0], lo=h16_next[1], prec=prec, mean_rstd=mr2, film=emb_all if film else None, film_off=emb_off,
+                          film_bstride=emb_bstride, drop=drop)
         out = self._buf(tag + ".out", (B, H, W, co))
         pk2 = self._packed[id(rb.out_layers[3])]
         o16 = None
@@ -792,9 +772,8 @@ class UNetModel(nn.Module):
         # _norm16 hands them out instead of running its own pass (inference)
         gnn, npl, coop2 = None, None, None
         if next_norm is not None and self._tape is None and o16 is None and next_cat is None and not os.environ.get("STEDM_NO_NEXT_GN"):
-            nn_, nact = next_norm
             npl = self._planes(B, H, W, co)
-            gnn = (nn_.weight, nn_.bias, nn_.eps, nn_.num_groups, nact, npl if prec.npass == 3 else npl[0], None, False)
+            gnn = self._gn_next(*next_norm, npl, None, False)
             coop2 = self._coop_for(tag + ".c2", B, H, W, co, prec)     # (32 x 32 at 128 channels: the in-launch hand-off, as for out_layers' GroupNorm)
 
         def filed():
@@ -805,49 +784,33 @@ class UNetModel(nn.Module):
             # conv2 + skip_connection(x) in one kernel when the register-streamed kernel covers the problem (asked once per shape)
             ps = self._packed[id(rb.skip_connection)]
             h16 = h16_next if h16_next is not None else self._norm16(rb.out_layers[0], 1, h)
-            fuse_key = ("fuse", id(rb), B, H, W)
-            fused = self._consts.get(fuse_key)
             kw = dict(prec=prec, src16=h16, bias=pk2.bias, w_frag=pk2.frag, chan_stats=self._cs_new(out), ws=ws, out16=o16, w_frag16=pk2.frag16)
-            if fused is None:
-                fused = bool((pk2.frag is not None or pk2.frag16 is not None) and ps.frag is not None and
-                             ops.conv_igemm(None, pk2.hi, pk2.lo, out, skip=(x16[0], ps.frag, ps.bias, ps.frag16), query_fused=True, **kw))
-                self._consts[fuse_key] = fused
+            kwf = dict(kw, skip=(x16[0], ps.frag, ps.bias, ps.frag16))
+            fused = self._asked(("fuse", id(rb), B, H, W), lambda: bool((pk2.frag is not None or pk2.frag16 is not None) and ps.frag is not None and
+                                                                        ops.conv_igemm(None, pk2.hi, pk2.lo, out, query_fused=True, **kwf)))
             if fused and next_cat is not None and o16 is None:
-                keyc = ("fusecat", id(rb), B, H, W, next_cat)
-                okc = self._consts.get(keyc)
                 rawn = self._cat_plane(B, H, W, co, next_cat)
-                kwc = dict(kw, out16=(rawn, None), out16_stride=next_cat, cout=co)
-                if okc is None:
-                    okc = bool(ops.conv_igemm(None, pk2.hi, pk2.lo, None, skip=(x16[0], ps.frag, ps.bias, ps.frag16), query_fused=True, **kwc))
-                    self._consts[keyc] = okc
-                if okc:
-                    ops.conv_igemm(None, pk2.hi, pk2.lo, None, skip=(x16[0], ps.frag, ps.bias, ps.frag16), **kwc)
+                kwc = dict(kwf, out16=(rawn, None), out16_stride=next_cat, cout=co)
+                if self._asked(("fusecat", id(rb), B, H, W, next_cat), lambda: bool(ops.conv_igemm(None, pk2.hi, pk2.lo, None, query_fused=True, **kwc))):
+                    ops.conv_igemm(None, pk2.hi, pk2.lo, None, **kwc)
                     self._x16[out.data_ptr()] = (rawn, co)
                     return out
-            only16 = False
             if fused and o16 is not None and self._tape is None and prec.npass == 1:
                 # inference: the Upsample that follows reads the 16-bit planes only — the fp32 tensor and its statistics need not be written.
                 # A launch that splits K (small grids) has to write the fp32 tensor, though: asked once per shape
-                key16 = ("fuse16", id(rb), B, H, W)
-                only16 = self._consts.get(key16)
-                if only16 is None:
-                    only16 = bool(ops.conv_igemm(None, pk2.hi, pk2.lo, None, skip=(x16[0], ps.frag, ps.bias, ps.frag16), query_fused=True,
-                                                 **dict(kw, chan_stats=None)))
-                    self._consts[key16] = only16
-            if only16:
-                # (`out` stays the handle the planes are filed under)
-                kw.update(chan_stats=None)
-                self._cs.pop(out.data_ptr(), None)          # (no statistics are written for the handle: nothing may find a buffer for it)
-                ops.conv_igemm(None, pk2.hi, pk2.lo, None, skip=(x16[0], ps.frag, ps.bias, ps.frag16), **kw)
-            elif fused:
-                ops.conv_igemm(None, pk2.hi, pk2.lo, out, skip=(x16[0], ps.frag, ps.bias, ps.frag16), gn_next=gnn, **kw)
-                return filed()
+                kw16 = dict(kwf, chan_stats=None)
+                if self._asked(("fuse16", id(rb), B, H, W), lambda: bool(ops.conv_igemm(None, pk2.hi, pk2.lo, None, query_fused=True, **kw16))):
+                    # (`out` stays the handle the planes are filed under)
+                    self._cs.pop(out.data_ptr(), None)          # (no statistics are written for the handle: nothing may find a buffer for it)
+                    ops.conv_igemm(None, pk2.hi, pk2.lo, None, **kw16)
+                    return out
+            if fused:
+                ops.conv_igemm(None, pk2.hi, pk2.lo, out, gn_next=gnn, **kwf)
             else:
                 ops.conv_igemm(None, ps.hi, ps.lo, out, prec=prec, ks=1, src16=x16, bias=ps.bias, w_frag=ps.frag, ws=ws,
                                w_frag16=ps.frag16 if prec.npass == 3 else None)
                 ops.conv_igemm(None, pk2.hi, pk2.lo, out, res=out, gn_next=gnn, **kw)
-                return filed()
-            return out
+            return filed()
         # no skip_connection convolution: the residual is the block's input itself
         assert x2 is None
         h16 = h16_next if h16_next is not None else self._norm16(rb.out_layers[0], 1, h)
@@ -855,12 +818,7 @@ class UNetModel(nn.Module):
             rawn = self._cat_plane(B, H, W, co, next_cat)
             kwc = dict(prec=prec, src16=h16, bias=pk2.bias, res=xres, w_frag=pk2.frag, chan_stats=self._cs_new(out), ws=ws, w_frag16=pk2.frag16,
                        out16=(rawn, None), out16_stride=next_cat, cout=co)
-            keyc = ("rescat", id(rb), B, H, W, next_cat)
-            okc = self._consts.get(keyc)
-            if okc is None:
-                okc = bool(ops.conv_igemm(None, pk2.hi, pk2.lo, None, query_rs=True, **kwc))
-                self._consts[keyc] = okc
-            if okc:
+            if self._asked(("rescat", id(rb), B, H, W, next_cat), lambda: bool(ops.conv_igemm(None, pk2.hi, pk2.lo, None, query_rs=True, **kwc))):
                 ops.conv_igemm(None, pk2.hi, pk2.lo, None, **kwc)
                 self._x16[out.data_ptr()] = (rawn, co)
                 return out
@@ -879,17 +837,23 @@ class UNetModel(nn.Module):
             ops.conv_igemm(None, pk.hi, pk.lo, h, src16=a16, **kw)
             return
         seam, P, P2 = plan
-        Bs = P.shape[0]
         if P2 is not None:
             # the shared launch splits K two ways: its two partials stay where the kernel wrote them and the 2B launch adds p0 + p1 as its
             # residual (stedm_conv_args.res2) - the bits of the reduced P without the reduce launch, its store and its re-read
-            n = ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:Bs, :, :, seam:], None), w_frag=pk.frag, w_frag16=pk.frag16,
-                               ws=P2.view(-1), partials=True)
+            shared, rest = self._skip_kw(pk, a16, kw, seam, P.shape[0], P2.view(-1), res=P2[0], res2=P2[1])
+            n = ops.conv_igemm(None, pk.hi, pk.lo, P, partials=True, **shared)
             assert n == 2, n
-            ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P2[0], res2=P2[1], res_bmod=Bs, **kw)
-            return
-        ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:Bs, :, :, seam:], None), w_frag=pk.frag, w_frag16=pk.frag16, ws=kw["ws"])
-        ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P, res_bmod=Bs, **kw)
+        else:
+            shared, rest = self._skip_kw(pk, a16, kw, seam, P.shape[0], kw["ws"], res=P)
+            ops.conv_igemm(None, pk.hi, pk.lo, P, **shared)
+        ops.conv_igemm(None, pk.hi, pk.lo, h, **rest)
+
+    @staticmethod
+    def _skip_kw(pk, a16, kw, seam: int, Bs: int, ws, **res):
+        """keyword sets of _in_conv's pair, for its launches and for _shared_skip's dry queries: the shared launch over the skip channels
+        [seam, C) at batch Bs with workspace ws, and the 2B launch over [0, seam) with the residual(s) `res` read modulo Bs"""
+        return (dict(prec=kw["prec"], src16=(a16[0][:Bs, :, :, seam:], None), w_frag=pk.frag, w_frag16=pk.frag16, ws=ws),
+                dict(kw, src16=(a16[0][:, :, :, :seam], None), res_bmod=Bs, **res))
 
     def _shared_skip(self, rb: ResBlock, pk, a16, c1: int, x2_bmod: int, h, kw):
         """(seam, P, P2) when the in_layers convolution of `rb` runs as shared launch + 2B launch (_in_conv), else None. Inference, one CFG pair
@@ -900,39 +864,37 @@ class UNetModel(nn.Module):
                 a16[0].shape[0] != Bd or not a16[0].is_contiguous()):
             return None
         key = ("sskip", id(rb), Bd, H, W, self.cfg_shared_skip, self.cfg_skip_partials)
-        hit = self._consts.get(key)
-        if hit is None:
-            norm = rb.in_layers[0]
+
+        def ask():
             C = a16[0].shape[-1]
-            cpg = C // norm.num_groups
+            cpg = C // rb.in_layers[0].num_groups
             # first 32-channel boundary from which every GroupNorm group holds skip channels only; one chunk further when that makes the
             # shared chunk count even (the K split of a small grid halves it: 15 chunks would not split, 14 do)
             seam = -(-(-(-c1 // cpg) * cpg) // 32) * 32
             if (C - seam) // 32 > 1 and ((C - seam) // 32) % 2:
                 seam += 32
-            hit = 0
-            if 32 <= seam <= C - 32 and (pk.frag is not None or pk.frag16 is not None):
-                P = self._buf(f"sskip.P.{x2_bmod}x{H}x{W}x{co}", (x2_bmod, H, W, co))
-                ok = bool(ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:x2_bmod, :, :, seam:], None), w_frag=pk.frag,
-                                         w_frag16=pk.frag16, ws=kw["ws"], query_rs=True))
-                ok = ok and bool(ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P, res_bmod=x2_bmod, query_rs=True, **kw))
-                if ok and (self.cfg_shared_skip or self._shared_skip_rule(Bd, H, W, co, C, seam)):
-                    hit = seam
-                    # a two-way K split of the shared launch (asked with the workspace the plain form would use): partials as res / res2
-                    two = self.cfg_skip_partials is True and kw["ws"] is not None and ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:x2_bmod, :, :, seam:], None), w_frag=pk.frag,
-                                                                  w_frag16=pk.frag16, ws=kw["ws"], partials=True, query_rs=True) == 2
-                    if two:
-                        P2 = self._buf(f"sskip.P2.{x2_bmod}x{H}x{W}x{co}", (2, x2_bmod, H, W, co))
-                        two = (ops.conv_igemm(None, pk.hi, pk.lo, P, prec=kw["prec"], src16=(a16[0][:x2_bmod, :, :, seam:], None), w_frag=pk.frag,
-                                              w_frag16=pk.frag16, ws=P2.view(-1), partials=True, query_rs=True) == 2 and
-                               bool(ops.conv_igemm(None, pk.hi, pk.lo, h, src16=(a16[0][:, :, :, :seam], None), res=P2[0], res2=P2[1], res_bmod=x2_bmod,
-                                                   query_rs=True, **kw)))
-                    self._consts[("sskip2",) + key[1:]] = bool(two)
-            self._consts[key] = hit
-        if not hit:
+            if not (32 <= seam <= C - 32 and (pk.frag is not None or pk.frag16 is not None)):
+                return 0
+            P = self._buf(f"sskip.P.{x2_bmod}x{H}x{W}x{co}", (x2_bmod, H, W, co))
+            shared, rest = self._skip_kw(pk, a16, kw, seam, x2_bmod, kw["ws"], res=P)
+            if not (ops.conv_igemm(None, pk.hi, pk.lo, P, query_rs=True, **shared) and ops.conv_igemm(None, pk.hi, pk.lo, h, query_rs=True, **rest) and
+                    (self.cfg_shared_skip or self._shared_skip_rule(Bd, H, W, co, C, seam))):
+                return 0
+            # a two-way K split of the shared launch (asked with the workspace the plain form would use): partials as res / res2
+            two = (self.cfg_skip_partials is True and kw["ws"] is not None and
+                   ops.conv_igemm(None, pk.hi, pk.lo, P, partials=True, query_rs=True, **shared) == 2)
+            if two:
+                P2 = self._buf(f"sskip.P2.{x2_bmod}x{H}x{W}x{co}", (2, x2_bmod, H, W, co))
+                shared, rest = self._skip_kw(pk, a16, kw, seam, x2_bmod, P2.view(-1), res=P2[0], res2=P2[1])
+                two = (ops.conv_igemm(None, pk.hi, pk.lo, P, partials=True, query_rs=True, **shared) == 2 and
+                       bool(ops.conv_igemm(None, pk.hi, pk.lo, h, query_rs=True, **rest)))
+            self._consts[("sskip2",) + key[1:]] = bool(two)
+            return seam
+        seam = self._asked(key, ask)
+        if not seam:
             return None
-        P2 = self._buf(f"sskip.P2.{x2_bmod}x{H}x{W}x{co}", (2, x2_bmod, H, W, co)) if self._consts.get(("sskip2",) + key[1:]) else None
-        return hit, self._buf(f"sskip.P.{x2_bmod}x{H}x{W}x{co}", (x2_bmod, H, W, co)), P2
+        P2 = self._buf(f"sskip.P2.{x2_bmod}x{H}x{W}x{co}", (2, x2_bmod, H, W, co)) if self._consts[("sskip2",) + key[1:]] else None
+        return seam, self._buf(f"sskip.P.{x2_bmod}x{H}x{W}x{co}", (x2_bmod, H, W, co)), P2
 
     @staticmethod
     def _shared_skip_rule(Bd: int, H: int, W: int, co: int, C: int, seam: int) -> bool:
@@ -975,16 +937,14 @@ class UNetModel(nn.Module):
         pk, pk2 = self._packed[id(rb.in_layers[2])], self._packed[id(rb.out_layers[3])]
         h = self._buf(f"h.{Bd}x{H}x{W}x{co}", (Bd, H, W, co))
         out = self._buf(tag + ".out", (Bd, H, W, co))
-        gn2 = rb.out_layers[0]
         h16 = self._planes(Bd, H, W, co, "g16")
         gnn = npl = coop2 = None
         if next_norm is not None and not os.environ.get("STEDM_NO_NEXT_GN"):
-            nn_, nact = next_norm
             npl = self._planes(Bd, H, W, co)
-            gnn = (nn_.weight, nn_.bias, nn_.eps, nn_.num_groups, nact, npl[0], None, False)
+            gnn = self._gn_next(*next_norm, npl, None, False)
             coop2 = self._coop_for(tag + ".c2", Bd, H, W, co, prec)
         part = dict(prec=prec, w_frag=pk.frag, w_frag16=pk.frag16, ws=self._front_ws(B * H * W * co), partials=True)
-        fin = dict(prec=prec, ws_bmod=B, bias=pk.bias, gn_next=(gn2.weight, gn2.bias, gn2.eps, gn2.num_groups, 1, h16[0], None, True))
+        fin = dict(prec=prec, ws_bmod=B, bias=pk.bias, gn_next=self._gn_next(rb.out_layers[0], 1, h16, None, True))
         tail = dict(prec=prec, src16=h16, bias=pk2.bias, res=x1, res_bmod=B, w_frag=pk2.frag, ws=self._splitk_ws_res(Bd * H * W * co), w_frag16=pk2.frag16,
                     gn_next=gnn, coop=coop2)
         return pk, pk2, h, out, npl, part, fin, tail
@@ -1000,17 +960,16 @@ class UNetModel(nn.Module):
             #  dropout: the finish pass writes out_layers' planes without the mask)
             return False
         key = ("sfront", id(rb), 2 * B, H, W, self.cfg_shared_front)
-        hit = self._consts.get(key)
-        if hit is None:
-            hit = 0
+
+        def ask():
             pk, pk2, h, out, npl, part, fin, tail = self._front_kw(tag, rb, self._buf("mid.a.0.out", x1shape), next_norm)      # (the shared tensor's own buffer)
             if (pk.frag is not None or pk.frag16 is not None) and C % 4 == 0 and (self.cfg_shared_front or self._shared_front_rule(2 * B, H, W, C)):
                 a16 = self._planes(B, H, W, C)
                 n = ops.conv_igemm(None, pk.hi, pk.lo, self._buf(f"h.{B}x{H}x{W}x{C}", (B, H, W, C)), src16=a16, query_rs=True, **part)
                 if n and ops.conv_igemm(None, pk2.hi, pk2.lo, out, chan_stats=self._cs_new(out), query_rs=True, **tail):
-                    hit = int(n)
-            self._consts[key] = hit
-        return bool(hit)
+                    return int(n)
+            return 0
+        return bool(self._asked(key, ask))
 
     @staticmethod
     def _shared_front_rule(Bd: int, H: int, W: int, co: int) -> bool:
@@ -1131,12 +1090,7 @@ class UNetModel(nn.Module):
             ncat = layer.out_channels + next_skip_c
             rawn = self._cat_plane(B, 2 * H, 2 * W, layer.out_channels, ncat)
             kwc = dict(kwu, out16=(rawn, None), out16_stride=ncat, cout=layer.out_channels)
-            keyc = ("upcat", id(layer), B, H, W, ncat)
-            okc = self._consts.get(keyc)
-            if okc is None:
-                okc = bool(ops.conv_igemm(None, pu.hi, pu.lo, None, query_rs=True, **kwc))
-                self._consts[keyc] = okc
-            if okc:
+            if self._asked(("upcat", id(layer), B, H, W, ncat), lambda: bool(ops.conv_igemm(None, pu.hi, pu.lo, None, query_rs=True, **kwc))):
                 ops.conv_igemm(None, pu.hi, pu.lo, None, **kwc)
                 self._x16[out.data_ptr()] = (rawn, layer.out_channels)
                 return out
