@@ -61,9 +61,10 @@ def clip_steps_max_norm(shapes: Sequence[tuple]) -> float:
     return 0.03 * math.sqrt(n)
 
 
-def clipped_adamw_reference(params0: Sequence[torch.Tensor], dtype=torch.float32, lr: float = 1e-3, weight_decay: float = 0.01, steps: int = 3):
+def clipped_adamw_reference(params0: Sequence[torch.Tensor], dtype=torch.float32, lr: float = 1e-3, weight_decay: float = 0.01, steps: int = 3,
+                            with_moments: bool = False):
     """Three steps of clip_grad_norm_ (on CPU tensors of `dtype`) + oracle AdamW + oracle EMA from the parameters params0, on the gradients of
-    clip_step_grads. -> (parameters, EMA shadows, the norms clip_grad_norm_ returned)"""
+    clip_step_grads. -> (parameters, EMA shadows, the norms clip_grad_norm_ returned); with_moments: + (AdamW's m, AdamW's v)"""
     from oracle import train as otrain
     shapes = [tuple(p.shape) for p in params0]
     mx = clip_steps_max_norm(shapes)
@@ -81,15 +82,24 @@ def clipped_adamw_reference(params0: Sequence[torch.Tensor], dtype=torch.float32
         for i, h in enumerate(holders):
             otrain.adamw_step(p[i], h.grad, m[i], v[i], step, lr, weight_decay=weight_decay)
             otrain.ema_update(e[i], p[i], d)
-    return p, e, norms
+    return (p, e, norms, m, v) if with_moments else (p, e, norms)
 
 
 @functools.lru_cache(maxsize=None)
-def tiny_unet_clip_reference(dtype_name: str = "float32"):
-    """clipped_adamw_reference for the TINY U-Net of tests/test_gpu_train.py filled from seed 6, in module.parameters() order; computed
-    once per process and shared (callers must not modify it)."""
+def _tiny_unet_clip_reference(dtype_name: str):
     from stedm_amd.unet import UNetModel
     from stedm_amd.utils import prng
     m = UNetModel(precision="parity", **TINY).eval()
     prng.fill_module_(m, seed=6)
-    return clipped_adamw_reference([q for q in m.parameters()], getattr(torch, dtype_name))
+    return clipped_adamw_reference([q for q in m.parameters()], getattr(torch, dtype_name), with_moments=True)
+
+
+def tiny_unet_clip_reference(dtype_name: str = "float32"):
+    """clipped_adamw_reference for the TINY U-Net of tests/test_gpu_train.py filled from seed 6, in module.parameters() order; computed
+    once per process and shared (callers must not modify it)."""
+    return _tiny_unet_clip_reference(dtype_name)[:3]
+
+
+def tiny_unet_clip_moments(dtype_name: str = "float32"):
+    """(m, v) of the same three steps (same computation, same cache)"""
+    return _tiny_unet_clip_reference(dtype_name)[3:]

@@ -184,6 +184,11 @@ def test_clipped_adamw_steps_vs_torch_clip_and_oracle(dev):
     ema = {id(p): e for p, e in zip(tr._opt["params"], tr.ema_parameters())}
     for i, p in enumerate(params):
         assert torch.allclose(ema[id(p)].cpu(), ref_e[i], rtol=2e-6, atol=2e-7), i
+    ref_m, ref_v = refs_clip.tiny_unet_clip_moments("float32")          # the moments, at the same tolerances
+    mom = {id(p): mv for p, mv in zip(tr._opt["params"], zip(tr._opt["m"], tr._opt["v"]))}
+    for i, p in enumerate(params):
+        assert torch.allclose(mom[id(p)][0].cpu(), ref_m[i], rtol=2e-6, atol=2e-7), i
+        assert torch.allclose(mom[id(p)][1].cpu(), ref_v[i], rtol=2e-6, atol=2e-7), i
 
 
 def test_norm_under_gradient_accumulation_is_that_of_the_mean_gradient(dev):

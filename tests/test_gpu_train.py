@@ -134,6 +134,10 @@ def test_adamw_ema_step_vs_oracle(dev):
     ema = {id(p): e for p, e in zip(tr._opt["params"], tr.ema_parameters())}
     for i, p in enumerate(params):
         assert torch.allclose(ema[id(p)].cpu(), ref_e[i], rtol=2e-6, atol=2e-7), i
+    mom = {id(p): mv for p, mv in zip(tr._opt["params"], zip(tr._opt["m"], tr._opt["v"]))}          # the moments, at the same tolerances
+    for i, p in enumerate(params):
+        assert torch.allclose(mom[id(p)][0].cpu(), ref_m[i], rtol=2e-6, atol=2e-7), i
+        assert torch.allclose(mom[id(p)][1].cpu(), ref_v[i], rtol=2e-6, atol=2e-7), i
 
 
 def test_train_steps_reduce_the_loss(dev):
@@ -153,7 +157,9 @@ def test_optimizer_writes_the_weight_packs_itself(dev, precision):
     """stedm_adamw_ema_pack: AdamW + EMA over the convolution weights that also refreshes their fragment-order packs (forward order and the
     flipped / transposed dgrad order, 32x32x16 and 16x16x32 forms). Against the separate launches (AdamW, then stedm_pack_frag_multi before the
     next forward / backward) on the same model and batch: losses of four steps, parameters, EMA shadows and every pack bit for bit; in-place
-    edits of a weight between two steps still re-pack it (the freshness mark follows the parameters' versions and UNetModel.invalidate())."""
+    edits of a weight between two steps still re-pack it (the freshness mark follows the parameters' versions and UNetModel.invalidate()).
+    This is self-consistency on one model; the kernel's pack words against the layout references of tests/refs_pack.py, its descriptor
+    search, 1 / 2 / 4 outputs and rows beyond cout are held in tests/test_gpu_opt_exact.py."""
     from stedm_amd.train import UNetTrainer
     cfg = dict(image_size=16, in_channels=7, model_channels=64, out_channels=4, num_res_blocks=1, attention_resolutions=[32, 16, 8], channel_mult=[1, 4, 8],
                num_heads=4)
