@@ -1,6 +1,6 @@
 // GroupNorm statistics from channel partials, stated once: the {sum, sumsq} -> {mean, rstd} formula, the block fold of the partials
 // of a virtual concat [x1 | x2] with its summation order, the per-channel table of the 8-wide apply kernels with the fp16 guard's
-// switch for the normalised planes, the FiLM modulation of scale-shift-norm blocks (gn_film) and the 16-bit hi / lo split. gn.hip (the apply kernels), bwd.hip (gn_fold_kernel) and the
+// switch for the normalised planes, the FiLM modulation of scale-shift-norm blocks (gn_film) and the 16-bit hi / lo split. gn.hip (the apply kernels), gn_bwd.hip (gn_fold_kernel) and the
 // convolution epilogues that normalise their own output (conv_io.hip, conv_rs.inc) must agree bit for bit; they do so by calling this.
 #pragma once
 #include "common.hpp"

@@ -1,6 +1,6 @@
 // The 16-bit weight layouts the convolution kernels read, stated once: the two MFMA fragment orders, the sub-pixel tap fold, the
 // space-to-depth tap map and the hi / lo split. Index arithmetic and one rounding; no kernels. Writers: pack.hip (stedm_pack_*) and the
-// optimizer pass of bwd.hip (adamw_ema_pack_kernel). Plain torch restatement: tests/refs_pack.py.
+// optimizer pass of opt.hip (adamw_ema_pack_kernel). Plain torch restatement: tests/refs_pack.py.
 #pragma once
 #include "common.hpp"
 

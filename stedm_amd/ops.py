@@ -1521,6 +1521,19 @@ def gn_bwd_ws_floats(B: int, HW: int, C: int, groups: int) -> int:
     return lib().stedm_gn_bwd_ws_floats(B, HW, C, groups)
 
 
+def _gn_bwd_film_args(B: int, C: int, dx16, film=None, film_off: int = 0, film_bstride: int = 0, d_film=None, d_film_off: int = 0):
+    """C arguments the gn_bwd* calls share: the (dx16_hi, dx16_lo) pointer pair and, with `film`, the checked (film, film_bstride, film_off)
+    and (d_film, its row stride, d_film_off) triples (None without)."""
+    d16 = (None if dx16 is None else dx16[0].data_ptr(), None if dx16 is None else _ptr(dx16[1]))
+    if film is None:
+        return d16, None, None
+    _chk(film, name="film")
+    assert film_off >= 0 and film.numel() >= (B - 1) * film_bstride + film_off + 2 * C, "film rows out of range"
+    assert d_film.dtype == torch.float32 and d_film.dim() == 2 and d_film.shape[0] == B and d_film.stride(1) == 1
+    assert 0 <= d_film_off and d_film_off + 2 * C <= d_film.shape[1], "d_film columns out of range"
+    return d16, (film.data_ptr(), int(film_bstride), int(film_off)), (d_film.data_ptr(), d_film.stride(0), int(d_film_off))
+
+
 def gn_bwd(x1, x2, mean_rstd, gamma, beta, groups: int, act: int, dA, add, ws, dx1, acc1: bool, dx2, acc2: bool, dx16, prec: Precision,
            dgamma, dbeta, acc_param: bool) -> None:
     """Backward of act(GroupNorm([x1|x2])): see stedm_gn_bwd."""
@@ -1539,18 +1552,14 @@ def gn_bwd_film(x1, mean_rstd, gamma, beta, groups: int, act: int, film, film_of
                 prec: Precision, dgamma, dbeta, acc_param: bool, d_film, d_film_off: int) -> None:
     """Backward of act(GroupNorm(x1) * (1 + scale) + shift): see stedm_gn_bwd_film. d_film [B, N]: row b receives dscale | dshift at
     columns [d_film_off, d_film_off + 2 C); its row stride may exceed N (a column block of a wider matrix)."""
-    _chk(x1, name="x1"); _chk(dA, name="dA"); _chk(film, name="film")
+    _chk(x1, name="x1"); _chk(dA, name="dA")
     B, C = x1.shape[0], x1.shape[-1]
     HW = x1.numel() // (B * C)
     assert dA.numel() == B * HW * C and ws.numel() >= gn_bwd_ws_floats(B, HW, C, groups)
-    assert film_off >= 0 and film.numel() >= (B - 1) * film_bstride + film_off + 2 * C, "film rows out of range"
-    assert d_film.dtype == torch.float32 and d_film.dim() == 2 and d_film.shape[0] == B and d_film.stride(1) == 1
-    assert 0 <= d_film_off and d_film_off + 2 * C <= d_film.shape[1], "d_film columns out of range"
-    check(lib().stedm_gn_bwd_film(x1.data_ptr(), C, mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, act, film.data_ptr(),
-                                  int(film_bstride), int(film_off), dA.data_ptr(), _ptr(add), B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1),
-                                  None if dx16 is None else dx16[0].data_ptr(), None if dx16 is None else _ptr(dx16[1]), prec.mm_dtype,
-                                  dgamma.data_ptr(), dbeta.data_ptr(), int(acc_param), d_film.data_ptr(), d_film.stride(0), int(d_film_off),
-                                  _stream()), "stedm_gn_bwd_film")
+    d16, fl, dfl = _gn_bwd_film_args(B, C, dx16, film, film_off, film_bstride, d_film, d_film_off)
+    check(lib().stedm_gn_bwd_film(x1.data_ptr(), C, mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, act, *fl, dA.data_ptr(), _ptr(add),
+                                  B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1), *d16, prec.mm_dtype, dgamma.data_ptr(), dbeta.data_ptr(),
+                                  int(acc_param), *dfl, _stream()), "stedm_gn_bwd_film")
 
 
 def gn_bwd_drop(x1, mean_rstd, gamma, beta, groups: int, act: int, dA, add, ws, dx1, acc1: bool, dx16, prec: Precision, dgamma, dbeta,
@@ -1561,20 +1570,15 @@ def gn_bwd_drop(x1, mean_rstd, gamma, beta, groups: int, act: int, dA, add, ws, 
     B, C = x1.shape[0], x1.shape[-1]
     HW = x1.numel() // (B * C)
     assert dA.numel() == B * HW * C and ws.numel() >= gn_bwd_ws_floats(B, HW, C, groups)
-    d16 = (None if dx16 is None else dx16[0].data_ptr(), None if dx16 is None else _ptr(dx16[1]))
+    d16, fl, dfl = _gn_bwd_film_args(B, C, dx16, film, film_off, film_bstride, d_film, d_film_off)
     if film is None:
         check(lib().stedm_gn_bwd_drop(x1.data_ptr(), C, None, 0, mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, act, dA.data_ptr(),
                                       _ptr(add), B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1), None, 0, *d16, prec.mm_dtype, dgamma.data_ptr(),
                                       dbeta.data_ptr(), int(acc_param), *_drop_tail(drop), _stream()), "stedm_gn_bwd_drop")
         return
-    _chk(film, name="film")
-    assert film_off >= 0 and film.numel() >= (B - 1) * film_bstride + film_off + 2 * C, "film rows out of range"
-    assert d_film.dtype == torch.float32 and d_film.dim() == 2 and d_film.shape[0] == B and d_film.stride(1) == 1
-    assert 0 <= d_film_off and d_film_off + 2 * C <= d_film.shape[1], "d_film columns out of range"
-    check(lib().stedm_gn_bwd_film_drop(x1.data_ptr(), C, mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, act, film.data_ptr(),
-                                       int(film_bstride), int(film_off), dA.data_ptr(), _ptr(add), B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1),
-                                       *d16, prec.mm_dtype, dgamma.data_ptr(), dbeta.data_ptr(), int(acc_param), d_film.data_ptr(), d_film.stride(0),
-                                       int(d_film_off), *_drop_tail(drop), _stream()), "stedm_gn_bwd_film_drop")
+    check(lib().stedm_gn_bwd_film_drop(x1.data_ptr(), C, mean_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, act, *fl, dA.data_ptr(), _ptr(add),
+                                       B, HW, ws.data_ptr(), dx1.data_ptr(), int(acc1), *d16, prec.mm_dtype, dgamma.data_ptr(), dbeta.data_ptr(),
+                                       int(acc_param), *dfl, *_drop_tail(drop), _stream()), "stedm_gn_bwd_film_drop")
 
 
 def im2col_t16(src16: torch.Tensor, dst16: torch.Tensor, ks: int, mode: int) -> None:

@@ -11,7 +11,8 @@ The backward is a reverse walk over the tape `UNetModel._forward_impl` records i
     operands from the NHWC planes, transposed in the LDS reads, all nine taps from one LDS image); other shapes: one GEMM
     dW[(tap,ci)][co] = sum_p col[(tap,ci)][p] dY^T[co][p] on the forward's kernels over transposed im2col planes (stedm_im2col_t16),
     K = B*H*W split over blocks by the register-streamed kernel's split-K, in batch chunks beyond 65 536;
-  * GroupNorm+SiLU, attention, embeddings, reductions: fp32 kernels of csrc/bwd.hip;
+  * GroupNorm+SiLU (csrc/gn_bwd.hip), attention (csrc/attn_bwd.hip), embeddings, reductions and the loss (csrc/bwd.hip), gradient norm and
+    AdamW + EMA (csrc/opt.hip): fp32 kernels;
   * 16-bit operands of the backward contractions are bf16 (fp32 exponent range: no loss scaling), single product or
     hi/lo 3-product following the forward's mode; normalised operand planes are kept by a bf16 forward, recomputed from the saved
     fp32 tensors otherwise.
@@ -1303,7 +1304,7 @@ class UNetTrainer:
 
     def _sched_rows(self, first_step: int, first_ema: int, n: int, with_valid: bool = False):
         """{1 - beta1^s, sqrtf(1 - beta2^s), LitEma decay, lr} for steps first_step .. first_step + n - 1 with the arithmetic of stedm_adamw_ema
-        (bwd.hip: betas arrive as C floats, the powers are taken in double) and of _next_ema_decay — a replayed step uses the very scalars the
+        (opt.hip: betas arrive as C floats, the powers are taken in double) and of _next_ema_decay — a replayed step uses the very scalars the
         eager step would have been launched with. The lr column: _lr_rows (with_valid: also its count of usable rows)."""
         import numpy as np
         lrs, valid = self._lr_rows(first_step, n)

@@ -1,4 +1,4 @@
-"""Plain torch restatements of the training step's helper kernels (stedm_amd/csrc/bwd.hip), written from the formulas in the kernel
+"""Plain torch restatements of the training step's helper kernels (stedm_amd/csrc/bwd.hip; the SiLU arithmetic is silu_bwd.hpp), written from the formulas in the kernel
 comments and the docstrings of stedm_amd/ops.py. Every function runs in the dtype and on the device of its inputs: the tests feed
 fp64 for a reference, fp32 to pin a reference's own rounding against its bound. Shared by tests/test_bwd_refs_cpu.py (pins these
 functions against torch autograd), tests/test_gpu_bwd_kernels.py (pins the kernels against these functions) and

@@ -1,4 +1,4 @@
-"""Plain torch restatements of the GroupNorm family (stedm_amd/csrc/gn.hip, gn_fold / gn_bwd in bwd.hip), their derived per-element error
+"""Plain torch restatements of the GroupNorm family (stedm_amd/csrc/gn.hip, gn_fold / gn_bwd in gn_bwd.hip), their derived per-element error
 bounds, inputs whose outputs are known bit for bit, and fp32 emulations of the kernels with switchable defects. No GPU. Shared by
 tests/test_gn_refs_cpu.py (pins the references against torch, holds the honest emulations inside both tiers and every seeded defect
 outside one) and tests/test_gpu_gn_exact.py (holds the kernels to the same two tiers).

@@ -1,5 +1,5 @@
 """Plain torch restatements of the FiLM (use_scale_shift_norm) GroupNorm kernels - stedm_gn_apply16c_film (gn.hip: the FILM instantiation
-of gn_apply16c_v8_kernel, arithmetic in gn_fold.hpp: gn_film / gn_build_table_film) and stedm_gn_bwd_film (bwd.hip) - with their
+of gn_apply16c_v8_kernel, arithmetic in gn_fold.hpp: gn_film / gn_build_table_film) and stedm_gn_bwd_film (gn_bwd.hip) - with their
 derived per-element bounds, exact inputs and fp32 emulations with switchable defects. No GPU. Builds on tests/refs_gn.py (same
 conventions: tensors flattened to [B, HW, C], u = 2^-24, gamma_k, u_T). Shared by tests/test_gn_film_refs_cpu.py and
 tests/test_gpu_gn_film.py.

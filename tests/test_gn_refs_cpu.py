@@ -72,7 +72,7 @@ def test_chan_partials_slot_rule():
 def test_geometry_names_every_form():
     """the cases reach the forms their names say, by refs_gn's RESTATEMENT of the launch rules (apply16c_geometry: gn_apply16c_launch;
     gn_bwd_fused_cb, chan_stats_qbs: their namesakes). It pins the cases to the rules as written today, not to the library: whoever changes
-    a launch heuristic in gn.hip / bwd.hip restates it there, and this test then shows which cases moved to another instantiation."""
+    a launch heuristic in gn.hip / gn_bwd.hip restates it there, and this test then shows which cases moved to another instantiation."""
     got = {c[0]: R.apply16c_geometry(c[1], c[2] * c[3], c[4], c[5], c[7], c[8] == "hilo", c[8] == "x16") for c in R.FWD}
     assert all(got[n][0] == "quad" for n in got if n.startswith("quad"))
     assert got["quad_two_passes"] == ("quad", 2, 0, False) and 1024 < 2 * (1540 + 1536) // 4 < 2048      # quads of a block: two passes of 1024

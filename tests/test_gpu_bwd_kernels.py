@@ -1,4 +1,4 @@
-"""GPU tier (-m gpu): the helper kernels of the training step (stedm_amd/csrc/bwd.hip, and sum_planes of wgrad.hip), each called through
+"""GPU tier (-m gpu): the helper kernels of the training step (stedm_amd/csrc/bwd.hip with silu_bwd.hpp, and sum_planes of wgrad.hip), each called through
 its `ops` wrapper and held against the plain references of tests/refs_bwd.py at the shapes where such kernels go wrong: tails, partial
 tiles, odd leading dimensions, unaligned views, more than one trip of a grid-stride loop, accumulate on and off.
 

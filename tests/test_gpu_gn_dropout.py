@@ -8,7 +8,9 @@ partial iteration only, one full iteration plus a partial one, hi + lo planes, a
 refs_gn.apply16c_geometry).
 Backward. stedm_gn_bwd_drop(dA) equals stedm_gn_bwd(dA_eff) bit for bit, dA_eff = keep ? dA * inv_keep : 0 formed by torch as one fp32
 multiply; and it stays within the plain backward's bounds of the fp64 closed form on dA_eff. One shape per kernel selection (one-pass,
-three-kernel chain). Every output buffer starts as NaN / FILL16 and must be fully written."""
+three-kernel chain). Every output buffer starts as NaN / FILL16 and must be fully written.
+Argument errors of the backward FiLM and dropout entries (gn_bwd.hip: one shared check under the entry's name), and p = 0 forwarding to the
+plain / FiLM entries bit for bit: test_backward_argument_errors."""
 import numpy as np
 import pytest
 import torch
@@ -267,3 +269,63 @@ def test_argument_errors(dev):
     assert call(raw=hi.data_ptr()) != 0, "raw planes must be an argument error"
     assert call(c=36) != 0, "C % 8 != 0 must be an argument error"
     torch.cuda.synchronize()
+
+
+def test_backward_argument_errors(dev):
+    """The C entries stedm_gn_bwd_film / _drop / _film_drop: a valid call returns 0, every bad argument set below is refused on the host
+    before any launch, and with p = 0 the drop entries are the plain / FiLM entries bit for bit."""
+    from stedm_amd import _lib, ops
+    L = _lib.lib()
+    B, H, W, C, groups = 2, 4, 4, 32, 8
+    x = RG.normal((B, H * W, C), 0, "drop.bwdargs.x", std=1.5, mean=0.3).to(dev)
+    dA = RG.normal((B, H * W, C), 0, "drop.bwdargs.dA").to(dev)
+    gm, bt = RG.normal((C,), 0, "drop.bwdargs.g", std=0.5, mean=1.0).to(dev), RG.normal((C,), 0, "drop.bwdargs.b", std=0.5).to(dev)
+    film = RG.normal((B, 2 * C), 0, "drop.bwdargs.film", std=0.5).to(dev)
+    xg = x.view(B, H * W, groups, C // groups).double()
+    mean, var = xg.mean((1, 3)), xg.var((1, 3), unbiased=False)
+    mr = torch.stack((mean, (var + EPS).rsqrt()), -1).float().contiguous()
+    ws = torch.zeros((ops.gn_bwd_ws_floats(B, H * W, C, groups),), device=dev)
+    drop_tail = lambda p: (p, SEED, RD.SITE0 + K, STEP, None)
+
+    def outs():
+        return dict(dx=torch.full((B, H * W, C), float("nan"), device=dev), hi=torch.full((B, H * W, C), FILL16, dtype=torch.int16, device=dev),
+                    dg=torch.full((C,), float("nan"), device=dev), db=torch.full((C,), float("nan"), device=dev),
+                    dE=torch.full((B, 2 * C), float("nan"), device=dev))
+
+    def plain(o):
+        return L.stedm_gn_bwd(x.data_ptr(), C, None, 0, mr.data_ptr(), gm.data_ptr(), bt.data_ptr(), groups, 1, dA.data_ptr(), None, B, H * W,
+                              ws.data_ptr(), o["dx"].data_ptr(), 0, None, 0, o["hi"].data_ptr(), None, _lib.BF16, o["dg"].data_ptr(),
+                              o["db"].data_ptr(), 0, None)
+
+    def film_call(o, entry="stedm_gn_bwd_film", film_ptr=film.data_ptr(), film_off=0, d_bs=2 * C, tail=()):
+        return getattr(L, entry)(x.data_ptr(), C, mr.data_ptr(), gm.data_ptr(), bt.data_ptr(), groups, 1, film_ptr, 2 * C, film_off, dA.data_ptr(), None,
+                                 B, H * W, ws.data_ptr(), o["dx"].data_ptr(), 0, o["hi"].data_ptr(), None, _lib.BF16, o["dg"].data_ptr(),
+                                 o["db"].data_ptr(), 0, o["dE"].data_ptr(), d_bs, 0, *tail, None)
+
+    def drop_call(o, p=0.1, x2=None, c=C):
+        return L.stedm_gn_bwd_drop(x.data_ptr(), c, x2, 0, mr.data_ptr(), gm.data_ptr(), bt.data_ptr(), groups, 1, dA.data_ptr(), None, B, H * W,
+                                   ws.data_ptr(), o["dx"].data_ptr(), 0, None, 0, o["hi"].data_ptr(), None, _lib.BF16, o["dg"].data_ptr(),
+                                   o["db"].data_ptr(), 0, *drop_tail(p), None)
+
+    o = outs()
+    assert film_call(o) == 0
+    assert drop_call(o) == 0
+    assert film_call(o, entry="stedm_gn_bwd_film_drop", tail=drop_tail(0.1)) == 0
+    assert film_call(o, film_ptr=None) != 0, "gn_bwd_film: a null film must be an argument error"
+    assert film_call(o, film_off=2) != 0, "gn_bwd_film: film_off must be a multiple of 4"
+    assert film_call(o, d_bs=2 * C - 1) != 0, "gn_bwd_film: a d_film row shorter than d_film_off + 2 C must be an argument error"
+    assert drop_call(o, x2=x.data_ptr()) != 0, "gn_bwd_drop: x2 != NULL must be an argument error"
+    assert drop_call(o, p=1.0) != 0 and drop_call(o, p=-0.1) != 0, "gn_bwd_drop: p outside [0, 1) must be an argument error"
+    assert drop_call(o, c=36) != 0, "gn_bwd_drop: C % 8 != 0 must be an argument error"
+    assert film_call(o, entry="stedm_gn_bwd_film_drop", film_ptr=None, tail=drop_tail(0.1)) != 0, "gn_bwd_film_drop: a null film must be an argument error"
+    # p = 0: the drop entries forward to the plain / FiLM entries
+    a, b = outs(), outs()
+    assert plain(a) == 0 and drop_call(b, p=0.0) == 0
+    torch.cuda.synchronize()
+    for k in ("dx", "hi", "dg", "db"):
+        assert not bool(torch.isnan(a[k].float()).any()) and torch.equal(a[k], b[k]), f"gn_bwd_drop(p=0) {k} differs from gn_bwd"
+    a, b = outs(), outs()
+    assert film_call(a) == 0 and film_call(b, entry="stedm_gn_bwd_film_drop", tail=drop_tail(0.0)) == 0
+    torch.cuda.synchronize()
+    for k in ("dx", "hi", "dg", "db", "dE"):
+        assert not bool(torch.isnan(a[k].float()).any()) and torch.equal(a[k], b[k]), f"gn_bwd_film_drop(p=0) {k} differs from gn_bwd_film"

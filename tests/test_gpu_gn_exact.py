@@ -1,4 +1,4 @@
-"""GPU tier (-m gpu): the GroupNorm kernels (stedm_amd/csrc/gn.hip, gn_fold / gn_bwd in bwd.hip) against tests/refs_gn.py, in two tiers.
+"""GPU tier (-m gpu): the GroupNorm kernels (stedm_amd/csrc/gn.hip, gn_fold / gn_bwd in gn_bwd.hip) against tests/refs_gn.py, in two tiers.
 
   exact   inputs m_g +- a_g (refs_gn.exact_pattern; 'A' alternating signs, 'B' a fixed shuffle with m_g distinct per sample), eps = 0,
           dyadic gamma / beta, act = 0: the fp32 partials, {mean, rstd} and every plane word are known bit for bit - torch.equal on the
@@ -11,7 +11,7 @@ its words. tests/test_gn_refs_cpu.py holds fp32 emulations of the kernels to the
 
 Kernel instantiation -> case. The branch rules are RESTATED in Python (refs_gn.apply16c_geometry / gn_bwd_fused_cb / chan_stats_qbs) and the
 mapping is asserted against that restatement on the CPU tier (test_geometry_names_every_form), as the guard tests do: a change of a launch
-heuristic in gn.hip / bwd.hip has to be restated there, or cases silently move to other instantiations. Every stedm_gn_apply16c case runs
+heuristic in gn.hip / gn_bwd.hip has to be restated there, or cases silently move to other instantiations. Every stedm_gn_apply16c case runs
 single-product and hi + lo in both tiers (refs_gn.forms; both modes of an 8-wide shape run in the quad-pair kernel):
 
   gn_scale_shift_kernel<true>                cpg, c1, c2 multiples of 4                      test_scale_shift[vec4*]

@@ -1,5 +1,5 @@
 """GPU tier (-m gpu): the optimizer kernels called by name, no trainer and no U-Net. adamw_ema_kernel, adamw_ema_pack_kernel and
-ema_update_kernel (stedm_amd/csrc/bwd.hip) through all eleven entry points, on pointer tables built here the way UNetTrainer._build_opt,
+ema_update_kernel (stedm_amd/csrc/opt.hip) through all eleven entry points, on pointer tables built here the way UNetTrainer._build_opt,
 _chunks and _fused_opt build them.
 
 What each output is held to (tests/refs_opt.py, pinned on the CPU by tests/test_opt_refs_cpu.py):
