@@ -642,6 +642,33 @@ int stedm_gn_bwd_film_drop(const float* x1, int c1, const float* mean_rstd, cons
 int stedm_svit_head(const float* x, int B, int T, int dim, int pool, const float* c_old, const float* ln_w,
                     const float* ln_b, float eps, const float* wt, const float* bias, float* out, int ncls, float* ws, long ws_floats,
                     void* stream);
+/* ---- backward of the set-ViT style encoder (added within ABI 31, whose number tests/test_attn_order_cpu.py pins: additions only, no existing entry changes; svit_bwd.hip) — fp32, no atomics, every reduction in a fixed order.
+ * stedm_lsa_bwd: LSA.forward (vit_set.py:52-66) reversed, flash-style, from the planes stedm_qkv_pack wrote (q scaled by
+ * qscale = exp(temperature) * log2 e; lo planes NULL: hi only) and d_out [B*T][heads*64]. Writes d_qkv [B*T][3*heads*64] in to_qkv's output
+ * order (the gradient with respect to the UNSCALED q) and d_temp[0] (+)= sum dS o dots. p, seed, site: the forward's probability dropout
+ * (stedm_lsa_flash_drop), the keep bits regenerated from the counters; p == 0: none. ws: stedm_lsa_bwd_ws_floats floats
+ * (the rows' log-sum-exp as its two parts, maximum and 1 / sum, [B*heads][Tp] each | D [B*heads][Tp] | one fp64 d_temp partial per
+ * (sample-head, 64-query tile)), 16-byte aligned. Pad rows / columns >= T of the planes are not used. */
+long stedm_lsa_bwd_ws_floats(int B, int T, int Tp, int heads);
+int stedm_lsa_bwd(const void* q_hi, const void* q_lo, const void* k_hi, const void* k_lo, const void* vt_hi, const void* vt_lo,
+                  const float* d_out, float* d_qkv, float* d_temp, int accumulate_temp, float qscale, int B, int T, int Tp, int heads,
+                  int mm_dtype, float p, unsigned long long seed, unsigned site, float* ws, void* stream);
+/* dpre = dh * gelu'(pre), exact erf GELU (FeedForward, vit_set.py:24-31); n elements. */
+int stedm_gelu_bwd(const float* pre, const float* dh, float* dpre, long n, void* stream);
+/* 16-bit operand planes -> fp32: out = hi (+ lo; NULL: none). The operands of the fp32 weight-gradient GEMMs. */
+int stedm_widen16(const void* hi, const void* lo, float* out, long n, int mm_dtype, void* stream);
+/* the fp32 patch rows [B*ntok][patch*patch*3*ns] that stedm_svit_patch_ln16 normalises (same gather). */
+int stedm_svit_patch_gather(const float* img, int B, int ns, int H, int W, int patch, float* rows, void* stream);
+/* stedm_svit_tok_place reversed: dx [B][ntok+2][dim] -> d_pos [ntok+2][dim] and d_cls [dim] (batch sums, ascending b; accumulate: added
+ * onto the tensors), d_tok [B*ntok][dim] (rows of tokens 2..). */
+int stedm_svit_tok_bwd(const float* dx, float* d_pos, float* d_cls, float* d_tok, int B, int ntok, int dim, int accumulate, void* stream);
+/* stedm_svit_head reversed (pool 0 mean / 1 cls, c_old NULL): d_out [B][ncls], x [B][T][dim] (the head's input), w [ncls][dim] (the Linear's
+ * own layout) -> dx [B][T][dim], and (+)= d_ln_w, d_ln_b [dim], d_w [ncls][dim], d_bias [ncls] (batch sums, ascending b).
+ * ws: stedm_svit_head_bwd_ws_floats floats. */
+long stedm_svit_head_bwd_ws_floats(int B, int dim);
+int stedm_svit_head_bwd(const float* x, int B, int T, int dim, int pool, const float* ln_w, const float* ln_b, float eps, const float* w,
+                        const float* d_out, int ncls, float* dx, float* d_ln_w, float* d_ln_b, float* d_w, float* d_bias, int accumulate,
+                        float* ws, void* stream);
 /* GEGLU attention.py:37-44: g [M][2*I] fp32 (value | gate) -> value * gelu_erf(gate) as 16-bit planes [M][I]. */
 int stedm_geglu16(const float* g, void* out_hi, void* out_lo, long M, int I, int mm_dtype, void* stream);
 /* Agg_Mean (mode 0) / Agg_Max (mode 1) over the set: feats [B*n][F] -> out [B][F]; agg_blocks.py:52,73. */

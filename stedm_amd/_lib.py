@@ -129,6 +129,14 @@ SIGNATURES = {
     "stedm_qkv_pack_mx8": (_I, [_P, _I, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "stedm_lsa_flash_mx8": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "stedm_svit_head": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _I, _P, C.c_long, _P]),
+    "stedm_lsa_bwd_ws_floats": (C.c_long, [_I, _I, _I, _I]),
+    "stedm_lsa_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _F, C.c_ulonglong, C.c_uint, _P, _P]),
+    "stedm_gelu_bwd": (_I, [_P, _P, _P, C.c_long, _P]),
+    "stedm_widen16": (_I, [_P, _P, _P, C.c_long, _I, _P]),
+    "stedm_svit_patch_gather": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "stedm_svit_tok_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "stedm_svit_head_bwd_ws_floats": (C.c_long, [_I, _I]),
+    "stedm_svit_head_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
     "stedm_ln_bwd_blocks": (_I, [C.c_long]),
     "stedm_ln_bwd": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, C.c_long, _I, _I, _P]),
     "stedm_geglu_bwd": (_I, [_P, _P, _P, C.c_long, _I, _P]),
@@ -230,7 +238,11 @@ def lib() -> C.CDLL:
         except OSError as e:  # pragma: no cover
             raise StedmHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError as e:       # (entries have been added within one ABI number: a stale build shows up here first)
+                raise StedmHipError(f"{LIB_PATH} does not export {name}: it is older than this binding; rebuild it with "
+                                    "`python -m stedm_amd.build`") from e
             fn.restype = res
             fn.argtypes = args
         if L.stedm_abi_version() != ABI_VERSION:

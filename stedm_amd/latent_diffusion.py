@@ -159,6 +159,7 @@ class _HipTrainingLoss(torch.autograd.Function):
             cs = ld.cond_stage_model
             if ld._cond_stage_in_optimizer() and ctx.cond_input is not None and hasattr(cs, "backward"):
                 cs.backward(ctx.cond_input, dx[:, ctx.nx:].contiguous())
+            ld._style_encoder_backward(dctx)
             tr.publish_grads(1.0, accumulate=had)
             tr._ema_pending = True
         dcc = dx[:, ctx.nx:].contiguous() if ctx.needs_input_grad[1] else None
@@ -361,7 +362,16 @@ class LatentDiffusion(nn.Module):
         """whether the trainer's extra parameters include the cond stage's (a learned logvar is one too, and needs no cond_input)"""
         tr = self.__dict__.get("_trainer")
         lv = self.logvar if self.learn_logvar else None
-        return tr is not None and any(p is not lv for p in tr.extra_params)
+        style = {id(p) for p in self._style_encoder_params()}
+        return tr is not None and any(p is not lv and id(p) not in style for p in tr.extra_params)
+
+    def _style_encoder_params(self) -> list:
+        """parameters of a trainable style encoder (S_ZSS_DM(train_style_encoder=True)); none here"""
+        return []
+
+    def _style_encoder_backward(self, dctx) -> None:
+        """hands dL/dc_crossattn to a trainable style encoder (S_ZSS_DM(train_style_encoder=True)); nothing here"""
+        return None
 
     def _grad_anchor(self, device) -> torch.Tensor:
         """a scalar that requires grad, so that the bridge node is part of the autograd graph (not a Parameter: it must stay out of
@@ -610,6 +620,9 @@ class LatentDiffusion(nn.Module):
             # ddpm.py:1370-1372 / ldm_diffusion.py:228-229: appended after the cond stage's; no EMA shadow (LitEma covers `model` only). Its
             # gradient is written by the loss kernel into its slot of the arena's tail: it accumulates and all-reduces with that bucket
             extra.append(self.logvar)
+        # a trainable style encoder (opt-in): after logvar, the position ldm_diffusion.py:230-231 gives `model.embedder`'s parameters; no EMA
+        # shadow either. Its gradients accumulate and all-reduce with the arena's tail, like the cond stage's
+        extra.extend(self._style_encoder_params())
         algorithm = str(gradient_clip_algorithm or "norm").lower()
         if algorithm != "norm":
             if algorithm == "value":
@@ -645,7 +658,8 @@ class LatentDiffusion(nn.Module):
         """p_losses (ddpm.py:1015-1048) followed by the backward pass autograd runs for the reference in training_step
         (ddpm.py:345-358): eps-parameterisation, the model's objective. Fills `.grad` of the U-Net's parameters (and of a learned logvar) and returns
         (loss, loss_dict, dL/dx_noisy over [x | c_concat], dL/dc_crossattn). With `cond_input` (the raw layout fed to the cond stage) the
-        SpatialRescaler's channel-mapper gradient is filled too; the style encoder's backward is not built."""
+        SpatialRescaler's channel-mapper gradient is filled too, and a trainable style encoder (S_ZSS_DM(train_style_encoder=True)) receives
+        dL/dc_crossattn."""
         tr = self._trainer_or_default()
         noise = torch.randn_like(x_start) if noise is None else noise
         x_noisy = self.q_sample(x_start, t, noise)
@@ -657,6 +671,7 @@ class LatentDiffusion(nn.Module):
         if cond_input is not None and hasattr(self.cond_stage_model, "backward"):
             # cond_stage_trainable (s_zss_dm.py:46-48): the layout conditioner's channel mapper receives the c_concat slice of dL/dx
             self.cond_stage_model.backward(cond_input, dx[:, x_noisy.shape[1]:].contiguous())
+        self._style_encoder_backward(dctx)
         return loss, self._loss_dict("train", loss, tr.last_loss_terms), dx, dctx
 
     def _split_cond(self, cond):
@@ -689,6 +704,13 @@ class LatentDiffusion(nn.Module):
         if cond_input is not None and hasattr(self.cond_stage_model, "backward"):
             nx = x_noisy.shape[1]
             after = lambda dx, dctx: self.cond_stage_model.backward(cond_input, dx[:, nx:].contiguous())
+        if self._style_encoder_params():
+            cond_after = after
+
+            def after(dx, dctx):
+                if cond_after is not None:
+                    cond_after(dx, dctx)
+                self._style_encoder_backward(dctx)
         if graph and after is None and not tr.extra_params and tr.accumulate_grad_batches == 1 and x_noisy.is_cuda:
             import torch.distributed as dist
             if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1):
@@ -872,10 +894,16 @@ class S_ZSS_DM(LatentDiffusion):
 
     `encoder` names the torchvision embedder of the mean/max/linear aggregators in the reference ("swin_v2_t", third-party,
     SURVEY.md §8c): the Swin-V2 family is built on the HIP kernels (stedm_amd/swin.py); any other embedder can be supplied as a module
-    through `embedder=`. `style_agg: svit` and `style_sampling: none` need no embedder."""
+    through `embedder=`. `style_agg: svit` and `style_sampling: none` need no embedder.
 
-    def __init__(self, encoder, sampling_cfg, agg_cfg, cfg, *args, embedder: Optional[nn.Module] = None, **kwargs):
+    train_style_encoder (default False: the reference as wired, whose optimizer never sees the aggregation block): with `style_agg: svit`
+    the set-ViT is trained with the U-Net — `get_input` in training mode keeps its forward, the training step hands it dL/dc_crossattn
+    (sViT.backward) and its parameters follow `logvar` in the optimizer. Any other aggregation block raises: only the sViT has a backward."""
+
+    def __init__(self, encoder, sampling_cfg, agg_cfg, cfg, *args, embedder: Optional[nn.Module] = None, train_style_encoder: bool = False,
+                 **kwargs):
         super().__init__(*args, **kwargs)
+        self.train_style_encoder = bool(train_style_encoder)
         from . import style as st
         self._sampling_cfg = sampling_cfg
         self._agg_cfg = agg_cfg
@@ -907,6 +935,17 @@ class S_ZSS_DM(LatentDiffusion):
                 raise Exception("Unkown aggregation function!")
             self._agg_block = cls(sampling_cfg, embedder)
         self.register_module("agg_block", self._agg_block)
+        if self.train_style_encoder and not isinstance(self._agg_block, st.sViT):
+            raise NotImplementedError(f"train_style_encoder: only the set-ViT (style_agg: svit) has a backward; got {type(self._agg_block).__name__}")
+        if self.train_style_encoder:
+            self._agg_block.repack_on_raw_writes = True      # the fused optimizer writes its parameters through raw pointers
+
+    def _style_encoder_params(self) -> list:
+        return list(self._agg_block.parameters()) if self.train_style_encoder else []
+
+    def _style_encoder_backward(self, dctx) -> None:
+        if self.train_style_encoder and dctx is not None:
+            self._agg_block.backward(dctx.contiguous())
 
     def get_input(self, batch, k, cond_key=None, bs=None, predict_only: Optional[bool] = None, **kwargs):
         """s_zss_dm.py:45-60 over LatentDiffusion.get_input (ddpm.py:656-706). batch tensors are NHWC (LDM_Diffusion.prepare_batch,
@@ -940,7 +979,14 @@ class S_ZSS_DM(LatentDiffusion):
             style_imgs = batch[self.embed_key]
             if bs is not None:
                 style_imgs = style_imgs[:bs]
-            style_features = self._agg_block(style_imgs.to(dev))
+            keep = self.train_style_encoder and self.training
+            if keep:
+                self._agg_block.keep_for_backward = True
+            try:
+                style_features = self._agg_block(style_imgs.to(dev))
+            finally:
+                if keep:
+                    self._agg_block.keep_for_backward = False
         noutputs = [z, {"c_concat": [c], "c_crossattn": [style_features]}]
         noutputs.extend(outputs[2:])
         return noutputs

@@ -69,7 +69,10 @@ class LDM_Diffusion(_Base):
         if isinstance(fs, dict) and isinstance(fs.get("params"), dict) and fs["params"].get("ckpt_path") and hasattr(cfg, "location"):
             fs["params"]["ckpt_path"] = cfg.location.result_dir + "/" + fs["params"]["ckpt_path"]      # ldm_diffusion.py:30
         ldm_dict.pop("ckpt_path", None)
-        self._model = S_ZSS_DM(encoder="swin_v2_t", sampling_cfg=cfg.style_sampling, agg_cfg=cfg.style_agg, cfg=cfg, **ldm_dict)
+        # optional config key (default false: the reference as wired): train the set-ViT style encoder with the U-Net
+        tse = getattr(cfg, "train_style_encoder", False)
+        self._model = S_ZSS_DM(encoder="swin_v2_t", sampling_cfg=cfg.style_sampling, agg_cfg=cfg.style_agg, cfg=cfg,
+                               train_style_encoder=bool(tse), **ldm_dict)
         self.register_module("model", self._model)          # state-dict aliasing of ldm_diffusion.py:38-41: `_model.*` and `model.*`
         self._loss_sum, self._loss_n = None, 0          # device-side accumulator (the reference's MeanMetric, ldm_diffusion.py:44)
         self.predict_dir: Optional[str] = None

@@ -989,6 +989,80 @@ def geglu_bwd(g, dh, dg) -> None:
     check(lib().stedm_geglu_bwd(g.data_ptr(), dh.data_ptr(), dg.data_ptr(), M, g.shape[-1] // 2, _stream()), "stedm_geglu_bwd")
 
 
+def lsa_bwd_ws_floats(B: int, T: int, Tp: int, heads: int) -> int:
+    return lib().stedm_lsa_bwd_ws_floats(B, T, Tp, heads)
+
+
+def lsa_bwd(q, k, vt, d_out, d_qkv, d_temp, qscale: float, B: int, T: int, Tp: int, heads: int, prec: Precision, p: float = 0.0, seed: int = 0,
+            site: int = 0, accumulate_temp: bool = False, ws=None) -> None:
+    """Backward of the LSA attention (vit_set.py:52-66) from the forward's operand planes q, k, vt ((hi, lo) tuples as qkv_pack writes them,
+    lo None: hi only; q scaled by qscale = exp(temperature) * log2 e) and d_out [B*T, heads*64]: d_qkv [B*T, 3*heads*64] in to_qkv's output
+    order, d_temp[0] (+)= sum dS o dots. p, seed, site: the forward's probability dropout (lsa_flash_drop); p == 0: none."""
+    _chk(d_out, name="d_out"); _chk(d_qkv, name="d_qkv"); _chk(d_temp, name="d_temp")
+    assert d_out.numel() == B * T * heads * 64 and d_qkv.numel() == 3 * B * T * heads * 64 and d_temp.numel() == 1
+    for pl, n in ((q, B * heads * Tp * 64), (k, B * heads * Tp * 64), (vt, B * heads * 64 * Tp)):
+        for t in pl:
+            assert t is None or (t.dtype == torch.int16 and t.is_contiguous() and t.numel() == n and t.is_cuda)
+    need = lsa_bwd_ws_floats(B, T, Tp, heads)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.float32, device=d_out.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need and ws.is_contiguous()
+    check(lib().stedm_lsa_bwd(q[0].data_ptr(), _ptr(q[1]), k[0].data_ptr(), _ptr(k[1]), vt[0].data_ptr(), _ptr(vt[1]), d_out.data_ptr(),
+                              d_qkv.data_ptr(), d_temp.data_ptr(), int(accumulate_temp), float(qscale), B, T, Tp, heads, prec.mm_dtype, float(p),
+                              int(seed), int(site), ws.data_ptr(), _stream()), "stedm_lsa_bwd")
+
+
+def gelu_bwd(pre, dh, dpre) -> None:
+    """dpre = dh * gelu'(pre), the exact erf GELU of FeedForward (vit_set.py:24-31)."""
+    _chk(pre, name="pre"); _chk(dh, name="dh"); _chk(dpre, name="dpre")
+    assert pre.numel() == dh.numel() == dpre.numel()
+    check(lib().stedm_gelu_bwd(pre.data_ptr(), dh.data_ptr(), dpre.data_ptr(), pre.numel(), _stream()), "stedm_gelu_bwd")
+
+
+def widen16(hi, lo, out, prec: Precision):
+    """16-bit operand planes (hi, or hi + lo) -> fp32."""
+    _chk(out, name="out")
+    assert hi.dtype == torch.int16 and hi.numel() == out.numel() and (lo is None or lo.numel() == out.numel())
+    check(lib().stedm_widen16(hi.data_ptr(), _ptr(lo), out.data_ptr(), out.numel(), prec.mm_dtype, _stream()), "stedm_widen16")
+    return out
+
+
+def svit_patch_gather(img, rows, patch: int):
+    """The fp32 patch rows [B*ntok, patch*patch*3*ns] that svit_patch_ln16 normalises."""
+    _chk(img, name="style images"); _chk(rows, name="rows")
+    B, ns, H, W, C3 = img.shape
+    assert C3 == 3 and rows.numel() == B * (H // patch) * (W // patch) * patch * patch * 3 * ns
+    check(lib().stedm_svit_patch_gather(img.data_ptr(), B, ns, H, W, patch, rows.data_ptr(), _stream()), "stedm_svit_patch_gather")
+    return rows
+
+
+def svit_tok_bwd(dx, d_pos, d_cls, d_tok, accumulate: bool = False) -> None:
+    """svit_tok_place reversed: dx [B, T, dim] -> d_pos [T, dim], d_cls [dim] (batch sums, (+)=), d_tok [B*(T-2), dim]."""
+    _chk(dx, name="dx"); _chk(d_pos, name="d_pos"); _chk(d_cls, name="d_cls"); _chk(d_tok, name="d_tok")
+    B, T, dim = dx.shape
+    assert d_pos.numel() == T * dim and d_cls.numel() == dim and d_tok.numel() == B * (T - 2) * dim
+    check(lib().stedm_svit_tok_bwd(dx.data_ptr(), d_pos.data_ptr(), d_cls.data_ptr(), d_tok.data_ptr(), B, T - 2, dim, int(accumulate), _stream()),
+          "stedm_svit_tok_bwd")
+
+
+def svit_head_bwd(x, pool: int, ln_w, ln_b, eps: float, w, d_out, dx, d_ln_w, d_ln_b, d_w, d_bias, accumulate: bool = False, ws=None) -> None:
+    """svit_head reversed (pool 0 mean / 1 cls, no c_old): x [B, T, dim], w [ncls, dim], d_out [B, ncls] -> dx [B, T, dim] and the head's
+    parameter gradients ((+)=)."""
+    for t, nm in ((x, "x"), (d_out, "d_out"), (dx, "dx"), (d_ln_w, "d_ln_w"), (d_ln_b, "d_ln_b"), (d_w, "d_w"), (d_bias, "d_bias"), (w, "w")):
+        _chk(t, name=nm)
+    B, T, dim = x.shape
+    ncls = d_out.shape[-1]
+    assert d_out.shape[0] == B and dx.numel() == x.numel() and d_w.numel() == w.numel() == ncls * dim and d_bias.numel() == ncls
+    assert d_ln_w.numel() == dim and d_ln_b.numel() == dim
+    need = lib().stedm_svit_head_bwd_ws_floats(B, dim)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.float32, device=x.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= need and ws.is_contiguous()
+    check(lib().stedm_svit_head_bwd(x.data_ptr(), B, T, dim, pool, ln_w.data_ptr(), ln_b.data_ptr(), float(eps), w.data_ptr(), d_out.data_ptr(), ncls,
+                                    dx.data_ptr(), d_ln_w.data_ptr(), d_ln_b.data_ptr(), d_w.data_ptr(), d_bias.data_ptr(), int(accumulate),
+                                    ws.data_ptr(), _stream()), "stedm_svit_head_bwd")
+
+
 def agg_reduce(feats, out, n: int, mode: int):
     _chk(feats, name="features")
     Bn, Fd = feats.shape

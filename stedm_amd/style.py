@@ -108,6 +108,11 @@ class sViT(nn.Module):
         self.last_dropout_seed = 0
         # to_qkv's epilogue writes the attention's operand planes (single-product modes, no dropout); STEDM_SVIT_FUSE_QKV=0: the separate pack pass
         self.fuse_qkv = os.environ.get("STEDM_SVIT_FUSE_QKV", "1") != "0"
+        # training of the encoder (opt-in): a forward with `keep_for_backward` set also saves the residual stream at the input of every
+        # attention and FeedForward block (two fp32 [B][T][dim] per layer) and the dropout seed it used; `backward` consumes them
+        self.keep_for_backward: bool = False
+        self.repack_on_raw_writes: bool = False       # set by the owner whose optimizer updates this module's parameters in place
+        self._tape: Optional[Dict] = None
 
     # mask stream ids of the dropout sites (include/stedm_hip.h, "train-mode dropout"): site = 8 * layer + kind, the embedding site alone
     SITE_EMB, SITE_ATTN, SITE_OUT, SITE_FF1, SITE_FF2 = 0x10000, 1, 2, 3, 4
@@ -131,7 +136,9 @@ class sViT(nn.Module):
         dev = params[0].device
         if dev.type != "cuda":
             raise StedmHipError("sViT.forward needs its parameters on the GPU; there is no CPU fallback")
-        key = (self.precision, dev, tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
+        # (a trained encoder's parameters are written by the optimizer kernels through raw pointers, which no tensor version counts)
+        key = (self.precision, dev, tuple(p._version for p in params), tuple(p.data_ptr() for p in params),
+               ops.raw_write_epoch() if self.repack_on_raw_writes else 0)
         if key == self._pack_key:
             return
         P = {}
@@ -178,6 +185,13 @@ class sViT(nn.Module):
                 raise NotImplementedError("train-mode dropout is not built for the fp8 attention experiment (prediction-only mode)")
             seed = self.dropout_seed if self.dropout_seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
         self.last_dropout_seed = seed
+        keep = self.keep_for_backward
+        if keep and self.precision.attn_fp8:
+            raise NotImplementedError("keep_for_backward: the fp8 attention mode is prediction-only (no backward)")
+        if keep and (c_old is not None or self.pool not in ("mean", "cls")):
+            raise NotImplementedError("keep_for_backward: the backward is built for pool 'mean' / 'cls' without c_old (all STEDM uses)")
+        self._tape = None
+        xa, xf = [], []
         self._prepare()
         P, prec = self._packed, self.precision
         img = img.float().contiguous()
@@ -216,6 +230,8 @@ class sViT(nn.Module):
         qkv = None if fused_qkv else (self._buf("qkv16", (M, 3 * heads * 64), i16) if q16 else self._buf("qkv", (M, 3 * heads * 64)))
         for l, (attn, ff) in enumerate(self.transformer.layers):
             mlp = ff.fn.net[0].out_features
+            if keep:
+                xa.append(x.clone())
             ops.ln_apply16(x, attn.norm.weight, attn.norm.bias, attn.norm.eps, ln[0], ln[1], prec)
             if fused_qkv:
                 self._gemm(ln, P[f"qkv{l}"], M, 3 * heads * 64, qkv_planes=planes(l))
@@ -243,6 +259,8 @@ class sViT(nn.Module):
                 yd, ym = y.view(-1)[:M * dim].view(M, dim), y.view(-1)[:M * mlp].view(M, mlp)
                 self._gemm(att, P[f"out{l}"], M, dim, bias=attn.fn.to_out[0].bias, out=yd)
                 ops.dropout_rows(yd, p_drop, seed, 8 * l + self.SITE_OUT, prec, res=x, out=x)                  # x = drop(attn(x)) + x
+                if keep:
+                    xf.append(x.clone())
                 ops.ln_apply16(x, ff.norm.weight, ff.norm.bias, ff.norm.eps, ln[0], ln[1], prec)
                 self._gemm(ln, P[f"ff1{l}"], M, mlp, bias=ff.fn.net[0].bias, act_out=2, out=ym)                # GELU(Linear)
                 ops.dropout_rows(ym, p_drop, seed, 8 * l + self.SITE_FF1, prec, hi=h16[0], lo=h16[1])
@@ -250,6 +268,8 @@ class sViT(nn.Module):
                 ops.dropout_rows(yd, p_drop, seed, 8 * l + self.SITE_FF2, prec, res=x, out=x)                  # x = drop(ff(x)) + x
                 continue
             self._gemm(att, P[f"out{l}"], M, dim, bias=attn.fn.to_out[0].bias, res=x, out=x)          # x = attn(x) + x
+            if keep:
+                xf.append(x.clone())
             ops.ln_apply16(x, ff.norm.weight, ff.norm.bias, ff.norm.eps, ln[0], ln[1], prec)
             self._gemm(ln, P[f"ff1{l}"], M, mlp, bias=ff.fn.net[0].bias, act_out=2, out16=h16)       # GELU(Linear)
             self._gemm(h16, P[f"ff2{l}"], M, dim, bias=ff.fn.net[3].bias, res=x, out=x)              # x = ff(x) + x
@@ -257,7 +277,159 @@ class sViT(nn.Module):
         pool = {"mean": 0, "cls": 1, "sum": 2}[self.pool]
         ops.svit_head(x, pool, None if c_old is None else c_old.float().contiguous(), self.mlp_head[0].weight, self.mlp_head[0].bias,
                       self.mlp_head[0].eps, P["head_wt"], self.mlp_head[1].bias, out, ws=self._buf("head.ws", (1024 * dim,)))
+        if keep:
+            self._tape = dict(img=img, xa=xa, xf=xf, x_out=x.clone(), seed=seed, p_emb=p_emb, p_drop=p_drop, fused_qkv=fused_qkv, prec=prec,
+                              B=B, T=T, Tp=Tp, n=n)
         return out
+
+    # ---------------------------------------------------------------------------------------------- backward (opt-in training)
+    def _grad(self, prm: nn.Parameter, accumulate: bool) -> torch.Tensor:
+        if prm.grad is None or prm.grad.dtype != torch.float32 or not prm.grad.is_contiguous():
+            prm.grad = torch.zeros_like(prm, dtype=torch.float32, memory_format=torch.contiguous_format)
+        return prm.grad        # (the kernels overwrite it, or add onto it with accumulate)
+
+    def _colsum(self, mat: torch.Tensor, dst: torch.Tensor, accumulate: bool) -> None:
+        """dst[n] (+)= sum_m mat[m][n] (the bias-sum pair of the training backward: slab partials, folded in a fixed order)"""
+        Mr, N = mat.shape
+        cs = self._buf(f"bwd.cs.{Mr}x{N}", (1, ops.gn_chan_nslab(Mr), N, 2))
+        ops.gn_chan_stats(mat.view(1, Mr, 1, N), cs)
+        ops.chan_sum_fold(cs, None, 0, dst, accumulate)
+
+    def _lin_bwd(self, dy, x32, lin: nn.Linear, dx, accumulate: bool) -> None:
+        """Linear y = x W^T + b reversed in fp32: W.grad (+)= dy^T x, b.grad (+)= column sums of dy, dx = dy W (dx None: skipped)."""
+        beta = 1.0 if accumulate else 0.0
+        # (few output tiles, a contraction over all token rows: the workspace lets the GEMM split K, reduced in a fixed order)
+        ops.gemm_f32(dy, True, x32, False, self._grad(lin.weight, accumulate), beta=beta, ws=self._buf("bwd.gemmws", (1 << 24,)))
+        if lin.bias is not None:
+            self._colsum(dy, self._grad(lin.bias, accumulate), accumulate)
+        if dx is not None:
+            ops.gemm_f32(dy, False, lin.weight.detach(), False, dx)
+
+    @torch.no_grad()
+    def backward(self, d_out, accumulate: bool = False):
+        """Fills `.grad` of every parameter from d_out = dL/d(forward(img)) [B, num_classes], walking the forward kept by
+        `keep_for_backward` in reverse. The normalised / activated operands are recomputed by the forward's own launches (ln_apply16, the
+        GEMMs, qkv_pack, lsa_flash), the dropout masks are regenerated from the kept seed; the Linear gradients run as fp32 GEMMs on the
+        widened operand planes. accumulate: add onto the existing gradients. `to_time_embedding` receives none (t_emb is always None)."""
+        if self.precision.attn_fp8:
+            raise NotImplementedError("sViT.backward: the fp8 attention mode is prediction-only")
+        tape = self._tape
+        if tape is None:
+            raise RuntimeError("sViT.backward: no forward was kept (set keep_for_backward = True and run forward first)")
+        prec = tape["prec"]
+        if prec != self.precision:
+            raise RuntimeError("sViT.backward: the precision changed since the kept forward")
+        self._prepare()
+        P = self._packed
+        B, T, Tp, n, seed, p_emb, p_drop = tape["B"], tape["T"], tape["Tp"], tape["n"], tape["seed"], tape["p_emb"], tape["p_drop"]
+        dim, heads = self.dim, self.heads
+        HD = heads * 64
+        M = B * T
+        i16 = torch.int16
+        lo_ok = prec.npass == 3
+        q16 = prec.npass == 1
+        acc = bool(accumulate)
+        G = lambda prm: self._grad(prm, acc)
+        d_out = d_out.detach().float().contiguous()
+        assert tuple(d_out.shape) == (B, self.mlp_head[1].out_features), "d_out must be [B, num_classes] of the kept forward"
+        planes = lambda nm, shp, zero=False: (self._buf(nm + ".hi", shp, i16, zero=zero), self._buf(nm + ".lo", shp, i16, zero=zero) if lo_ok else None)
+        ln = planes("ln", (M, dim))
+        lnws = self._buf("bwd.lnws", (ops.ln_bwd_ws_floats(M, dim),))
+        # ---- head: out = Linear(LN(pool(x)))
+        dx = self._buf("bwd.dx0", (B, T, dim))
+        dx2 = self._buf("bwd.dx1", (B, T, dim))
+        hl, hn = self.mlp_head[1], self.mlp_head[0]
+        ops.svit_head_bwd(tape["x_out"], {"mean": 0, "cls": 1}[self.pool], hn.weight, hn.bias, hn.eps, hl.weight.detach().float().contiguous(), d_out,
+                          dx, G(hn.weight), G(hn.bias), G(hl.weight), G(hl.bias), accumulate=acc)
+        q, k, vt = planes("q", (B * heads, Tp, 64), True), planes("k", (B * heads, Tp, 64), True), planes("vt", (B * heads, 64, Tp), True)
+        att = planes("att", (M, HD))
+        lsa_ws = self._buf("bwd.lsaws", (ops.lsa_bwd_ws_floats(B, T, Tp, heads),))
+        for l in reversed(range(self.depth)):
+            attn, ff = self.transformer.layers[l]
+            mlp = ff.fn.net[0].out_features
+            # ---- FeedForward: x_out = drop(W2 drop(gelu(W1 LN(x) + b1)) + b2) + x
+            x_in = tape["xf"][l]
+            ops.ln_apply16(x_in, ff.norm.weight, ff.norm.bias, ff.norm.eps, ln[0], ln[1], prec)
+            pre = self._buf("bwd.pre", (M, mlp))
+            self._gemm(ln, P[f"ff1{l}"], M, mlp, bias=ff.fn.net[0].bias, out=pre)                        # the pre-activation (no GELU)
+            h16 = planes("h", (M, mlp))
+            if p_drop > 0:
+                ym = self._buf("bwd.ym", (M, mlp))
+                self._gemm(ln, P[f"ff1{l}"], M, mlp, bias=ff.fn.net[0].bias, act_out=2, out=ym)
+                ops.dropout_rows(ym, p_drop, seed, 8 * l + self.SITE_FF1, prec, hi=h16[0], lo=h16[1])
+            else:
+                self._gemm(ln, P[f"ff1{l}"], M, mlp, bias=ff.fn.net[0].bias, act_out=2, out16=h16)
+            h32 = ops.widen16(h16[0], h16[1], self._buf("bwd.h32", (M, mlp)), prec)
+            dy = dx.view(M, dim)
+            if p_drop > 0:
+                dy = self._buf("bwd.dy", (M, dim))
+                ops.dropout_rows(dx.view(M, dim), p_drop, seed, 8 * l + self.SITE_FF2, prec, out=dy)
+            dh = self._buf("bwd.dh", (M, mlp))
+            self._lin_bwd(dy, h32, ff.fn.net[3], dh, acc)
+            if p_drop > 0:
+                ops.dropout_rows(dh, p_drop, seed, 8 * l + self.SITE_FF1, prec, out=dh)
+            ops.gelu_bwd(pre, dh, dh)
+            ln32 = ops.widen16(ln[0], ln[1], self._buf("bwd.ln32", (M, dim)), prec)
+            dln = self._buf("bwd.dln", (M, dim))
+            self._lin_bwd(dh, ln32, ff.fn.net[0], dln, acc)
+            ops.ln_bwd(x_in.view(M, dim), dln, ff.norm.weight, ff.norm.eps, dx2.view(M, dim), G(ff.norm.weight), G(ff.norm.bias), add=dx.view(M, dim),
+                       accumulate=acc, ws=lnws)
+            dx, dx2 = dx2, dx
+            # ---- LSA: x_out = drop(Wo attention(Wqkv LN(x)) + bo) + x
+            x_in = tape["xa"][l]
+            ops.ln_apply16(x_in, attn.norm.weight, attn.norm.bias, attn.norm.eps, ln[0], ln[1], prec)
+            tau = P[f"tau{l}"]
+            if tape["fused_qkv"]:       # the forward's to_qkv epilogue wrote the planes itself: the same launch gives the same bits
+                self._gemm(ln, P[f"qkv{l}"], M, 3 * HD, qkv_planes=(q[0], k[0], vt[0], T, Tp, heads, tau))
+            else:
+                if q16:
+                    qkv = self._buf("qkv16", (M, 3 * HD), i16)
+                    self._gemm(ln, P[f"qkv{l}"], M, 3 * HD, out16=(qkv, None))
+                else:
+                    qkv = self._buf("qkv", (M, 3 * HD))
+                    self._gemm(ln, P[f"qkv{l}"], M, 3 * HD, out=qkv)
+                ops.qkv_pack(qkv, tau, q, k, vt, B, T, Tp, heads, prec)
+            if p_drop > 0:
+                ops.lsa_flash_drop(q, k, vt, att, B, T, Tp, heads, prec, p_drop, seed, 8 * l + self.SITE_ATTN)
+            else:
+                ops.lsa_flash(q, k, vt, att, B, T, Tp, heads, prec)
+            att32 = ops.widen16(att[0], att[1], self._buf("bwd.att32", (M, HD)), prec)
+            dy = dx.view(M, dim)
+            if p_drop > 0:
+                dy = self._buf("bwd.dy", (M, dim))
+                ops.dropout_rows(dx.view(M, dim), p_drop, seed, 8 * l + self.SITE_OUT, prec, out=dy)
+            datt = self._buf("bwd.datt", (M, HD))
+            self._lin_bwd(dy, att32, attn.fn.to_out[0], datt, acc)
+            dqkv = self._buf("bwd.dqkv", (M, 3 * HD))
+            ops.lsa_bwd(q, k, vt, datt, dqkv, G(attn.fn.temperature), tau, B, T, Tp, heads, prec, p=p_drop, seed=seed, site=8 * l + self.SITE_ATTN,
+                        accumulate_temp=acc, ws=lsa_ws)
+            ln32 = ops.widen16(ln[0], ln[1], self._buf("bwd.ln32", (M, dim)), prec)
+            dln = self._buf("bwd.dln", (M, dim))
+            self._lin_bwd(dqkv, ln32, attn.fn.to_qkv, dln, acc)
+            ops.ln_bwd(x_in.view(M, dim), dln, attn.norm.weight, attn.norm.eps, dx2.view(M, dim), G(attn.norm.weight), G(attn.norm.bias),
+                       add=dx.view(M, dim), accumulate=acc, ws=lnws)
+            dx, dx2 = dx2, dx
+        # ---- embedding: x = drop(cat(cls, 0, tok) + pos_embedding)
+        if p_emb > 0:
+            ops.dropout_rows(dx.view(M, dim), p_emb, seed, self.SITE_EMB, prec, out=dx.view(M, dim))
+        tp = self.to_patch_embedding.to_patch_tokens
+        pd = tp[2].in_features
+        dtok = self._buf("bwd.dtok", (B * n, dim))
+        ops.svit_tok_bwd(dx, G(self.pos_embedding), G(self.cls_token), dtok, accumulate=acc)
+        # ---- SPT: tok = Linear(LN(patch rows))
+        img = tape["img"]
+        pe16 = planes("pe", (B * n, pd))
+        ops.svit_patch_ln16(img, tp[1].weight, tp[1].bias, tp[1].eps, pe16[0], pe16[1], self.patch_size, prec)
+        pe32 = ops.widen16(pe16[0], pe16[1], self._buf("bwd.pe32", (B * n, pd)), prec)
+        dpe = self._buf("bwd.dpe", (B * n, pd))
+        self._lin_bwd(dtok, pe32, tp[2], dpe, acc)
+        rows = ops.svit_patch_gather(img, self._buf("bwd.rows", (B * n, pd)), self.patch_size)
+        ops.ln_bwd(rows, dpe, tp[1].weight, tp[1].eps, pe32, G(tp[1].weight), G(tp[1].bias), accumulate=acc,
+                   ws=self._buf("bwd.lnws.pe", (ops.ln_bwd_ws_floats(B * n, pd),)))        # (d rows lands in pe32: the images need no gradient)
+        for prm in self.to_time_embedding.parameters():                                    # no gradient reaches it (t_emb is always None)
+            g0 = G(prm)
+            if not acc:
+                g0.zero_()
 
 
 # ---------------------------------------------------------------------------------------------------- agg blocks
