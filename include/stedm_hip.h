@@ -653,6 +653,18 @@ long stedm_lsa_bwd_ws_floats(int B, int T, int Tp, int heads);
 int stedm_lsa_bwd(const void* q_hi, const void* q_lo, const void* k_hi, const void* k_lo, const void* vt_hi, const void* vt_lo,
                   const float* d_out, float* d_qkv, float* d_temp, int accumulate_temp, float qscale, int B, int T, int Tp, int heads,
                   int mm_dtype, float p, unsigned long long seed, unsigned site, float* ws, void* stream);
+/* stedm_lsa_bwd16: the same backward on the 16-bit matrix pipe (lsa_bwd16.hip; added within ABI 31 as the entries above), for the
+ * single-product modes: the arguments of stedm_lsa_bwd without the lo planes. Contract (R = round to nearest even into the mode's format):
+ * dOr = R(s dO) with s one exact power of two per call, taken on the device from the biased exponent e of amax |dO|
+ * (s = 2^(clamp(264 - e, 1, 253) - 127): s amax in [2^10, 2^11); all-zero dO: s = 1; the same rule in f16 and bf16) and divided out of the
+ * outputs exactly; Pd = R(P keep / (1 - p)) is the operand of dV, R(dS) that of dQ and dK; everything else fp32 (d_temp: fp64 sums of the
+ * unrounded dS). Bitwise reproducible; pad rows / columns >= T of the planes are replaced by zero before use. ws: stedm_lsa_bwd16_ws_bytes
+ * bytes, 16-byte aligned (amax word | row statistics | fp64 d_temp partials | five 16-bit planes [B*heads][Tp][64]: dOr, dOr^T, q^T, k^T,
+ * vt^T | p > 0: the keep bits as a 1-bit mask, B * heads * Tp * Tp / 8 bytes, written by the query-side kernel for the key side). */
+long stedm_lsa_bwd16_ws_bytes(int B, int T, int Tp, int heads, float p);
+int stedm_lsa_bwd16(const void* q_hi, const void* k_hi, const void* vt_hi, const float* d_out, float* d_qkv, float* d_temp,
+                    int accumulate_temp, float qscale, int B, int T, int Tp, int heads, int mm_dtype, float p, unsigned long long seed,
+                    unsigned site, void* ws, void* stream);
 /* dpre = dh * gelu'(pre), exact erf GELU (FeedForward, vit_set.py:24-31); n elements. */
 int stedm_gelu_bwd(const float* pre, const float* dh, float* dpre, long n, void* stream);
 /* 16-bit operand planes -> fp32: out = hi (+ lo; NULL: none). The operands of the fp32 weight-gradient GEMMs. */

@@ -130,6 +130,8 @@ SIGNATURES = {
     "stedm_lsa_flash_mx8": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "stedm_svit_head": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _I, _P, C.c_long, _P]),
     "stedm_lsa_bwd_ws_floats": (C.c_long, [_I, _I, _I, _I]),
+    "stedm_lsa_bwd16_ws_bytes": (C.c_long, [_I, _I, _I, _I, _F]),
+    "stedm_lsa_bwd16": (_I, [_P, _P, _P, _P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _F, C.c_ulonglong, C.c_uint, _P, _P]),
     "stedm_lsa_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _F, C.c_ulonglong, C.c_uint, _P, _P]),
     "stedm_gelu_bwd": (_I, [_P, _P, _P, C.c_long, _P]),
     "stedm_widen16": (_I, [_P, _P, _P, C.c_long, _I, _P]),

@@ -898,10 +898,12 @@ class S_ZSS_DM(LatentDiffusion):
 
     train_style_encoder (default False: the reference as wired, whose optimizer never sees the aggregation block): with `style_agg: svit`
     the set-ViT is trained with the U-Net — `get_input` in training mode keeps its forward, the training step hands it dL/dc_crossattn
-    (sViT.backward) and its parameters follow `logvar` in the optimizer. Any other aggregation block raises: only the sViT has a backward."""
+    (sViT.backward) and its parameters follow `logvar` in the optimizer. Any other aggregation block raises: only the sViT has a backward.
+    style_lsa_bwd ("f32" | "mfma16", default "f32"): the form of the set-ViT's attention backward (sViT(lsa_bwd=...)); ignored without
+    train_style_encoder."""
 
     def __init__(self, encoder, sampling_cfg, agg_cfg, cfg, *args, embedder: Optional[nn.Module] = None, train_style_encoder: bool = False,
-                 **kwargs):
+                 style_lsa_bwd: str = "f32", **kwargs):
         super().__init__(*args, **kwargs)
         self.train_style_encoder = bool(train_style_encoder)
         from . import style as st
@@ -921,7 +923,7 @@ class S_ZSS_DM(LatentDiffusion):
             data = cfg["data"] if isinstance(cfg, dict) else cfg.data
             img = data["patch_size"] if isinstance(data, dict) else data.patch_size
             ns = get(sampling_cfg, "num_patches") if name(sampling_cfg) == "mp" else 1
-            self._agg_block = st.sViT(image_size=img, num_classes=512, ns=ns, **a)
+            self._agg_block = st.sViT(image_size=img, num_classes=512, ns=ns, lsa_bwd=style_lsa_bwd if self.train_style_encoder else "f32", **a)
         else:
             if embedder is None:
                 # s_zss_dm.py:19-20: `torchvision.models.get_model(encoder)` with its head replaced by Linear(768, 512). The HIP-backed

@@ -1012,6 +1012,33 @@ def lsa_bwd(q, k, vt, d_out, d_qkv, d_temp, qscale: float, B: int, T: int, Tp: i
                               int(seed), int(site), ws.data_ptr(), _stream()), "stedm_lsa_bwd")
 
 
+def lsa_bwd16_ws_bytes(B: int, T: int, Tp: int, heads: int, p: float = 0.0) -> int:
+    return lib().stedm_lsa_bwd16_ws_bytes(B, T, Tp, heads, float(p))
+
+
+def lsa_bwd16(q, k, vt, d_out, d_qkv, d_temp, qscale: float, B: int, T: int, Tp: int, heads: int, prec: Precision, p: float = 0.0, seed: int = 0,
+              site: int = 0, accumulate_temp: bool = False, ws=None) -> None:
+    """lsa_bwd on the 16-bit matrix pipe (csrc/lsa_bwd16.hip) for the single-product modes: same arguments, the hi planes only (q, k, vt:
+    (hi, None) tuples or the hi tensors). Three values are rounded to the mode's format - dO (times one power of two from its amax),
+    P keep / (1 - p) and dS; see include/stedm_hip.h. ws: uint8 workspace of lsa_bwd16_ws_bytes(B, T, Tp, heads, p) bytes."""
+    if prec.npass != 1:
+        raise ValueError("lsa_bwd16 runs the single-product modes (f16, bf16); the parity mode's backward is lsa_bwd")
+    _chk(d_out, name="d_out"); _chk(d_qkv, name="d_qkv"); _chk(d_temp, name="d_temp")
+    assert d_out.numel() == B * T * heads * 64 and d_qkv.numel() == 3 * B * T * heads * 64 and d_temp.numel() == 1
+    hi = []
+    for pl, n in ((q, B * heads * Tp * 64), (k, B * heads * Tp * 64), (vt, B * heads * 64 * Tp)):
+        t = pl[0] if isinstance(pl, (tuple, list)) else pl
+        assert t.dtype == torch.int16 and t.is_contiguous() and t.numel() == n and t.is_cuda
+        hi.append(t)
+    need = lsa_bwd16_ws_bytes(B, T, Tp, heads, p)
+    if ws is None:
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=d_out.device)
+    assert ws.dtype == torch.uint8 and ws.numel() >= need and ws.is_contiguous()
+    check(lib().stedm_lsa_bwd16(hi[0].data_ptr(), hi[1].data_ptr(), hi[2].data_ptr(), d_out.data_ptr(), d_qkv.data_ptr(), d_temp.data_ptr(),
+                                int(accumulate_temp), float(qscale), B, T, Tp, heads, prec.mm_dtype, float(p), int(seed), int(site),
+                                ws.data_ptr(), _stream()), "stedm_lsa_bwd16")
+
+
 def gelu_bwd(pre, dh, dpre) -> None:
     """dpre = dh * gelu'(pre), the exact erf GELU of FeedForward (vit_set.py:24-31)."""
     _chk(pre, name="pre"); _chk(dh, name="dh"); _chk(dpre, name="dpre")

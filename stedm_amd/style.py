@@ -74,8 +74,12 @@ class sViT(nn.Module):
     """Set-ViT style encoder, vit_set.py:109-208. forward(img [B, ns, H, W, 3]) -> [B, num_classes]."""
 
     def __init__(self, *, image_size, patch_size, num_classes, dim, depth, heads, mlp_dim, pool='cls', channels=3, dim_head=64,
-                 dropout=0., emb_dropout=0., ns=5, t_dim=256, precision: str = "parity"):
+                 dropout=0., emb_dropout=0., ns=5, t_dim=256, precision: str = "parity", lsa_bwd: str = "f32"):
         super().__init__()
+        if lsa_bwd not in self.LSA_BWD_FORMS:
+            raise ValueError(f"sViT: lsa_bwd must be one of {self.LSA_BWD_FORMS}, got {lsa_bwd!r}")
+        # form of the attention's backward: "f32" (ops.lsa_bwd, every mode) or "mfma16" (ops.lsa_bwd16: the 16-bit matrix pipe, f16 / bf16 modes)
+        self.lsa_bwd = lsa_bwd
         image_height, image_width = pair(image_size)
         patch_height, patch_width = pair(patch_size)
         assert image_height % patch_height == 0 and image_width % patch_width == 0, \
@@ -116,6 +120,7 @@ class sViT(nn.Module):
 
     # mask stream ids of the dropout sites (include/stedm_hip.h, "train-mode dropout"): site = 8 * layer + kind, the embedding site alone
     SITE_EMB, SITE_ATTN, SITE_OUT, SITE_FF1, SITE_FF2 = 0x10000, 1, 2, 3, 4
+    LSA_BWD_FORMS = ("f32", "mfma16")
 
     # ---------------------------------------------------------------------------------------------- engine
     def set_precision(self, precision):
@@ -313,6 +318,11 @@ class sViT(nn.Module):
         widened operand planes. accumulate: add onto the existing gradients. `to_time_embedding` receives none (t_emb is always None)."""
         if self.precision.attn_fp8:
             raise NotImplementedError("sViT.backward: the fp8 attention mode is prediction-only")
+        if self.lsa_bwd not in self.LSA_BWD_FORMS:
+            raise ValueError(f"sViT: lsa_bwd must be one of {self.LSA_BWD_FORMS}, got {self.lsa_bwd!r}")
+        mfma16 = self.lsa_bwd == "mfma16"
+        if mfma16 and self.precision.npass != 1:
+            raise ValueError("sViT.backward: lsa_bwd='mfma16' runs the single-product modes (f16, bf16); the parity mode's backward is 'f32'")
         tape = self._tape
         if tape is None:
             raise RuntimeError("sViT.backward: no forward was kept (set keep_for_backward = True and run forward first)")
@@ -343,7 +353,10 @@ class sViT(nn.Module):
                           dx, G(hn.weight), G(hn.bias), G(hl.weight), G(hl.bias), accumulate=acc)
         q, k, vt = planes("q", (B * heads, Tp, 64), True), planes("k", (B * heads, Tp, 64), True), planes("vt", (B * heads, 64, Tp), True)
         att = planes("att", (M, HD))
-        lsa_ws = self._buf("bwd.lsaws", (ops.lsa_bwd_ws_floats(B, T, Tp, heads),))
+        if mfma16:
+            lsa_ws = self._buf("bwd.lsaws16", (ops.lsa_bwd16_ws_bytes(B, T, Tp, heads, p_drop),), torch.uint8)
+        else:
+            lsa_ws = self._buf("bwd.lsaws", (ops.lsa_bwd_ws_floats(B, T, Tp, heads),))
         for l in reversed(range(self.depth)):
             attn, ff = self.transformer.layers[l]
             mlp = ff.fn.net[0].out_features
@@ -401,8 +414,8 @@ class sViT(nn.Module):
             datt = self._buf("bwd.datt", (M, HD))
             self._lin_bwd(dy, att32, attn.fn.to_out[0], datt, acc)
             dqkv = self._buf("bwd.dqkv", (M, 3 * HD))
-            ops.lsa_bwd(q, k, vt, datt, dqkv, G(attn.fn.temperature), tau, B, T, Tp, heads, prec, p=p_drop, seed=seed, site=8 * l + self.SITE_ATTN,
-                        accumulate_temp=acc, ws=lsa_ws)
+            (ops.lsa_bwd16 if mfma16 else ops.lsa_bwd)(q, k, vt, datt, dqkv, G(attn.fn.temperature), tau, B, T, Tp, heads, prec, p=p_drop, seed=seed, site=8 * l + self.SITE_ATTN,
+                                                       accumulate_temp=acc, ws=lsa_ws)
             ln32 = ops.widen16(ln[0], ln[1], self._buf("bwd.ln32", (M, dim)), prec)
             dln = self._buf("bwd.dln", (M, dim))
             self._lin_bwd(dqkv, ln32, attn.fn.to_qkv, dln, acc)
